@@ -4,10 +4,21 @@ Mpixels/s (primary + shadow rays) at 1920x1080 on Scene_W4_BunnyScene (Initializ
 state, Combined lighting, shadows on).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S --width W --height H]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-The JSON line has four parts:
+A plain run does what the headline needs and no more: it uploads the scene, warms up (1000
+serialized launches per context, then W steps), times the K steps and prints the JSON line with part 1
+below (`value`, `ms_per_step`, `config`).  `--dump-outputs DIR` also writes the frames the last timed
+step left in HBM, fetched as a caller would fetch them, to DIR/frame.npy (DIR/frame_rank<r>.npy under
+torchrun): float32 R, G, B per pixel, shape (views, H, W, 3), or a fixed seeded sample of pixels where
+that would pass 48 MB.  The scene and cameras are built from constants, so two runs with the same
+arguments render the same inputs.  Everything else — `roofline` (kernel time, FLOP count, PMC
+traffic), `host_gather`, `parity`, `end_to_end_mpix_s` and parts 2-4 — takes runs of its own and is
+measured only with `--full`.
+
+With `--full` the JSON line has four parts:
 
 1. The headline (`value`), `--mode views` by default.  A step renders N views of the scene:
    view f is the reference camera moved 0.05 f along x.  Every view's rows are cut into 16-row
@@ -410,6 +421,28 @@ def parity_report(px: np.ndarray, rgb: np.ndarray, scene: str, width: int, heigh
     return out
 
 
+DUMP_BUDGET = 48 << 20   # bytes of --dump-outputs over all ranks (under the 64 MB a dump may hold)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir: Path, px: np.ndarray, nviews: int, W: int, H: int, rank: int, world: int) -> Path:
+    """--dump-outputs: the timed path's last frames as float32 R, G, B (0..255, exact) per pixel,
+    `frame.npy` (N = 1) or `frame_rank<r>.npy`, shape (views, H, W, 3).  Frames beyond this
+    rank's share of DUMP_BUDGET are cut to a fixed sample of pixels (the same seeded indices
+    in every run, sorted), shape (samples, 3)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rgb = _channels(px).astype(np.float32)
+    keep = DUMP_BUDGET // world // 12
+    if rgb.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rgb.shape[0], keep, replace=False))
+        rgb = rgb[idx]
+    else:
+        rgb = rgb.reshape(nviews, H, W, 3)
+    f = out_dir / ("frame.npy" if world == 1 else f"frame_rank{rank}.npy")
+    np.save(f, rgb)
+    return f
+
+
 # ---------------------------------------------------------------------------- one workload
 class Workload:
     """One scene x size x mode on this rank's contexts: the timed regions, the algorithmic
@@ -489,7 +522,18 @@ class Workload:
         flop = int(sum(int(c) * w for c, w in zip(counts[:12], COST))) + int(counts[14]) * COST_CULL_TEST
         return flop, [int(x) for x in counts]
 
-    def run(self, steps: int, warmup: int, launches: int, gather: bool, tag: str) -> dict:
+    def last_frames(self, steps: int) -> np.ndarray:
+        """What the last of `steps` timed steps left in HBM, fetched as a caller would
+        (rtx_gather_async of the context that rendered it): the packed XRGB pixels of this
+        rank's rows of every view, the other ranks' rows zero."""
+        c = self.ctxs[(steps - 1) % len(self.ctxs)]
+        px = np.zeros(self.nviews * self.W * self.H, np.uint32)
+        c.gather_async(px)
+        c.synchronize()
+        return px
+
+    def run(self, steps: int, warmup: int, launches: int, gather: bool, tag: str, full: bool = True,
+            dump_to: Path | None = None) -> dict:
         d, W, H = self.d, self.W, self.H
         # untimed: serialized launches on EVERY context (each context's tile schedule measured and its
         # split threshold tuned before its frames go in flight), which also bring the GPU clock up
@@ -499,6 +543,11 @@ class Workload:
             self.step(i)
         self.sync_all()
         elapsed = self.timed(self.step, steps)          # device-resident frames (`value`)
+        if dump_to is not None:
+            dump_outputs(dump_to, self.last_frames(steps), self.nviews, W, H, d.rank, d.world)
+        if not full:
+            return {"elapsed": elapsed, "value": self.frame_pixels * steps / elapsed / 1e6,
+                    "ms_per_step": elapsed / steps * 1e3}
         # timed after the steps: a fresh process starts the GPU at its idle clock, whose ramp a mean
         # taken first would include ("Short runs and the GPU clock")
         kernel_ms = self.kernel_ms(launches)
@@ -674,7 +723,14 @@ def main() -> int:
     ap.add_argument("--inflight", type=int, default=2, help="frames in flight (render contexts per GPU)")
     ap.add_argument("--inflight-frame", type=int, default=3,
                     help="frames in flight for the one-frame-per-step workloads (multi_gpu_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline (kernel time, FLOP count, PMC traffic), host "
+                         "gather, parity, end-to-end frame, multi_gpu_configs, parity_configs, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path, default=None,
+                    help="write the frames of the last timed step to DIR/frame.npy (float32 R, G, B per pixel)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # RTX_BENCH_DEVICE pins every rank to one device: rehearsing the N-rank path on a one-GPU
     # machine (the driver's multi-GPU runs leave it unset: rank r -> device LOCAL_RANK)
@@ -690,7 +746,42 @@ def main() -> int:
 
     # ---- 1. headline
     hw = Workload(ctxs, d, args.scene, W, H, args.mode)
-    hr = hw.run(args.steps, args.warmup, K_KERNEL_LAUNCHES, not args.no_gather, tag + "_h")
+    hr = hw.run(args.steps, args.warmup, K_KERNEL_LAUNCHES, not args.no_gather, tag + "_h", full=args.full,
+                dump_to=args.dump_outputs)
+    strong = args.mode == "frame"
+    out = {
+        "metric": "Mpixels/s (primary+shadow rays) at 1920x1080; per-channel max-abs vs CPU ref",
+        "value": round(hr["value"], 3),
+        "unit": "Mpixels/s",
+        "n_gpus": N,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(hr["ms_per_step"], 5),
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": f"synthetic: the reference's {args.scene} scene (Initialize state) built by the host scene layer; "
+                "no datasets",
+        "config": {"workload": (f"{args.scene} {W}x{H}, Combined lighting, shadows on, one frame per step"
+                                if N == 1 else
+                                f"{args.scene} {W}x{H}, Combined lighting, shadows on, one frame per step tiled "
+                                f"over {N} ranks in 16-row stripes" if strong else
+                                f"{args.scene} {W}x{H}, Combined lighting, shadows on, {N} views per step, each "
+                                f"tiled over the {N} ranks in 16-row stripes"),
+                   "scene": args.scene, "width": W, "height": H, "views_per_step": hw.nviews,
+                   "stripe_rows": 16 if N > 1 else 0,
+                   "parallelism": f"image stripes x{N} (no collective)", "frames_in_flight": len(ctxs)},
+        "full": args.full,
+    }
+    if not args.full:
+        # the plain run: the headline and nothing that takes a run of its own
+        if d.rank == 0:
+            print(json.dumps(out), flush=True)
+        for c in ctxs:
+            c.close()
+        d.close()
+        return 0
 
     # End-to-end single frame through the blocking C-ABI entry into pageable memory (N = 1).
     e2e = None
@@ -806,30 +897,7 @@ def main() -> int:
                          "FLOP = SURVEY §8(d) algorithmic model counted by the instrumented kernel; "
                          "kernel_ms/achieved are rank 0's launches (mean of kernel_launches serialized launches, "
                          "timed after the timed steps, the clock up)"})
-    strong = args.mode == "frame"
-    out = {
-        "metric": "Mpixels/s (primary+shadow rays) at 1920x1080; per-channel max-abs vs CPU ref",
-        "value": round(hr["value"], 3),
-        "unit": "Mpixels/s",
-        "n_gpus": N,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(hr["ms_per_step"], 5),
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": f"synthetic: the reference's {args.scene} scene (Initialize state) built by the host scene layer; "
-                "no datasets",
-        "config": {"workload": (f"{args.scene} {W}x{H}, Combined lighting, shadows on, one frame per step"
-                                if N == 1 else
-                                f"{args.scene} {W}x{H}, Combined lighting, shadows on, one frame per step tiled "
-                                f"over {N} ranks in 16-row stripes" if strong else
-                                f"{args.scene} {W}x{H}, Combined lighting, shadows on, {N} views per step, each "
-                                f"tiled over the {N} ranks in 16-row stripes"),
-                   "scene": args.scene, "width": W, "height": H, "views_per_step": hw.nviews,
-                   "stripe_rows": 16 if N > 1 else 0,
-                   "parallelism": f"image stripes x{N} (no collective)", "frames_in_flight": len(ctxs)},
+    out.update({
         "roofline": roof,
         "cpu_baseline": cpu,
         "parity": parity,
@@ -837,7 +905,7 @@ def main() -> int:
         "end_to_end_mpix_s": round(e2e, 3) if e2e else None,
         "multi_gpu_configs": multi,
         "parity_configs": pconf,
-    }
+    })
     if pconf is not None:
         out["parity_configs_all_ok"] = all(p.get("ok", False) for p in pconf)
     if cpu and cpu.get("value"):

@@ -124,10 +124,18 @@ def build_checkers(force: bool = False) -> Path:
     return out
 
 
+def have_reference() -> bool:
+    """The reference's sources are there and this user may read them."""
+    try:
+        return (REFERENCE / "source" / "Scene.cpp").exists()
+    except OSError:   # a directory on the way is closed to this user: as good as absent
+        return False
+
+
 def build_reference(force: bool = False) -> Path | None:
     """Test infrastructure: the reference's own sources compiled in place (oracle/ref)."""
     out = ORACLE / "_ref" / "ref_harness"
-    if not (REFERENCE / "source" / "Scene.cpp").exists():
+    if not have_reference():
         return out if out.exists() else None
     if force and (ORACLE / "_ref").exists():
         shutil.rmtree(ORACLE / "_ref")

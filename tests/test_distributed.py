@@ -97,7 +97,7 @@ def test_bench_two_ranks_hip_shmctl(mode, tmp_path):
     port = 29700 + os.getpid() % 200 + (0 if mode == "views" else 1)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(root / "bench.py"), "--gpus", str(world),
-           "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--mode", mode]
+           "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--mode", mode]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-4000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -154,9 +154,49 @@ def test_bench_control_plane_shm(world):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_headline_only_and_dumps_its_frame(tmp_path):
+    """The plain command (`bench.py --gpus 1 --steps 7 --warmup 2 --dump-outputs DIR`): one JSON line
+    with the headline's fields and none of the legs that take runs of their own (those need --full);
+    `value` = pixels / ms_per_step over the 7 timed steps; DIR/frame.npy is the frame the last timed
+    step left in HBM as float32 R, G, B, equal to the reference's own frame bit for bit
+    (tests/golden/config_W4_Bunny_1920x1080.npz, SHA-256 of the packed pixels)."""
+    import hashlib
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+           "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-4000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in r, k
+    assert r["n_gpus"] == 1 and r["steps"] == 7 and r["warmup"] == 2 and r["higher_is_better"] is True
+    assert r["unit"] == "Mpixels/s" and r["dtype"] == "f32" and r["full"] is False
+    assert abs(r["value"] - 1920 * 1080 / (r["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * r["value"]
+    for k in ("roofline", "cpu_baseline", "parity", "host_gather", "end_to_end_mpix_s", "multi_gpu_configs",
+              "parity_configs"):
+        assert k not in r, k
+    assert [f.name for f in dump.iterdir()] == ["frame.npy"]
+    frame = np.load(dump / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (1, 1080, 1920, 3)
+    c = frame.astype(np.uint32).reshape(-1, 3)
+    assert np.array_equal(c.astype(np.float32), frame.reshape(-1, 3)) and int(c.max()) <= 255
+    px = (c[:, 0] << 16) | (c[:, 1] << 8) | c[:, 2]
+    g = np.load(root / "tests" / "golden" / "config_W4_Bunny_1920x1080.npz")
+    assert hashlib.sha256(px.astype("<u4").tobytes()).hexdigest() == str(g["sha_pixels"][0])
+
+
+@pytest.mark.gpu
 def test_bench_one_gpu_contract(tmp_path):
-    """The driver's N = 1 command (`bench.py --gpus 1 --steps 20 --warmup 5`, here with a 1-frame CPU
-    sample): one JSON line with the contract's fields; `value` = pixels / ms_per_step; the roofline
+    """The driver's N = 1 command with everything measured (`bench.py --gpus 1 --steps 20 --warmup 5
+    --full`, here with a 1-frame CPU sample): one JSON line with the contract's fields; `value` = pixels / ms_per_step; the roofline
     object; the CPU baseline and `speedup_vs_cpu` against its best configuration; every extra
     workload with its parity and the one-GPU strong-scaling predictor (efficiency = t_full / (s x the
     slowest share)); the culled lines' `frac` counts the work the culled walk executes, the
@@ -166,7 +206,8 @@ def test_bench_one_gpu_contract(tmp_path):
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
-    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-frames", "1"]
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full",
+           "--cpu-frames", "1"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-4000:]
     r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

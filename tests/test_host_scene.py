@@ -12,7 +12,7 @@ from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene, parse_obj, RENDERABLE, SCENES
 
 G = Path(__file__).resolve().parent / "golden"
-REF_RES = Path("/root/reference/source/Resources")
+REF_RES = G / "obj"
 
 
 def _u(a):
@@ -81,9 +81,9 @@ def test_mesh_assets_match_parseobj(stem, tmp_path):
     assert np.array_equal(_u(d["normals"]), _u(g["normals"]))
 
 
-@pytest.mark.skipif(not REF_RES.exists(), reason="reference resources only in the build container")
 @pytest.mark.parametrize("stem", ["lowpoly_bunny2", "Assignment3D1", "simple_object", "simple_cube", "simple_quad"])
 def test_parse_obj_on_reference_files(stem):
+    """The reference's own mesh files (tests/golden/obj/, byte for byte its Resources/*.obj)."""
     g = np.load(G / f"obj_{stem}.npz")
     d = parse_obj(REF_RES / f"{stem}.obj")
     assert np.array_equal(_u(d["positions"]), _u(g["positions"]))

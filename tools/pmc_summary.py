@@ -36,7 +36,7 @@ rec = {"counters": out, "derived": derived, "dispatch": meta}
 if len(sys.argv) > 2:
     rec = {"kernel": "rtx_render_kernel<false, 0>",
            "config": {"scene": "W4_Bunny", "width": 1920, "height": 1080, "views": 1},
-           "command": "rocprofv3 --pmc <group> -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline "
+           "command": "rocprofv3 --pmc <group> -- python3 bench.py --steps 20 --warmup 2 --full --no-cpu-baseline "
                       "(tools/profile.sh, one group per pass)",
            **rec,
            "hbm_bytes_per_launch": int(round((2 * out["FETCH_SIZE"] + out["WRITE_SIZE"]) * 1024)),
