@@ -4,7 +4,7 @@
 //
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
-//              [--device-update]
+//              [--device-update] [--ss K]
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -12,6 +12,7 @@
 // ">> HIGH/LOW/AVG" on stdout and benchmark.txt in the reference's format.  Animated
 // scenes are re-uploaded after every Update; the per-stage means are printed as well.
 // --inflight F (default 2) overlaps F frames (run_benchmark); 1 = the serial loop.
+// --ss K (1, 2, 4 or 8; default 1) renders K x K samples per pixel (rtx_set_supersample).
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -129,7 +130,7 @@ private:
 // `<stem>_<k>.bmp` when it completes (the pipelined loop's frames, checked by the tests).
 int run_benchmark(rtx::Renderer& r, rtx_host_scene* hs, int windows, int inflight, bool device_update,
                   const std::vector<float>* seq = nullptr, const std::string& stem = "",
-                  const std::vector<rtx_host_scene*>& extra = {}) {
+                  const std::vector<rtx_host_scene*>& extra = {}, uint32_t ss = 1) {
     const bool animated = rtx_host_scene_animated(hs) == 1;
     // (pipelined host side) D = the snapshot scenes: `hs` is the chain the worker updates, frame k is
     // uploaded from snapshot extra[k % D]
@@ -144,6 +145,7 @@ int run_benchmark(rtx::Renderer& r, rtx_host_scene* hs, int windows, int infligh
             for (size_t i = 1; i < ctx.size(); ++i) rtx_destroy(ctx[i]);
             return 1;
         }
+        rtx_set_supersample(c, ss);   // (main checked the factor)
         ctx.push_back(c);
     }
     std::vector<std::vector<uint32_t>> buf(inflight, std::vector<uint32_t>(npx));
@@ -296,12 +298,12 @@ int run_benchmark(rtx::Renderer& r, rtx_host_scene* hs, int windows, int infligh
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
-                             "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update]\n",
+                             "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K]\n",
                      argv[0]);
         return 2;
     }
     std::string scene = argv[1], out = "RayTracing_Buffer.bmp", assets;
-    int W = 640, H = 480, mode = 3, frames = 1, bench = 0, inflight = 2;
+    int W = 640, H = 480, mode = 3, frames = 1, bench = 0, inflight = 2, ss = 1;
     std::vector<float> seq;
     float t = -1.f;
     bool shadows = true, device_update = false;
@@ -322,6 +324,13 @@ int main(int argc, char** argv) {
         }
         else if (a == "--inflight" && i + 1 < argc) inflight = std::max(1, std::min(8, std::atoi(argv[++i])));
         else if (a == "--device-update") device_update = true;
+        else if (a == "--ss") {   // checked here: a bad factor ends the program before any device work
+            ss = i + 1 < argc ? std::atoi(argv[++i]) : 0;
+            if (ss != 1 && ss != 2 && ss != 4 && ss != 8) {
+                std::fprintf(stderr, "--ss: the supersample factor must be 1, 2, 4 or 8\n");
+                return 2;
+            }
+        }
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
         else if (a == "--benchmark") bench = (i + 1 < argc && std::atoi(argv[i + 1]) > 0) ? std::atoi(argv[++i]) : 10;
@@ -355,19 +364,20 @@ int main(int argc, char** argv) {
         rtx::Renderer r(W, H);
         r.m_CurrentLightingMode = static_cast<rtx::Renderer::LightingMode>(mode);
         r.m_ShadowsEnabled = shadows;
+        r.SetSupersample(static_cast<uint32_t>(ss));
         if (!seq.empty()) {
             // --sequence t1,...: the pipelined frame loop over fixed Update times, frame k
             // written to <out stem>_<k>.bmp
             const std::string stem = out.size() > 4 && out.substr(out.size() - 4) == ".bmp" ? out.substr(0, out.size() - 4) : out;
             const std::vector<rtx_host_scene*> more = more_scenes();
-            rc = run_benchmark(r, hs, 0, inflight, device_update, &seq, stem, more);
+            rc = run_benchmark(r, hs, 0, inflight, device_update, &seq, stem, more, static_cast<uint32_t>(ss));
             for (rtx_host_scene* h : more) rtx_host_scene_destroy(h);
             rtx_host_scene_destroy(hs);
             return rc;
         }
         if (bench) {
             const std::vector<rtx_host_scene*> more = more_scenes();
-            rc = run_benchmark(r, hs, bench, inflight, device_update, nullptr, "", more);
+            rc = run_benchmark(r, hs, bench, inflight, device_update, nullptr, "", more, static_cast<uint32_t>(ss));
             for (rtx_host_scene* h : more) rtx_host_scene_destroy(h);
         } else {
             r.Render(hs, true);

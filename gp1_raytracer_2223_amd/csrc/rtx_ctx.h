@@ -54,6 +54,9 @@ struct rtx_ctx {
     uint32_t* d_px = nullptr;
     float* d_rgb = nullptr;
     size_t px_cap = 0, rgb_cap = 0;
+    // supersampling (rtx_set_supersample): log2 of the k x k samples per pixel of every later frame;
+    // the frame buffer stays width x height per view (FrameArgs::ss_log2)
+    uint32_t ss_log2 = 0;
     unsigned long long* d_counters = nullptr;
     // last render
     // cost-ordered tile dispatch
@@ -106,6 +109,7 @@ struct rtx_ctx {
     int join_views = 0;
     uint64_t join_gen = 0;
     int join_sb = -1;
+    uint32_t join_ss = 0;
     const uint32_t* join_heavy = nullptr;
     uint32_t join_heavy_n = 0;
     // the split frames' interval in flight on this context's stream (inflight_onepiece): 0 skipping

@@ -167,6 +167,24 @@ extern "C" int rtx_group_upload_scene(rtx_group* g, const rtx_scene* s) {
     return run_job(g);
 }
 
+extern "C" int rtx_group_set_supersample(rtx_group* g, uint32_t k) {
+    if (!g) return RTX_E_INVALID;
+    // (host state only, no job: the members are idle between rtx_group_* calls.  The factor is checked
+    // before any member changes, so a refused one leaves every member at the previous factor.)
+    if (k != 1 && k != 2 && k != 4 && k != 8) {
+        g->err = "supersample factor must be 1, 2, 4 or 8 (got " + std::to_string(k) + ")";
+        return RTX_E_INVALID;
+    }
+    for (rtx_ctx* c : g->ctx) {
+        const int rc = rtx_set_supersample(c, k);
+        if (rc != RTX_OK) {
+            g->err = rtx_last_error(c);
+            return rc;
+        }
+    }
+    return RTX_OK;
+}
+
 extern "C" int rtx_group_render(rtx_group* g, const rtx_camera* cam, const rtx_render_params* p, uint32_t* out_px,
                                 float* out_rgb) {
     if (!g || !cam || !p || !out_px) return RTX_E_INVALID;

@@ -887,6 +887,10 @@ __device__ __forceinline__ uint32_t q8(float c) {
 // W4_Optional's variant 231 -> 223 us.  The variant with spheres and meshes stays at 7 (8: +4 %).
 // CULLK: the variant with the exact cull (DevScene::cull; launched only for scenes that have the
 // records — the code of the cull paths costs the kernel without them registers and 8 %).
+// SS: the variant of a supersampled frame (FrameArgs::ss_log2 > 0) for the phases with the output
+// epilogue (0, 3, 6): the frame is the sample frame and the epilogue resolves each pixel's k x k
+// samples across the wave.  A variant of its own so that the plain kernels stay the code they were
+// (as a run-time branch it moved their VGPR counts by 1-2: profiles/ss/resource_usage.txt).
 #define f_mode (kComb ? RTX_MODE_COMBINED : F.mode)
 #define f_shadows (kComb ? 1 : F.shadows)
 #define n_sph (kNoSph ? 0u : S.n_spheres)
@@ -905,7 +909,52 @@ __device__ __forceinline__ void part_stat(const FrameArgs& F, uint32_t part, uin
               static_cast<uint32_t>(d < 0xffffffffull ? d : 0xffffffffull));
 }
 
-template <bool COUNT, int PHASE, bool DEEP, int SPEC, bool HSTK, bool CULLK>
+// Supersampling resolve (FrameArgs::ss_log2): v + the value of lane ^ X, in every lane
+// of the wave (all 64 must execute it), without LDS.  fp32 addition commutes, so both lanes of a pair
+// get the same bits and an xor butterfly is the adjacent-pair tree.  The exchanges:
+//   X = 1, 2   DPP quad_perm [1,0,3,2] / [2,3,0,1]
+//   X = 4      DPP row_half_mirror (lane i of 8 reads 7 - i): the other quad of the 8, whose four
+//              lanes hold one value after the X = 1 and 2 levels, which always precede this one
+//   X = 8      DPP row_ror:8 (a rotation of the 16-lane row by half of it)
+//   X = 16, 32 v_permlane16_swap / v_permlane32_swap of v with itself: the two results are the even
+//              and the odd rows' (the lower and the upper half's) value in both of them
+template <int X>
+__device__ __forceinline__ float ss_add_xor(float v) {
+    const int i = __float_as_int(v);
+    if constexpr (X < 16) {
+        constexpr int kCtrl = X == 1 ? 0xB1 : (X == 2 ? 0x4E : (X == 4 ? 0x141 : 0x128));
+        // (every lane of these controls has a source lane: bound_ctrl and the old value never apply,
+        // and with them set so the exchange folds into the add as its DPP operand)
+        return v + __int_as_float(__builtin_amdgcn_update_dpp(0, i, kCtrl, 0xf, 0xf, true));
+    } else if constexpr (X == 16) {
+        const auto r = __builtin_amdgcn_permlane16_swap(static_cast<uint32_t>(i), static_cast<uint32_t>(i), false, false);
+        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    } else {
+        const auto r = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(i), static_cast<uint32_t>(i), false, false);
+        return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+}
+template <int X>
+__device__ __forceinline__ void ss_add_xor3(float& r, float& g, float& b) {
+    r = ss_add_xor<X>(r); g = ss_add_xor<X>(g); b = ss_add_xor<X>(b);
+}
+// The tree of a pixel's k x k samples, k = 1 << n (n = 1..3, wave-uniform), in every lane of the pixel:
+// the levels along x (lane bits 0..n-1) and then along y (lane bits 3..3+n-1); the wave tile's lanes
+// are row-major, px = lane & 7, py = lane >> 3.  One straight line of exchanges per factor.
+__device__ __forceinline__ void ss_tree(uint32_t n, float& r, float& g, float& b) {
+    ss_add_xor3<1>(r, g, b);
+    if (n == 1) {
+        ss_add_xor3<8>(r, g, b);
+        return;
+    }
+    ss_add_xor3<2>(r, g, b);
+    if (n == 3) ss_add_xor3<4>(r, g, b);
+    ss_add_xor3<8>(r, g, b);
+    ss_add_xor3<16>(r, g, b);
+    if (n == 3) ss_add_xor3<32>(r, g, b);
+}
+
+template <bool COUNT, int PHASE, bool DEEP, int SPEC, bool HSTK, bool CULLK, bool SS>
 __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& F, uint32_t widx, uint32_t tile,
                                             uint32_t part, uint32_t light, uint4* stk, unsigned long long* sT,
                                             float (*pnum)[64], uint32_t lane) {
@@ -1366,7 +1415,25 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     // ColorRGB::MaxToOne (ColorRGB.h:12-17)
     const float mv = smax(fr, smax(fg, fb));
     if (mv > 1.f) { fr /= mv; fg /= mv; fb /= mv; }
-    if (valid) {
+    if constexpr (SS) {
+        // Supersampled frame: this lane's sample is (px & (k - 1), py & (k - 1)) of pixel (px / k, py / k),
+        // k = 1 << ss_log2 dividing the tile's 8, so the wave holds every sample of its pixels and a
+        // pixel's samples are valid together.  The box filter: per channel the adjacent-pair tree over
+        // sx, then over sy, times the exact 1 / (k * k); the pixel's first lane stores it.
+        const uint32_t n = uni(F.ss_log2);
+        ss_tree(n, fr, fg, fb);
+        const float w = __uint_as_float((127u - 2u * n) << 23);   // 2^(-2 log2 k)
+        fr *= w; fg *= w; fb *= w;
+        const uint32_t m = (1u << n) - 1u;
+        if (valid && ((lane | (lane >> 3)) & m) == 0) {
+            const size_t o = (static_cast<size_t>(view) * F.out_height + (static_cast<uint32_t>(py) >> n)) * F.out_width +
+                             (static_cast<uint32_t>(px) >> n);
+            F.out_px[o] = (q8(fr) << F.rshift) | (q8(fg) << F.gshift) | (q8(fb) << F.bshift) | F.amask;
+            if (F.out_rgb) {
+                F.out_rgb[3 * o] = fr; F.out_rgb[3 * o + 1] = fg; F.out_rgb[3 * o + 2] = fb;
+            }
+        }
+    } else if (valid) {
         const size_t o = static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
                          static_cast<size_t>(px);
         F.out_px[o] = (q8(fr) << F.rshift) | (q8(fg) << F.gshift) | (q8(fb) << F.bshift) | F.amask;
@@ -1407,10 +1474,18 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
 }
 
 
-template <bool COUNT, int PHASE, bool DEEP = false, int SPEC = 0, bool HSTK = false, bool CULLK = false>
+// The one SS variant built for 7 waves per SIMD where its plain twin has 8: PHASE 0 of the Lambert +
+// Cook-Torrance one-mesh kernel with the cull (W4_Optional) fills the 64 VGPRs of 8 waves exactly, and
+// the SS epilogue's one more live VGPR put 3 VGPRs into scratch around the light loop.
+template <int PHASE, int SPEC, bool CULLK, bool SS>
+constexpr bool kSsSevenWaves = SS && CULLK && PHASE == 0 && (SPEC & kSpecKindCT) != 0 && (SPEC & kSpecOneMesh) != 0;
+
+template <bool COUNT, int PHASE, bool DEEP = false, int SPEC = 0, bool HSTK = false, bool CULLK = false,
+          bool SS = false>
 __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
                                                   : ((SPEC & (kSpecOneMesh | kSpecNoMesh))
-                                                         ? RTX_SPEC_WAVES
+                                                         ? (kSsSevenWaves<PHASE, SPEC, CULLK, SS> ? RTX_SPEC_WAVES_PARTIAL
+                                                                                                  : RTX_SPEC_WAVES)
                                                          : (SPEC ? RTX_SPEC_WAVES_PARTIAL : RTX_MIN_WAVES_PER_EU)))
     rtx_render_kernel(const DevScene S, const FrameArgs F) {
     constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
@@ -1447,7 +1522,7 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
             const uint32_t k = it / L;
             tile = F.order ? ldc(F.order, k) : k;
             if (F.heavy_flag && ldc(F.heavy_flag, tile)) continue;
-            render_tile<COUNT, PHASE, DEEP, SPEC, HSTK, CULLK>(S, F, it, tile, 0u, it - k * L, stk, sT, pnumS[wave],
+            render_tile<COUNT, PHASE, DEEP, SPEC, HSTK, CULLK, SS>(S, F, it, tile, 0u, it - k * L, stk, sT, pnumS[wave],
                                                                lane);
         }
         return;
@@ -1461,7 +1536,7 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
         light = blockIdx.z;
         tile = ldc(F.heavy_list, widx);
     }
-    render_tile<COUNT, PHASE, DEEP, SPEC, HSTK, CULLK>(S, F, widx, tile, part, light, stk, sT, pnumS[wave], lane);
+    render_tile<COUNT, PHASE, DEEP, SPEC, HSTK, CULLK, SS>(S, F, widx, tile, part, light, stk, sT, pnumS[wave], lane);
 }
 
 #undef f_mode
@@ -2923,10 +2998,20 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
     const bool striped = p->stripe_rows != 0 && p->stripe_step > 1;
     if (striped && (p->stripe_rows % 16 != 0 || p->stripe_first >= p->stripe_step))
         return fail(c, RTX_E_INVALID, "stripe_rows must be a multiple of 16 and stripe_first < stripe_step");
+    // Supersampling (rtx_set_supersample): the launch renders the k*width x k*height sample frame `sp`
+    // (the reference's frame of that size; stripes stay output rows, k*stripe_rows sample rows: whole
+    // wave-tile rows) and resolves it into the width x height frame buffer.  The sample frame's sides
+    // stay inside div_rn's divisor domain like a plain frame's.
+    const uint32_t ss = c->ss_log2;
+    if ((static_cast<uint64_t>(p->width) << ss) > 65536 || (static_cast<uint64_t>(p->height) << ss) > 65536)
+        return fail(c, RTX_E_INVALID, "bad image size: supersampled " + std::to_string(1u << ss) + "x" +
+                                          std::to_string(1u << ss) + ", the sample frame exceeds 65536 per side");
+    rtx_render_params sp = *p;
+    sp.width <<= ss; sp.height <<= ss; sp.stripe_rows <<= ss;
     const size_t npx = static_cast<size_t>(p->width) * p->height * static_cast<size_t>(n_views);
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->join_pending &&
-        !(n_views == c->join_views && c->scene_gen == c->join_gen && c->sb_cur == c->join_sb &&
+        !(n_views == c->join_views && c->scene_gen == c->join_gen && c->sb_cur == c->join_sb && ss == c->join_ss &&
           std::memcmp(p, &c->join_p, sizeof *p) == 0 &&
           std::memcmp(cams, c->join_cams, sizeof(rtx_camera) * static_cast<size_t>(n_views)) == 0)) {
         const int rc = join_split(c);
@@ -2937,6 +3022,7 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
     c->join_views = n_views;
     c->join_gen = c->scene_gen;
     c->join_sb = c->sb_cur;
+    c->join_ss = ss;
     if (npx > c->px_cap) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         (void)hipFree(c->d_px);
@@ -2984,24 +3070,25 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
         }
     }
     F.n_views = static_cast<uint32_t>(n_views);
-    F.aspect = static_cast<int>(p->width) / static_cast<float>(static_cast<int>(p->height));  // Renderer.cpp:30
-    F.inv_width = 1.f / static_cast<float>(static_cast<int>(p->width));
-    F.inv_height = 1.f / static_cast<float>(static_cast<int>(p->height));
-    F.width = p->width; F.height = p->height;
+    F.aspect = static_cast<int>(sp.width) / static_cast<float>(static_cast<int>(sp.height));  // Renderer.cpp:30
+    F.inv_width = 1.f / static_cast<float>(static_cast<int>(sp.width));
+    F.inv_height = 1.f / static_cast<float>(static_cast<int>(sp.height));
+    F.width = sp.width; F.height = sp.height;
+    F.ss_log2 = ss; F.out_width = p->width; F.out_height = p->height;
     F.mode = p->lighting_mode; F.shadows = p->shadows_enabled ? 1 : 0;
     F.rshift = p->format.rshift; F.gshift = p->format.gshift; F.bshift = p->format.bshift; F.amask = p->format.amask;
-    const uint32_t groups = (p->height + kWaveTile - 1) / kWaveTile;
+    const uint32_t groups = (sp.height + kWaveTile - 1) / kWaveTile;
     uint32_t gy = groups;
     if (striped) {
         // every view owns the same number of stripes only if the stripe count divides
         // evenly; size the grid for the largest owner and let the kernel skip the rest
-        const uint32_t gps = p->stripe_rows / kWaveTile;
+        const uint32_t gps = sp.stripe_rows / kWaveTile;
         const uint32_t nstripes = (groups + gps - 1) / gps;
         const uint32_t owned = (nstripes + p->stripe_step - 1) / p->stripe_step;
         F.groups_per_stripe = gps; F.stripe_first = p->stripe_first; F.stripe_step = p->stripe_step;
         gy = owned * gps;
     }
-    F.tiles_x = (p->width + kWaveTile - 1) / kWaveTile;
+    F.tiles_x = (sp.width + kWaveTile - 1) / kWaveTile;
     F.tiles_y = gy;
     F.out_px = c->d_px;
     F.out_rgb = want_rgb ? c->d_rgb : nullptr;
@@ -3038,10 +3125,10 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
         c->sched_cap = ntiles;
         c->sched_key.clear();
     }
-    std::string key = std::to_string(p->width) + "x" + std::to_string(p->height) + "v" + std::to_string(n_views) +
-                      "s" + std::to_string(p->stripe_rows) + "/" + std::to_string(p->stripe_first) + "/" +
+    std::string key = std::to_string(sp.width) + "x" + std::to_string(sp.height) + "v" + std::to_string(n_views) +
+                      "s" + std::to_string(sp.stripe_rows) + "/" + std::to_string(p->stripe_first) + "/" +
                       std::to_string(p->stripe_step) + "g" + c->scene_sig + "m" +
-                      std::to_string(p->lighting_mode) + std::to_string(p->shadows_enabled);
+                      std::to_string(p->lighting_mode) + std::to_string(p->shadows_enabled) + "k" + std::to_string(ss);
     // Motion mode: a camera differs from the previous frame's (any field), so the tile costs go
     // stale quickly.  For kMotionFrames frames from then on, every frame is measured whose previous
     // measurement has completed (adopted without waiting), and split tiles are costed by their
@@ -3217,23 +3304,41 @@ int spec_variant(int facts) {
 }
 
 // The split launches of a frame (PHASE 1-3) in the frame's specialised variant v (-1: generic).
-template <int P, bool CU>
+template <int P, bool CU, bool SS>
 void launch_phase_v(int v, dim3 g, hipStream_t s, const DevScene& d, const FrameArgs& F) {
     switch (v) {
-    case 0: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[0], false, CU>), g, dim3(kBlockThreads), 0, s, d, F); break;
-    case 1: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[1], false, CU>), g, dim3(kBlockThreads), 0, s, d, F); break;
-    case 2: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[2]>), g, dim3(kBlockThreads), 0, s, d, F); break;   // (no mesh: nothing to cull)
-    case 3: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[3], false, CU>), g, dim3(kBlockThreads), 0, s, d, F); break;
-    case 4: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[4], false, CU>), g, dim3(kBlockThreads), 0, s, d, F); break;
-    default: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, 0, false, CU>), g, dim3(kBlockThreads), 0, s, d, F); break;
+    case 0: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[0], false, CU, SS>), g, dim3(kBlockThreads), 0, s, d, F); break;
+    case 1: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[1], false, CU, SS>), g, dim3(kBlockThreads), 0, s, d, F); break;
+    case 2: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[2], false, false, SS>), g, dim3(kBlockThreads), 0, s, d, F); break;   // (no mesh: nothing to cull)
+    case 3: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[3], false, CU, SS>), g, dim3(kBlockThreads), 0, s, d, F); break;
+    case 4: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, kSpecVariants[4], false, CU, SS>), g, dim3(kBlockThreads), 0, s, d, F); break;
+    default: hipLaunchKernelGGL((rtx_render_kernel<false, P, false, 0, false, CU, SS>), g, dim3(kBlockThreads), 0, s, d, F); break;
     }
+}
+// ... of a supersampled frame (FrameArgs::ss_log2) in the SS instantiation when P has the output
+// epilogue (PHASE 0, 3 and 6; the other phases are the same code for every factor)
+template <int P, bool CU>
+void launch_phase_s(int v, dim3 g, hipStream_t s, const DevScene& d, const FrameArgs& F) {
+    constexpr bool kOut = P == 0 || P == 3 || P == 6;
+    if (kOut && F.ss_log2) launch_phase_v<P, CU, kOut>(v, g, s, d, F);
+    else launch_phase_v<P, CU, false>(v, g, s, d, F);
 }
 // PHASE P of a frame in the frame's specialised variant v (-1: generic), with the cull variant
 // when the scene has cull records
 template <int P>
 void launch_phase(int v, dim3 g, hipStream_t s, const DevScene& d, const FrameArgs& F) {
-    if (d.cull_stride) launch_phase_v<P, true>(v, g, s, d, F);
-    else launch_phase_v<P, false>(v, g, s, d, F);
+    if (d.cull_stride) launch_phase_s<P, true>(v, g, s, d, F);
+    else launch_phase_s<P, false>(v, g, s, d, F);
+}
+
+// The one-launch frames without a specialised variant (the counting and the deep-stack kernels), in
+// the SS instantiation for a supersampled frame.
+template <bool COUNT, bool DEEP, bool HSTK, bool CU>
+void launch_one(dim3 g, hipStream_t s, const DevScene& d, const FrameArgs& F) {
+    if (F.ss_log2)
+        hipLaunchKernelGGL((rtx_render_kernel<COUNT, 0, DEEP, 0, HSTK, CU, true>), g, dim3(kBlockThreads), 0, s, d, F);
+    else
+        hipLaunchKernelGGL((rtx_render_kernel<COUNT, 0, DEEP, 0, HSTK, CU>), g, dim3(kBlockThreads), 0, s, d, F);
 }
 
 // The HBM stacks of the HSTK variant: max_depth + 1 entries for each wave of a launch of
@@ -3283,14 +3388,13 @@ int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
         if (count == 2 && c->dev.cull_stride && !c->hbm_stack && !c->deep_stack) {
             const int rc = cull_views(c, F);   // the views' camera records, as a frame would
             if (rc != RTX_OK) return rc;
-            hipLaunchKernelGGL((rtx_render_kernel<true, 0, false, 0, false, true>), grid, dim3(kBlockThreads), 0,
-                               c->stream, c->dev, G);
+            launch_one<true, false, false, true>(grid, c->stream, c->dev, G);
         } else if (c->hbm_stack)
-            hipLaunchKernelGGL((rtx_render_kernel<true, 0, true, 0, true>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, G);
+            launch_one<true, true, true, false>(grid, c->stream, c->dev, G);
         else if (c->deep_stack)
-            hipLaunchKernelGGL((rtx_render_kernel<true, 0, true>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, G);
+            launch_one<true, true, false, false>(grid, c->stream, c->dev, G);
         else
-            hipLaunchKernelGGL((rtx_render_kernel<true, 0>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, G);
+            launch_one<true, false, false, false>(grid, c->stream, c->dev, G);
         HIP_TRY(c, hipGetLastError());
         return RTX_OK;
     }
@@ -3332,9 +3436,9 @@ int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
         HIP_TRY(c, hipEventRecord(c->ev_join, s2));
     }
     if (c->hbm_stack)   // (the deep variants walk without the cull)
-        hipLaunchKernelGGL((rtx_render_kernel<false, 0, true, 0, true>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, F);
+        launch_one<false, true, true, false>(grid, c->stream, c->dev, F);
     else if (c->deep_stack)
-        hipLaunchKernelGGL((rtx_render_kernel<false, 0, true>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, F);
+        launch_one<false, true, false, false>(grid, c->stream, c->dev, F);
     else if (F.lm_lights) {   // light-major: hit records, then the (tile, light) waves
         launch_phase<4>(v, grid, c->stream, c->dev, F);
         HIP_TRY(c, hipGetLastError());
@@ -3419,6 +3523,14 @@ void remember(rtx_ctx* c, const rtx_render_params* p, int n_views, bool rgb) {
 }
 
 }  // namespace
+
+extern "C" int rtx_set_supersample(rtx_ctx* c, uint32_t k) {
+    if (!c) return RTX_E_INVALID;
+    if (k != 1 && k != 2 && k != 4 && k != 8)
+        return fail(c, RTX_E_INVALID, "supersample factor must be 1, 2, 4 or 8 (got " + std::to_string(k) + ")");
+    c->ss_log2 = k == 8 ? 3u : (k == 4 ? 2u : (k == 2 ? 1u : 0u));
+    return RTX_OK;
+}
 
 extern "C" int rtx_render_views_async(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p,
                                       int want_rgb) {

@@ -245,6 +245,13 @@ struct FrameArgs {
     uint32_t lm_lights;                         // lights per tile (PHASE 5 items = n_tiles x lm_lights)
     float4* __restrict__ lm_rec;                // per tile pixel: {h, n.x}, {n.y, n.z, mat bits, did}
     unsigned long long* __restrict__ lm_mask;   // per (tile, light): the lanes whose shadow ray is occluded
+    // Supersampling (rtx_set_supersample): ss_log2 = log2 k of the k x k samples per
+    // pixel, k in {1, 2, 4, 8}.  With k > 1 every field above that describes the frame (aspect,
+    // inv_*, width, height, groups_per_stripe, tiles_*) is that of the k*out_width x k*out_height
+    // sample frame, and out_px / out_rgb hold out_width x out_height pixels per view: a pixel's
+    // samples lie in one wave tile, whose epilogue resolves them.  k = 1: 0 and width x height.
+    uint32_t ss_log2;
+    uint32_t out_width, out_height;
 };
 
 // Light-major frames (opt-in: RTX_LIGHT_MAJOR=1 always, =auto while a launch has at most kLmSlotsPercent /

@@ -54,6 +54,10 @@ class DeviceContext:
     def upload(self, scene: abi.Scene) -> None:
         abi.check(self.lib.rtx_upload_scene(self.h, C.byref(scene)), "rtx_upload_scene", self.h)
 
+    def set_supersample(self, k: int) -> None:
+        """k x k samples per pixel (1, 2, 4 or 8) for every later frame (rtx_set_supersample)."""
+        abi.check(self.lib.rtx_set_supersample(self.h, int(k)), "rtx_set_supersample", self.h)
+
     def render(self, cam: abi.Camera, params: abi.RenderParams, want_rgb: bool = True):
         n = params.width * params.height
         px = np.zeros(n, np.uint32)
@@ -173,6 +177,10 @@ class DeviceGroup:
     def upload(self, scene: abi.Scene) -> None:
         self._check(self.lib.rtx_group_upload_scene(self.h, C.byref(scene)), "rtx_group_upload_scene")
 
+    def set_supersample(self, k: int) -> None:
+        """k x k samples per pixel (1, 2, 4 or 8) on every member (rtx_group_set_supersample)."""
+        self._check(self.lib.rtx_group_set_supersample(self.h, int(k)), "rtx_group_set_supersample")
+
     def render(self, cam: abi.Camera, params: abi.RenderParams, want_rgb: bool = True, out_px=None):
         n = params.width * params.height
         px = np.zeros(n, np.uint32) if out_px is None else out_px
@@ -259,7 +267,7 @@ class DeviceAnimation:
 
 class Renderer:
     def __init__(self, width: int, height: int, device: int = 0, stripe: tuple[int, int, int] | None = None,
-                 pixel_format=abi.XRGB8888):
+                 pixel_format=abi.XRGB8888, supersample: int = 1):
         self.m_Width, self.m_Height = int(width), int(height)
         self.m_AspectRatio = self.m_Width / float(self.m_Height)
         self.m_CurrentLightingMode = LightingMode.Combined
@@ -267,6 +275,9 @@ class Renderer:
         self.stripe = stripe
         self.format = pixel_format
         self.ctx = DeviceContext(device)
+        if supersample != 1:
+            self.ctx.set_supersample(supersample)
+        self.supersample = int(supersample)
         self._scene_ref = None    # weakref to the uploaded HostScene
         self._scene_gen = -1      # its generation at upload
         self.buffer = np.zeros(self.m_Width * self.m_Height, np.uint32)

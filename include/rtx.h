@@ -203,6 +203,15 @@ int rtx_render_async(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_param
  * the same number of rows each (the weak-scaling partition of bench.py). */
 int rtx_render_views_async(rtx_ctx* ctx, const rtx_camera* cams, int n_views,
                            const rtx_render_params* params, int want_rgb);
+/* Supersampled anti-aliasing: every later frame of `ctx` (rtx_render*, rtx_time_*, rtx_count_work*)
+ * takes k x k samples per pixel, k in {1, 2, 4, 8} (1 = one ray through the pixel centre, the
+ * default).  Sample (X, Y) is pixel (X, Y) of the reference's k*width x k*height frame, up to and
+ * including MaxToOne; pixel (x, y) is the box filter of the samples (k x + sx, k y + sy): per channel
+ * the fp32 sum as an adjacent-pair tree over sx, then over sy, times 1/(k*k).  The render kernel
+ * resolves it, so the frame buffer, the downloads and the stripes stay width x height; k*width and
+ * k*height may not exceed 65536 (rtx_render* then returns RTX_E_INVALID).  Any other k returns
+ * RTX_E_INVALID and leaves the factor as it was.  The work counters count the sample frame. */
+int rtx_set_supersample(rtx_ctx* ctx, uint32_t k);
 int rtx_synchronize(rtx_ctx* ctx);
 /* Copy the context's frame buffer (rows owned by the last render) to host memory. */
 int rtx_download(rtx_ctx* ctx, uint32_t* out_pixels, float* out_rgb);
@@ -244,6 +253,8 @@ int rtx_group_upload_scene(rtx_group* group, const rtx_scene* scene);
  * (the group assigns the stripes).  out_pixels: width*height uint32; out_rgb may be NULL. */
 int rtx_group_render(rtx_group* group, const rtx_camera* cam, const rtx_render_params* params,
                      uint32_t* out_pixels, float* out_rgb);
+/* rtx_set_supersample on every member (stripes stay rows of the width x height frame). */
+int rtx_group_set_supersample(rtx_group* group, uint32_t k);
 
 /* ---- animated meshes: Scene::Update on the device -------------------
  * Replaces, per animated frame, the host's TriangleMesh::UpdateTransforms + BuildBVH

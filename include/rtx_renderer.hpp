@@ -54,6 +54,8 @@ public:
                                                           static_cast<int>(LightingMode::Count));
     }
     void ToggleShadows() { m_ShadowsEnabled = !m_ShadowsEnabled; }                // Renderer.h:34-36
+    // k x k samples per pixel (1, 2, 4 or 8) for every later Render (rtx_set_supersample); not in the reference
+    void SetSupersample(uint32_t k) { Check(rtx_set_supersample(m_Ctx, k), "rtx_set_supersample"); }
 
     // SDL_SaveBMP of the XRGB8888 surface (Renderer.cpp:184-187): 32-bit BI_RGB, bottom-up.
     bool SaveBufferToImage(const std::string& path = "RayTracing_Buffer.bmp") const {
