@@ -182,6 +182,8 @@ struct rtx_ctx {
     int scene_spec = 0;              // kSpec* facts of the uploaded scene (kernel specialisation)
     float room_p0[5] = {};           // kSpecRoomPlanes: plane k's origin on axis kRoomAxes[k]
     bool no_spec = false;            // RTX_NO_SPEC=1: always the generic kernel (tests)
+    int last_facts = 0;              // rtx_spec_info: the facts and the kSpecVariants index (-1: the
+    int last_variant = -1;           // generic kernel) of the last frame launched
     unsigned long long* d_hit_key = nullptr;
     uint32_t* d_occ = nullptr;
     // Light-major frames (FrameArgs::lm_*, DESIGN.md §6, opt-in): lm_mode 0 never (default), 1 auto

@@ -2955,6 +2955,8 @@ int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay) {
                         (s->n_planes == 5 ? kSpecFivePlanes : 0) | (s->n_meshes == 1 ? kSpecOneMesh : 0) |
                         (s->n_meshes == 0 ? kSpecNoMesh : 0) | (room ? kSpecRoomPlanes : 0) |
                         (cull_back ? kSpecCullBack : 0);
+        c->last_facts = c->scene_spec;   // (rtx_spec_info before the first frame)
+        c->last_variant = -1;
     }
     c->split_ok = split_ok && !parts.empty() && !c->deep_stack;
     c->refinable = refinable && c->split_ok && !c->refine_off;
@@ -3407,6 +3409,8 @@ int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
     // RTX_NO_SPEC=1 forces the generic kernel); the split launches take it too
     const int facts = c->scene_spec | ((F.mode == RTX_MODE_COMBINED && F.shadows) ? kSpecCombShadows : 0);
     const int v = (c->no_spec || c->deep_stack) ? -1 : spec_variant(facts);
+    c->last_facts = facts;
+    c->last_variant = v;
     if (F.heavy_flag) {
         // The heavy tiles, one BVH frontier part per workgroup (see the kernel), on a
         // high-priority stream forked from the frame stream: they share no pixels with the
@@ -3745,6 +3749,13 @@ extern "C" int rtx_cull_info(rtx_ctx* c, uint32_t* enabled, uint64_t* camera_upd
     if (!c) return RTX_E_INVALID;
     if (enabled) *enabled = c->dev.cull_stride ? 1u : 0u;
     if (camera_updates) *camera_updates = c->cull_updates;
+    return RTX_OK;
+}
+
+extern "C" int rtx_spec_info(rtx_ctx* c, uint32_t* facts, int32_t* last_variant) {
+    if (!c) return RTX_E_INVALID;
+    if (facts) *facts = static_cast<uint32_t>(c->last_facts);
+    if (last_variant) *last_variant = c->last_variant;
     return RTX_OK;
 }
 

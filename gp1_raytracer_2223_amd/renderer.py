@@ -128,6 +128,12 @@ class DeviceContext:
         abi.check(self.lib.rtx_cull_info(self.h, C.byref(on), C.byref(n)), "rtx_cull_info", self.h)
         return bool(on.value), n.value
 
+    def spec_info(self) -> tuple[int, int]:
+        """(kSpec* facts of the last frame launched, the kSpecVariants index it took: -1 = generic)."""
+        f, v = C.c_uint32(), C.c_int32()
+        abi.check(self.lib.rtx_spec_info(self.h, C.byref(f), C.byref(v)), "rtx_spec_info", self.h)
+        return f.value, v.value
+
     def count_work(self, cam, params) -> np.ndarray:
         out = (C.c_uint64 * 12)()
         abi.check(self.lib.rtx_count_work(self.h, C.byref(cam), C.byref(params), out), "rtx_count_work", self.h)

@@ -76,6 +76,13 @@ int rtx_inflight_info(rtx_ctx* ctx, uint32_t* concurrent, uint32_t* onepiece, fl
  * many times a camera's records were (re)built.  Environment: RTX_NO_CULL=1 disables;
  * RTX_CULL_MIN_SA, RTX_CULL_RATIO tune the enabling test and the per-node flag (tests). */
 int rtx_cull_info(rtx_ctx* ctx, uint32_t* enabled, uint64_t* camera_updates);
+/* Kernel specialisation (no reference counterpart: variants of the render kernel with uniform facts
+ * of the scene and frame compiled in; the same operations, so the same pixels).
+ * Reports the facts (kSpec* bits, csrc/rtx_kernels.h) of the last frame launched and the variant it
+ * took: an index into kSpecVariants, or -1 for the generic kernel (no variant's facts hold, a deep
+ * BVH, RTX_NO_SPEC=1).  After an upload and before the next frame: the scene's facts and -1.  Host
+ * bookkeeping at the launch site only. */
+int rtx_spec_info(rtx_ctx* ctx, uint32_t* facts, int32_t* last_variant);
 /* Diagnostics of the exact cull (tests): waits for the context stream, then copies the current
  * image's records of record copy `anchor` (view v < 8: its camera; 8 + l: light l) — n_slots x
  * 8 floats, {c, E.x}, {E.y, E.z, dt, flag bits} — and their inputs: per slot the triangle range

@@ -17,8 +17,10 @@ the reference's own functions:
   scene_file_<stem>[_t].npz, frame_file_<stem>_128x72_m<mode>s<sh>[_t].npz
                         the same for the scene files in scenes/*.rtxscene, built by the
                         harness with the reference's own classes
+  fuzz/<family>_<seed>.rtxscene, .npz   the seeded adversarial scenes of tests/scene_fuzz.py (the
+                        generated text) and the reference's 44x28 frames of them, modes (3,1), (2,0)
 
-Usage:  python tests/golden/make_goldens.py [--scene-files-only | --configs-only]
+Usage:  python tests/golden/make_goldens.py [--scene-files-only | --configs-only | --fuzz-only]
 
 """
 from __future__ import annotations
@@ -79,7 +81,39 @@ def scene_files() -> None:
         print("scene file", f.name, flush=True)
 
 
+FUZZ_DIR = HERE / "fuzz"
+FUZZ_W, FUZZ_H = 44, 28          # five wave tiles and a half across, three and a half down
+FUZZ_FRAMES = [(3, 1), (2, 0)]
+
+
+def fuzz() -> None:
+    """The seeded scenes of tests/scene_fuzz.py (its COMMITTED list): the generated text as
+    fuzz/<family>_<seed>.rtxscene and the reference's frames of it as fuzz/<family>_<seed>.npz
+    (pixels_m<mode>s<sh>, rgb_m<mode>s<sh>).  The harness alone is needed (no HIP library)."""
+    sys.path.insert(0, str(HERE.parent))
+    import scene_fuzz
+    if not HARNESS.exists():
+        subprocess.run(["make", "-s", "-C", str(ROOT / "oracle" / "ref"), str(HARNESS)], check=True)
+    FUZZ_DIR.mkdir(exist_ok=True)
+    for old in list(FUZZ_DIR.glob("*.rtxscene")) + list(FUZZ_DIR.glob("*.npz")):
+        old.unlink()
+    for family, seed in scene_fuzz.COMMITTED:
+        fs = scene_fuzz.make(family, seed)
+        f = FUZZ_DIR / f"{fs.name}.rtxscene"
+        f.write_text(fs.text)
+        out = {}
+        for mode, sh in FUZZ_FRAMES:
+            d = run("render", f"file:{f}", -1, FUZZ_W, FUZZ_H, mode, sh, 8)
+            out[f"pixels_m{mode}s{sh}"] = d["pixels"]
+            out[f"rgb_m{mode}s{sh}"] = d["rgb"]
+        np.savez_compressed(FUZZ_DIR / f"{fs.name}.npz", **out)
+        print("fuzz", fs.name, flush=True)
+
+
 def main() -> None:
+    if "--fuzz-only" in sys.argv:
+        fuzz()
+        return
     assert HARNESS.exists(), "build oracle/_ref first (python -m gp1_raytracer_2223_amd.build)"
     if "--scene-files-only" in sys.argv:
         scene_files()
@@ -88,6 +122,7 @@ def main() -> None:
         configs()
         return
     scene_files()
+    fuzz()
     for obj in sorted(REF_SRC.glob("Resources/*.obj")):
         d = run("obj", obj.relative_to(REF_SRC))
         np.savez_compressed(HERE / f"obj_{obj.stem}.npz", **d)

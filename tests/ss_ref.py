@@ -37,6 +37,9 @@ def quantize(rgb, fmt=(16, 8, 0, 0)) -> np.ndarray:
     """q8 of each channel (static_cast<uint8_t>(c * 255): the float32 product truncated, low byte)
     packed with the caller's shifts and alpha mask; XRGB8888 by default."""
     c = np.asarray(rgb, dtype=np.float32).reshape(-1, 3)
-    q = ((c * np.float32(255)).astype(np.int32) & 255).astype(np.uint32)
+    v = c * np.float32(255)
+    with np.errstate(invalid="ignore"):
+        in_range = np.abs(v) < np.float32(2.0 ** 31)   # cvttss2si: NaN and out of range give 0x80000000, low byte 0
+    q = (np.where(in_range, v, np.float32(0)).astype(np.int32) & 255).astype(np.uint32)
     rs, gs, bs, amask = fmt
     return (q[:, 0] << np.uint32(rs)) | (q[:, 1] << np.uint32(gs)) | (q[:, 2] << np.uint32(bs)) | np.uint32(amask)
