@@ -26,6 +26,19 @@ RTX_CULL_FRONT, RTX_CULL_BACK, RTX_CULL_NONE = 0, 1, 2
 RTX_LIGHT_POINT, RTX_LIGHT_DIRECTIONAL = 0, 1
 RTX_MODE_OBSERVED_AREA, RTX_MODE_RADIANCE, RTX_MODE_BRDF, RTX_MODE_COMBINED = 0, 1, 2, 3
 RTX_MAT_SOLID_COLOR, RTX_MAT_LAMBERT, RTX_MAT_LAMBERT_PHONG, RTX_MAT_COOK_TORRANCE = 0, 1, 2, 3
+# hit-record planes (rtx_render_aov*): the mask bits, and the primitive plane's kinds (kind << 30 | index)
+RTX_AOV_DEPTH, RTX_AOV_NORMAL, RTX_AOV_MATERIAL, RTX_AOV_PRIMITIVE, RTX_AOV_ALL = 1, 2, 4, 8, 15
+RTX_PRIM_NONE, RTX_PRIM_SPHERE, RTX_PRIM_PLANE, RTX_PRIM_TRIANGLE = 0, 1, 2, 3
+
+
+def prim_kind(p):
+    """RTX_PRIM_KIND of a primitive word (or array of them)."""
+    return p >> 30
+
+
+def prim_index(p):
+    """RTX_PRIM_INDEX of a primitive word (or array of them)."""
+    return p & 0x3FFFFFFF
 
 F3 = C.c_float * 3
 
@@ -78,6 +91,11 @@ class Camera(C.Structure):
 
 class PixelFormat(C.Structure):
     _fields_ = [("rshift", C.c_uint32), ("gshift", C.c_uint32), ("bshift", C.c_uint32), ("amask", C.c_uint32)]
+
+
+class AovPlanes(C.Structure):   # rtx_aov_planes (rtx.h): host or device planes, NULL = not asked for
+    _fields_ = [("depth", C.POINTER(C.c_float)), ("normal", C.POINTER(C.c_float)),
+                ("material", C.POINTER(C.c_uint32)), ("primitive", C.POINTER(C.c_uint32))]
 
 
 XRGB8888 = (16, 8, 0, 0)
@@ -156,7 +174,9 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_group_context", "rtx_group_upload_scene", "rtx_group_render", "rtx_schedule_state",
                "rtx_anim_create", "rtx_anim_destroy", "rtx_anim_last_error", "rtx_anim_update", "rtx_anim_status",
                "rtx_anim_download", "rtx_scene_image", "rtx_anim_stamps", "rtx_cull_info", "rtx_cull_dump", "rtx_light_major_info",
-               "rtx_inflight_info", "rtx_set_supersample", "rtx_group_set_supersample", "rtx_spec_info"]
+               "rtx_inflight_info", "rtx_set_supersample", "rtx_group_set_supersample", "rtx_spec_info",
+               "rtx_render_aov_async", "rtx_render_aov", "rtx_download_aov", "rtx_gather_aov_async",
+               "rtx_device_aov_buffers", "rtx_group_render_aov", "rtx_time_aov_frames"]
 
 
 def load_hip() -> C.CDLL:
@@ -264,6 +284,24 @@ def load_hip() -> C.CDLL:
             lib.rtx_group_render.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_float)]
             lib.rtx_group_render.restype = C.c_int
+        if hasattr(lib, "rtx_render_aov"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_render_aov_async.argtypes = [VP, C.POINTER(Camera), C.c_int, C.POINTER(RenderParams), C.c_uint32]
+            lib.rtx_render_aov_async.restype = C.c_int
+            lib.rtx_render_aov.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
+                                           C.POINTER(AovPlanes)]
+            lib.rtx_render_aov.restype = C.c_int
+            lib.rtx_download_aov.argtypes = [VP, C.POINTER(AovPlanes)]
+            lib.rtx_download_aov.restype = C.c_int
+            lib.rtx_gather_aov_async.argtypes = [VP, C.POINTER(AovPlanes)]
+            lib.rtx_gather_aov_async.restype = C.c_int
+            lib.rtx_device_aov_buffers.argtypes = [VP, C.POINTER(AovPlanes)]
+            lib.rtx_device_aov_buffers.restype = C.c_int
+            lib.rtx_group_render_aov.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
+                                                 C.POINTER(AovPlanes)]
+            lib.rtx_group_render_aov.restype = C.c_int
+            lib.rtx_time_aov_frames.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_int,
+                                                C.POINTER(C.c_float)]
+            lib.rtx_time_aov_frames.restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]
             lib.rtx_scene_image.restype = C.c_int

@@ -4,7 +4,7 @@
 //
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
-//              [--device-update] [--ss K]
+//              [--device-update] [--ss K] [--aov PREFIX]
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -13,6 +13,10 @@
 // scenes are re-uploaded after every Update; the per-stage means are printed as well.
 // --inflight F (default 2) overlaps F frames (run_benchmark); 1 = the serial loop.
 // --ss K (1, 2, 4 or 8; default 1) renders K x K samples per pixel (rtx_set_supersample).
+// --aov PREFIX (single frames only, not --benchmark / --sequence, and not with --ss above 1) also runs
+// the hit pass of the frame it rendered (rtx_render_aov) and writes its planes as raw little-endian
+// files: PREFIX_depth.f32, PREFIX_normal.f32 (3 floats per pixel), PREFIX_material.u32 and
+// PREFIX_primitive.u32 (kind << 30 | index), row-major width x height.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -293,16 +297,26 @@ int run_benchmark(rtx::Renderer& r, rtx_host_scene* hs, int windows, int infligh
     return 0;
 }
 
+// One plane of --aov as a raw file (the hosts this builds for are little-endian).
+template <class T>
+bool write_plane(const std::string& path, const std::vector<T>& v) {
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
+    return std::fclose(f) == 0 && ok;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
-                             "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K]\n",
+                             "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
+                             "[--aov prefix]\n",
                      argv[0]);
         return 2;
     }
-    std::string scene = argv[1], out = "RayTracing_Buffer.bmp", assets;
+    std::string scene = argv[1], out = "RayTracing_Buffer.bmp", assets, aov;
     int W = 640, H = 480, mode = 3, frames = 1, bench = 0, inflight = 2, ss = 1;
     std::vector<float> seq;
     float t = -1.f;
@@ -332,10 +346,15 @@ int main(int argc, char** argv) {
             }
         }
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
+        else if (a == "--aov" && i + 1 < argc) aov = argv[++i];
         else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
         else if (a == "--benchmark") bench = (i + 1 < argc && std::atoi(argv[i + 1]) > 0) ? std::atoi(argv[++i]) : 10;
         else if (pos == 0) { W = std::atoi(argv[i]); ++pos; }
         else if (pos == 1) { H = std::atoi(argv[i]); ++pos; }
+    }
+    if (!aov.empty() && (bench || !seq.empty())) {
+        std::fprintf(stderr, "--aov writes the planes of a single frame: not with --benchmark or --sequence\n");
+        return 2;
     }
     char err[512] = {0};
     rtx_host_scene* hs = nullptr;
@@ -388,6 +407,16 @@ int main(int argc, char** argv) {
                 const double s = secs(t0, t1) / (frames - 1);
                 std::printf("%s %dx%d: %.3f ms/frame incl. D2H, %.1f Mpix/s\n", scene.c_str(), W, H, s * 1e3,
                             W * (double)H / s / 1e6);
+            }
+            if (!aov.empty()) {   // the planes of the frame just rendered (the uploaded scene, the same camera)
+                const rtx::Renderer::AovFrame f = r.RenderAov(hs, RTX_AOV_ALL, false);
+                if (!write_plane(aov + "_depth.f32", f.depth) || !write_plane(aov + "_normal.f32", f.normal) ||
+                    !write_plane(aov + "_material.u32", f.material) || !write_plane(aov + "_primitive.u32", f.primitive)) {
+                    std::fprintf(stderr, "cannot write %s_*\n", aov.c_str());
+                    rc = 1;
+                } else {
+                    std::printf("wrote %s_depth.f32 _normal.f32 _material.u32 _primitive.u32\n", aov.c_str());
+                }
             }
         }
         if (rc == 0 && !r.SaveBufferToImage(out)) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); rc = 1; }

@@ -244,6 +244,17 @@ struct rtx_ctx {
     rtx_render_params last{};
     int last_views = 1;
     bool last_valid = false, last_rgb = false;
+    // Hit pass (rtx_render_aov*): the planes in HBM (each allocated when a mask first asks for it;
+    // aov_cap = the elements each allocated one holds) and the last pass's own record beside the
+    // colour frame's `last`, so a colour gather after a pass still copies the colour frame's rows
+    float* d_aov_depth = nullptr;
+    float* d_aov_normal = nullptr;
+    uint32_t* d_aov_material = nullptr;
+    uint32_t* d_aov_primitive = nullptr;
+    size_t aov_cap = 0;
+    rtx_render_params aov_last{};
+    int aov_last_views = 1;
+    uint32_t aov_last_mask = 0;   // 0: no pass yet
 };
 
 namespace rtxh {

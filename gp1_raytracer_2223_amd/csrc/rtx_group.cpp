@@ -31,12 +31,14 @@ struct rtx_group {
     int pending = 0;
     bool quit = false;
     // current job
-    enum Op { kUpload, kRender } op = kUpload;
+    enum Op { kUpload, kRender, kRenderAov } op = kUpload;
     const rtx_scene* scene = nullptr;
     const rtx_camera* cam = nullptr;
     rtx_render_params params{};
     uint32_t* out_px = nullptr;
     float* out_rgb = nullptr;
+    uint32_t aov_mask = 0;       // kRenderAov: the hit pass's planes and the caller's
+    rtx_aov_planes aov_out{};
     std::vector<int> rc;
     std::string err;
 };
@@ -59,8 +61,14 @@ int run_member(rtx_group* g, size_t i) {
         p.stripe_first = 0;
         p.stripe_step = 1;
     }
-    int rc = rtx_render_async(c, g->cam, &p, g->out_rgb != nullptr);
-    if (rc == RTX_OK) rc = rtx_gather_async(c, g->out_px, g->out_rgb);
+    int rc;
+    if (g->op == rtx_group::kRenderAov) {
+        rc = rtx_render_aov_async(c, g->cam, 1, &p, g->aov_mask);
+        if (rc == RTX_OK) rc = rtx_gather_aov_async(c, &g->aov_out);
+    } else {
+        rc = rtx_render_async(c, g->cam, &p, g->out_rgb != nullptr);
+        if (rc == RTX_OK) rc = rtx_gather_async(c, g->out_px, g->out_rgb);
+    }
     if (rc == RTX_OK) rc = rtx_synchronize(c);
     return rc;
 }
@@ -201,5 +209,24 @@ extern "C" int rtx_group_render(rtx_group* g, const rtx_camera* cam, const rtx_r
     g->params = *p;
     g->out_px = out_px;
     g->out_rgb = out_rgb;
+    return run_job(g);
+}
+
+extern "C" int rtx_group_render_aov(rtx_group* g, const rtx_camera* cam, const rtx_render_params* p, uint32_t mask,
+                                    const rtx_aov_planes* out) {
+    if (!g || !cam || !p || !out) return RTX_E_INVALID;
+    if (p->stripe_step > 1) {
+        g->err = "rtx_group_render_aov partitions the frame itself: stripe_step must be 0 or 1";
+        return RTX_E_INVALID;
+    }
+    if (p->stripe_rows % 16 != 0) {
+        g->err = "stripe_rows must be a multiple of 16 (0 = 16)";
+        return RTX_E_INVALID;
+    }
+    g->op = rtx_group::kRenderAov;
+    g->cam = cam;
+    g->params = *p;
+    g->aov_mask = mask;
+    g->aov_out = *out;
     return run_job(g);
 }

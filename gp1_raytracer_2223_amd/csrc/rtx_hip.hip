@@ -870,6 +870,9 @@ __device__ __forceinline__ uint32_t q8(float c) {
 //   PHASE 5  persistent waves over the (tile, light) items: that light's shadow ray from the
 //                                          record -> the occluded lanes; the tile's last light wave
 //                                          shades every light in order (the occlusion published)
+// The hit pass (rtx_render_aov*, FrameArgs::aov_*) is a launch of its own:
+//   PHASE 7  grid (tiles):                 PHASE 0 up to the hit record, whose t, normal, material and
+//                                          primitive it writes into the requested planes; no light loop
 // Every phase recomputes the primary ray and the sphere/plane hits with the same code, so
 // all of them see bit-identical values.
 // DEEP: the variant for scenes whose BVH is kStackDepth or more levels deep (a DFS stack of
@@ -1015,11 +1018,11 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     // FAST: every active lane's inverse direction finite and non-zero (make_ray's domain)
     const bool fast = (active & vslow) == 0 && S.tri_fast;
     // octant of the wave's primary rays (-1: mixed signs, or no octant copies)
-    const int poct = (fast && S.oct_bytes && (PHASE == 0 || PHASE == 4)) ? batch_octant(vr, active) : -1;
+    const int poct = (fast && S.oct_bytes && (PHASE == 0 || PHASE == 4 || PHASE == 7)) ? batch_octant(vr, active) : -1;
     // exact cull of the view's camera anchor (FAST waves; a direction normalised from a magnitude
     // of at least 2^-30 has |d| = 1 +- 3u, which the bound assumes)
     constexpr bool kCull = CULLK && !RTX_STAMPS_WALK;   // (with COUNT: rtx_count_work_culled)
-    const bool pcull = kCull && S.cull_stride && fast && (PHASE == 0 || PHASE == 1 || PHASE == 4);
+    const bool pcull = kCull && S.cull_stride && fast && (PHASE == 0 || PHASE == 1 || PHASE == 4 || PHASE == 7);
     CullRay pq{};
     if (pcull)
         pq = cull_ray(S.cull + static_cast<size_t>(uni(view)) * (S.cull_stride / 16u), vr, dm >= 0x1p-30f,
@@ -1087,7 +1090,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         best_kind = b ? 2u : best_kind;
         best_idx = b ? i : best_idx;
     }
-    if (PHASE == 0 || PHASE == 4) {
+    if (PHASE == 0 || PHASE == 4 || PHASE == 7) {
         for (uint32_t mi = 0; mi < ((RTX_ABL_PMESH) ? 0u : n_mesh); ++mi) {
             const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
             uint32_t sc_tri = 0;
@@ -1196,6 +1199,23 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         F.lm_rec[lm_slot] = make_float4(hx, hy, hz, nx);
         F.lm_rec[lm_slot + 1] = make_float4(ny, nz, __uint_as_float(mat), __uint_as_float(did ? 1u : 0u));
         if (F.cost && lane == 0) part_cost_add(F.cost + tile, __builtin_amdgcn_s_memtime() - t_block0);
+        return;
+    }
+
+    if (PHASE == 7) {   // hit pass: the record in the caller's terms (rtx.h, rtx_aov_planes), no colour
+        if (valid) {
+            const size_t o = static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
+                             static_cast<size_t>(px);
+            const uint32_t m = uni(F.aov_mask);
+            if (m & RTX_AOV_DEPTH) F.aov_depth[o] = best_t;   // (a miss: the empty HitRecord's FLT_MAX)
+            if (m & RTX_AOV_NORMAL) {
+                F.aov_normal[3 * o] = nx; F.aov_normal[3 * o + 1] = ny; F.aov_normal[3 * o + 2] = nz;
+            }
+            if (m & RTX_AOV_MATERIAL) F.aov_material[o] = mat;
+            // best_idx is the record's byte offset: 16 B per sphere, 32 per plane, 64 per triangle
+            if (m & RTX_AOV_PRIMITIVE)
+                F.aov_primitive[o] = did ? (best_kind << 30) | (best_idx >> (best_kind + 3u)) : 0u;
+        }
         return;
     }
 
@@ -1509,7 +1529,7 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
     uint32_t tile, part = 0, light = 0;
     // PHASE 4/5: the light-major frame (FrameArgs::lm_*): PHASE 4 = PHASE 0 up to the hit record,
     // PHASE 5 = item (tile, light), the tiles in dispatch order and a tile's lights consecutive
-    if (PHASE == 0 || PHASE == 4 || PHASE == 6) {
+    if (PHASE == 0 || PHASE == 4 || PHASE == 6 || PHASE == 7) {
         if (widx >= F.n_tiles) return;
         tile = F.order ? ldc(F.order, widx) : widx;
         if (F.heavy_flag && ldc(F.heavy_flag, tile)) return;   // rendered by the split launches
@@ -1575,6 +1595,11 @@ RTX_CULL_VARIANTS(1)
 RTX_CULL_VARIANTS(2)
 RTX_CULL_VARIANTS(3)
 #undef RTX_CULL_VARIANTS
+// the hit pass (PHASE 7, rtx_render_aov*): the generic kernel with every stack, and with the exact cull
+template __global__ void rtx_render_kernel<false, 7>(const DevScene, const FrameArgs);
+template __global__ void rtx_render_kernel<false, 7, true>(const DevScene, const FrameArgs);
+template __global__ void rtx_render_kernel<false, 7, true, 0, true>(const DevScene, const FrameArgs);
+template __global__ void rtx_render_kernel<false, 7, false, 0, false, true>(const DevScene, const FrameArgs);
 
 // Octant copies 1..7 of an uploaded node array from copy 0 (blockIdx.y + 1 = octant k):
 // copy k stores (hi, lo) on the axes set in k, the same swap the host applies for small
@@ -2343,6 +2368,10 @@ extern "C" void rtx_destroy(rtx_ctx* c) {
     }
     (void)hipFree(c->d_px);
     (void)hipFree(c->d_rgb);
+    (void)hipFree(c->d_aov_depth);
+    (void)hipFree(c->d_aov_normal);
+    (void)hipFree(c->d_aov_material);
+    (void)hipFree(c->d_aov_primitive);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_order);
     (void)hipFree(c->d_order_xcd);
@@ -2987,6 +3016,70 @@ int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay) {
 namespace {
 
 
+// The launch record of a frame of `n_views` cameras: the cameras (with their cull bounds and room-plane
+// numerators), the frame `sp` the kernel renders (the sample frame of a supersampled one, `p` otherwise),
+// its owned wave tiles and the launch grid.  Everything a colour frame and the hit pass share; the
+// outputs and the schedule are the caller's.
+void frame_shape(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p,
+                 const rtx_render_params& sp, uint32_t ss, FrameArgs& F, dim3& grid) {
+    const bool striped = p->stripe_rows != 0 && p->stripe_step > 1;
+    std::memset(&F, 0, sizeof F);
+    for (int v = 0; v < n_views; ++v) {
+        for (int k = 0; k < 3; ++k) {
+            F.cam[v].origin[k] = cams[v].origin[k]; F.cam[v].right[k] = cams[v].right[k];
+            F.cam[v].up[k] = cams[v].up[k]; F.cam[v].forward[k] = cams[v].forward[k];
+        }
+        F.cam[v].fov = cams[v].fov;
+        // the camera anchor's t bound (CullRay::bt): 4x the farthest corner of the meshes' box + 1
+        if (c->dev.cull_stride) {
+            double R = 0.0;
+            for (int k = 0; k < 8; ++k) {
+                const double dx = cams[v].origin[0] - ((k & 1) ? c->cull_bmax[0] : c->cull_bmin[0]);
+                const double dy = cams[v].origin[1] - ((k & 2) ? c->cull_bmax[1] : c->cull_bmin[1]);
+                const double dz = cams[v].origin[2] - ((k & 4) ? c->cull_bmax[2] : c->cull_bmin[2]);
+                R = std::fmax(R, std::sqrt(dx * dx + dy * dy + dz * dz));
+            }
+            const double bt = 4.0 * R + 1.0;
+            F.cam[v].cull_bt = std::isfinite(bt) && bt < 0x1p60 ? static_cast<float>(bt) : 0.f;   // 0: no pruning
+        }
+        if (c->scene_spec & kSpecRoomPlanes) {   // the room planes' camera numerators (ViewCam)
+            bool ok = true;
+            for (int k = 0; k < 5; ++k) {
+                const float a = c->room_p0[k] - cams[v].origin[kRoomAxes[k]];
+                const float aa = std::fabs(a);
+                F.cam[v].room_a[k] = a;
+                ok = ok && (a == 0.f || (aa >= 0x1p-60f && aa <= 0x1p60f));
+            }
+            F.cam[v].room_fast = ok ? 1u : 0u;
+        }
+    }
+    F.n_views = static_cast<uint32_t>(n_views);
+    F.aspect = static_cast<int>(sp.width) / static_cast<float>(static_cast<int>(sp.height));  // Renderer.cpp:30
+    F.inv_width = 1.f / static_cast<float>(static_cast<int>(sp.width));
+    F.inv_height = 1.f / static_cast<float>(static_cast<int>(sp.height));
+    F.width = sp.width; F.height = sp.height;
+    F.ss_log2 = ss; F.out_width = p->width; F.out_height = p->height;
+    F.mode = p->lighting_mode; F.shadows = p->shadows_enabled ? 1 : 0;
+    F.rshift = p->format.rshift; F.gshift = p->format.gshift; F.bshift = p->format.bshift; F.amask = p->format.amask;
+    const uint32_t groups = (sp.height + kWaveTile - 1) / kWaveTile;
+    uint32_t gy = groups;
+    if (striped) {
+        // every view owns the same number of stripes only if the stripe count divides
+        // evenly; size the grid for the largest owner and let the kernel skip the rest
+        const uint32_t gps = sp.stripe_rows / kWaveTile;
+        const uint32_t nstripes = (groups + gps - 1) / gps;
+        const uint32_t owned = (nstripes + p->stripe_step - 1) / p->stripe_step;
+        F.groups_per_stripe = gps; F.stripe_first = p->stripe_first; F.stripe_step = p->stripe_step;
+        gy = owned * gps;
+    }
+    F.tiles_x = (sp.width + kWaveTile - 1) / kWaveTile;
+    F.tiles_y = gy;
+    const uint32_t ntiles = F.tiles_x * gy * static_cast<uint32_t>(n_views);
+    F.n_tiles = ntiles;
+    const uint32_t nblocks = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    grid = dim3(nblocks, 1, 1);
+}
+
 int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p, bool want_rgb, FrameArgs& F,
             dim3& grid) {
     if (!c || !cams || !p) return RTX_E_INVALID;
@@ -3041,64 +3134,11 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
         HIP_TRY(c, hipMalloc(&c->d_rgb, npx * 12));
         c->rgb_cap = npx;
     }
-    std::memset(&F, 0, sizeof F);
-    for (int v = 0; v < n_views; ++v) {
-        for (int k = 0; k < 3; ++k) {
-            F.cam[v].origin[k] = cams[v].origin[k]; F.cam[v].right[k] = cams[v].right[k];
-            F.cam[v].up[k] = cams[v].up[k]; F.cam[v].forward[k] = cams[v].forward[k];
-        }
-        F.cam[v].fov = cams[v].fov;
-        // the camera anchor's t bound (CullRay::bt): 4x the farthest corner of the meshes' box + 1
-        if (c->dev.cull_stride) {
-            double R = 0.0;
-            for (int k = 0; k < 8; ++k) {
-                const double dx = cams[v].origin[0] - ((k & 1) ? c->cull_bmax[0] : c->cull_bmin[0]);
-                const double dy = cams[v].origin[1] - ((k & 2) ? c->cull_bmax[1] : c->cull_bmin[1]);
-                const double dz = cams[v].origin[2] - ((k & 4) ? c->cull_bmax[2] : c->cull_bmin[2]);
-                R = std::fmax(R, std::sqrt(dx * dx + dy * dy + dz * dz));
-            }
-            const double bt = 4.0 * R + 1.0;
-            F.cam[v].cull_bt = std::isfinite(bt) && bt < 0x1p60 ? static_cast<float>(bt) : 0.f;   // 0: no pruning
-        }
-        if (c->scene_spec & kSpecRoomPlanes) {   // the room planes' camera numerators (ViewCam)
-            bool ok = true;
-            for (int k = 0; k < 5; ++k) {
-                const float a = c->room_p0[k] - cams[v].origin[kRoomAxes[k]];
-                const float aa = std::fabs(a);
-                F.cam[v].room_a[k] = a;
-                ok = ok && (a == 0.f || (aa >= 0x1p-60f && aa <= 0x1p60f));
-            }
-            F.cam[v].room_fast = ok ? 1u : 0u;
-        }
-    }
-    F.n_views = static_cast<uint32_t>(n_views);
-    F.aspect = static_cast<int>(sp.width) / static_cast<float>(static_cast<int>(sp.height));  // Renderer.cpp:30
-    F.inv_width = 1.f / static_cast<float>(static_cast<int>(sp.width));
-    F.inv_height = 1.f / static_cast<float>(static_cast<int>(sp.height));
-    F.width = sp.width; F.height = sp.height;
-    F.ss_log2 = ss; F.out_width = p->width; F.out_height = p->height;
-    F.mode = p->lighting_mode; F.shadows = p->shadows_enabled ? 1 : 0;
-    F.rshift = p->format.rshift; F.gshift = p->format.gshift; F.bshift = p->format.bshift; F.amask = p->format.amask;
-    const uint32_t groups = (sp.height + kWaveTile - 1) / kWaveTile;
-    uint32_t gy = groups;
-    if (striped) {
-        // every view owns the same number of stripes only if the stripe count divides
-        // evenly; size the grid for the largest owner and let the kernel skip the rest
-        const uint32_t gps = sp.stripe_rows / kWaveTile;
-        const uint32_t nstripes = (groups + gps - 1) / gps;
-        const uint32_t owned = (nstripes + p->stripe_step - 1) / p->stripe_step;
-        F.groups_per_stripe = gps; F.stripe_first = p->stripe_first; F.stripe_step = p->stripe_step;
-        gy = owned * gps;
-    }
-    F.tiles_x = (sp.width + kWaveTile - 1) / kWaveTile;
-    F.tiles_y = gy;
+    frame_shape(c, cams, n_views, p, sp, ss, F, grid);
     F.out_px = c->d_px;
     F.out_rgb = want_rgb ? c->d_rgb : nullptr;
     F.counters = c->d_counters;
-    const uint32_t ntiles = F.tiles_x * gy * static_cast<uint32_t>(n_views);
-    F.n_tiles = ntiles;
-    const uint32_t nblocks = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    grid = dim3(nblocks, 1, 1);
+    const uint32_t ntiles = F.n_tiles;
     // Cost-ordered dispatch (see the kernel): keep one order/cost pair per launch shape.
     if (ntiles > c->sched_cap) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3562,39 +3602,30 @@ extern "C" int rtx_synchronize(rtx_ctx* c) {
 
 namespace {
 
-// Queue the D2H copy of the rows the last render owns (every view) into the caller's
-// full-frame host buffers, on the context stream.  A striped frame is one
-// hipMemcpy2DAsync per view and plane: `stripe_rows` rows every `stripe_step` stripes
+// Queue the D2H copy of the rows a render of `p` with `n_views` views owns into the caller's
+// full-frame host buffers, on the context stream, for every plane with a destination.  A striped
+// frame is one hipMemcpy2DAsync per view and plane: `stripe_rows` rows every `stripe_step` stripes
 // (row pitch of the 2-D copy = stripe_step stripes), plus the trailing partial stripe.
-int queue_owned_copy(rtx_ctx* c, uint32_t* out_px, float* out_rgb) {
-    if (!c || !out_px) return RTX_E_INVALID;
-    if (!c->last_valid) return fail(c, RTX_E_STATE, "nothing rendered yet");
-    if (out_rgb && !c->last_rgb) return fail(c, RTX_E_STATE, "last render did not produce colours");
-    const rtx_render_params& p = c->last;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+struct CopyPlane { char* dst; const char* src; size_t elem; };
+int queue_rows(rtx_ctx* c, const rtx_render_params& p, int n_views, const CopyPlane* planes, int n_planes) {
     const size_t W = p.width, H = p.height;
     const bool striped = p.stripe_rows != 0 && p.stripe_step > 1;
-    for (int v = 0; v < c->last_views; ++v) {
+    for (int v = 0; v < n_views; ++v) {
         const size_t base = static_cast<size_t>(v) * W * H;
-        if (!striped) {
-            HIP_TRY(c, hipMemcpyAsync(out_px + base, c->d_px + base, W * H * 4, hipMemcpyDeviceToHost, c->stream));
-            if (out_rgb)
-                HIP_TRY(c, hipMemcpyAsync(out_rgb + 3 * base, c->d_rgb + 3 * base, W * H * 12, hipMemcpyDeviceToHost,
-                                          c->stream));
-            continue;
-        }
-        const size_t rows = p.stripe_rows, step = p.stripe_step;
-        const size_t first = (p.stripe_first + step - static_cast<uint32_t>(v) % step) % step;
+        const size_t rows = striped ? p.stripe_rows : H, step = striped ? p.stripe_step : 1;
+        const size_t first = striped ? (p.stripe_first + step - static_cast<uint32_t>(v) % step) % step : 0;
         // owned stripes s = first + k*step; the full ones end at or before row H
         size_t n_full = 0;
         if ((first + 1) * rows <= H) n_full = ((H / rows) - 1 - first) / step + 1;
         const size_t last = first + n_full * step;   // next owned stripe (maybe partial or past H)
-        struct Plane { char* dst; const char* src; size_t elem; };
-        const Plane planes[2] = {{reinterpret_cast<char*>(out_px), reinterpret_cast<const char*>(c->d_px), 4},
-                                 {reinterpret_cast<char*>(out_rgb), reinterpret_cast<const char*>(c->d_rgb), 12}};
-        for (const Plane& pl : planes) {
+        for (int k = 0; k < n_planes; ++k) {
+            const CopyPlane& pl = planes[k];
             if (!pl.dst) continue;
+            if (!striped) {
+                HIP_TRY(c, hipMemcpyAsync(pl.dst + base * pl.elem, pl.src + base * pl.elem, W * H * pl.elem,
+                                          hipMemcpyDeviceToHost, c->stream));
+                continue;
+            }
             const size_t row_b = W * pl.elem, off = (base + first * rows * W) * pl.elem;
             if (n_full)
                 HIP_TRY(c, hipMemcpy2DAsync(pl.dst + off, step * rows * row_b, pl.src + off, step * rows * row_b,
@@ -3607,6 +3638,36 @@ int queue_owned_copy(rtx_ctx* c, uint32_t* out_px, float* out_rgb) {
         }
     }
     return RTX_OK;
+}
+
+// ... of the last colour frame
+int queue_owned_copy(rtx_ctx* c, uint32_t* out_px, float* out_rgb) {
+    if (!c || !out_px) return RTX_E_INVALID;
+    if (!c->last_valid) return fail(c, RTX_E_STATE, "nothing rendered yet");
+    if (out_rgb && !c->last_rgb) return fail(c, RTX_E_STATE, "last render did not produce colours");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    const CopyPlane planes[2] = {{reinterpret_cast<char*>(out_px), reinterpret_cast<const char*>(c->d_px), 4},
+                                 {reinterpret_cast<char*>(out_rgb), reinterpret_cast<const char*>(c->d_rgb), 12}};
+    return queue_rows(c, c->last, c->last_views, planes, 2);
+}
+
+// ... of the last hit pass (rtx_ctx::aov_last*)
+int queue_aov_copy(rtx_ctx* c, const rtx_aov_planes* out) {
+    if (!c || !out) return RTX_E_INVALID;
+    if (!c->aov_last_mask) return fail(c, RTX_E_STATE, "no hit pass rendered yet");
+    const uint32_t want = (out->depth ? RTX_AOV_DEPTH : 0u) | (out->normal ? RTX_AOV_NORMAL : 0u) |
+                          (out->material ? RTX_AOV_MATERIAL : 0u) | (out->primitive ? RTX_AOV_PRIMITIVE : 0u);
+    if (want & ~c->aov_last_mask)
+        return fail(c, RTX_E_STATE, "the last hit pass (mask " + std::to_string(c->aov_last_mask) +
+                                        ") did not write every plane asked for (mask " + std::to_string(want) + ")");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const CopyPlane planes[4] = {
+        {reinterpret_cast<char*>(out->depth), reinterpret_cast<const char*>(c->d_aov_depth), 4},
+        {reinterpret_cast<char*>(out->normal), reinterpret_cast<const char*>(c->d_aov_normal), 12},
+        {reinterpret_cast<char*>(out->material), reinterpret_cast<const char*>(c->d_aov_material), 4},
+        {reinterpret_cast<char*>(out->primitive), reinterpret_cast<const char*>(c->d_aov_primitive), 4}};
+    return queue_rows(c, c->aov_last, c->aov_last_views, planes, 4);
 }
 
 }  // namespace
@@ -3649,6 +3710,154 @@ extern "C" int rtx_device_buffers(rtx_ctx* c, void** d_px, void** d_rgb) {
     if (const int rc = join_split(c); rc != RTX_OK) return rc;   // (the caller orders its work after the stream)
     if (d_px) *d_px = c->d_px;
     if (d_rgb) *d_rgb = c->d_rgb;
+    return RTX_OK;
+}
+
+// ---- the hit pass (PHASE 7): rtx_render_aov* ----------------------------------------------------
+namespace {
+
+// One more plane of `n` elements of `elem` bytes (the frames queued on the stream may still write the old one).
+template <class T>
+int aov_alloc(rtx_ctx* c, T*& d, size_t n, size_t elem) {
+    if (d) return RTX_OK;
+    HIP_TRY(c, hipMalloc(&d, n * elem));
+    return RTX_OK;
+}
+
+// Checks, the planes of `mask` and the launch record of a pass; nothing of the colour frames' state
+// (schedule, split tuner, motion mode, frames in flight, the last-frame record) is read or written.
+int aov_prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p, uint32_t mask,
+                FrameArgs& F, dim3& grid) {
+    if (!c || !cams || !p) return RTX_E_INVALID;
+    if (mask == 0 || (mask & ~static_cast<uint32_t>(RTX_AOV_ALL)))
+        return fail(c, RTX_E_INVALID, "AOV mask must be a non-empty set of RTX_AOV_* bits (got " + std::to_string(mask) + ")");
+    if (n_views < 1 || n_views > kMaxViews) return fail(c, RTX_E_INVALID, "n_views must be 1..8");
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    if (c->ss_log2)
+        return fail(c, RTX_E_UNSUPPORTED, "no hit pass on a supersampled context (factor " +
+                                              std::to_string(1u << c->ss_log2) + "): averaged ids mean nothing");
+    if (p->width == 0 || p->height == 0 || p->width > 65536 || p->height > 65536)
+        return fail(c, RTX_E_INVALID, "bad image size");
+    const bool striped = p->stripe_rows != 0 && p->stripe_step > 1;
+    if (striped && (p->stripe_rows % 16 != 0 || p->stripe_first >= p->stripe_step))
+        return fail(c, RTX_E_INVALID, "stripe_rows must be a multiple of 16 and stripe_first < stripe_step");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = static_cast<size_t>(p->width) * p->height * static_cast<size_t>(n_views);
+    // the planes of every mask seen so far, each allocated when first asked for
+    uint32_t need = mask | (c->d_aov_depth ? RTX_AOV_DEPTH : 0u) | (c->d_aov_normal ? RTX_AOV_NORMAL : 0u) |
+                    (c->d_aov_material ? RTX_AOV_MATERIAL : 0u) | (c->d_aov_primitive ? RTX_AOV_PRIMITIVE : 0u);
+    if (npx > c->aov_cap) {   // larger planes: all of them again, at the new size
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_aov_depth); (void)hipFree(c->d_aov_normal);
+        (void)hipFree(c->d_aov_material); (void)hipFree(c->d_aov_primitive);
+        c->d_aov_depth = c->d_aov_normal = nullptr;
+        c->d_aov_material = c->d_aov_primitive = nullptr;
+        c->aov_last_mask = 0;   // (their contents are gone)
+        c->aov_cap = npx;
+    }
+    int rc = RTX_OK;
+    if (need & RTX_AOV_DEPTH) rc = aov_alloc(c, c->d_aov_depth, c->aov_cap, 4);
+    if (rc == RTX_OK && (need & RTX_AOV_NORMAL)) rc = aov_alloc(c, c->d_aov_normal, c->aov_cap, 12);
+    if (rc == RTX_OK && (need & RTX_AOV_MATERIAL)) rc = aov_alloc(c, c->d_aov_material, c->aov_cap, 4);
+    if (rc == RTX_OK && (need & RTX_AOV_PRIMITIVE)) rc = aov_alloc(c, c->d_aov_primitive, c->aov_cap, 4);
+    if (rc != RTX_OK) return rc;
+    frame_shape(c, cams, n_views, p, *p, 0u, F, grid);
+    F.aov_mask = mask;
+    F.aov_depth = c->d_aov_depth;
+    F.aov_normal = c->d_aov_normal;
+    F.aov_material = c->d_aov_material;
+    F.aov_primitive = c->d_aov_primitive;
+    return RTX_OK;
+}
+
+// Queue the pass on the context stream, like the counting launch: behind the last frame's split chain,
+// every tile rendered by the one launch (no order, no costs, no heavy set), with the walk the scene's
+// colour frames take (the exact cull, or the deep stacks, which walk without it).
+int aov_launch(rtx_ctx* c, const FrameArgs& F, dim3 grid) {
+    if (grid.x == 0) return RTX_OK;
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    if (c->hbm_stack) {
+        if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
+        hipLaunchKernelGGL((rtx_render_kernel<false, 7, true, 0, true>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, F);
+    } else if (c->deep_stack) {
+        hipLaunchKernelGGL((rtx_render_kernel<false, 7, true>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, F);
+    } else {
+        if (c->dev.cull_stride) {   // the views' camera-anchor cull records, as a frame would
+            if (const int rc = cull_views(c, F); rc != RTX_OK) return rc;
+        }
+        if (c->dev.cull_stride)   // (cull_views drops the records when it cannot build them)
+            hipLaunchKernelGGL((rtx_render_kernel<false, 7, false, 0, false, true>), grid, dim3(kBlockThreads), 0,
+                               c->stream, c->dev, F);
+        else
+            hipLaunchKernelGGL((rtx_render_kernel<false, 7>), grid, dim3(kBlockThreads), 0, c->stream, c->dev, F);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return RTX_OK;
+}
+
+}  // namespace
+
+extern "C" int rtx_render_aov_async(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p,
+                                    uint32_t mask) {
+    FrameArgs F;
+    dim3 grid;
+    int rc = aov_prepare(c, cams, n_views, p, mask, F, grid);
+    if (rc != RTX_OK) return rc;
+    rc = aov_launch(c, F, grid);
+    if (rc != RTX_OK) return rc;
+    c->aov_last = *p;
+    c->aov_last_views = n_views;
+    c->aov_last_mask = mask;
+    return RTX_OK;
+}
+
+extern "C" int rtx_gather_aov_async(rtx_ctx* c, const rtx_aov_planes* out) { return queue_aov_copy(c, out); }
+
+extern "C" int rtx_download_aov(rtx_ctx* c, const rtx_aov_planes* out) {
+    const int rc = queue_aov_copy(c, out);
+    if (rc != RTX_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+extern "C" int rtx_render_aov(rtx_ctx* c, const rtx_camera* cam, const rtx_render_params* p, uint32_t mask,
+                              const rtx_aov_planes* out) {
+    if (!out) return RTX_E_INVALID;
+    const int rc = rtx_render_aov_async(c, cam, 1, p, mask);
+    if (rc != RTX_OK) return rc;
+    return rtx_download_aov(c, out);
+}
+
+extern "C" int rtx_device_aov_buffers(rtx_ctx* c, rtx_aov_planes* out) {
+    if (!c || !out) return RTX_E_INVALID;
+    out->depth = c->d_aov_depth;
+    out->normal = c->d_aov_normal;
+    out->material = c->d_aov_material;
+    out->primitive = c->d_aov_primitive;
+    return RTX_OK;
+}
+
+extern "C" int rtx_time_aov_frames(rtx_ctx* c, const rtx_camera* cam, const rtx_render_params* p, uint32_t mask,
+                                   int iters, float* mean_ms) {
+    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
+    FrameArgs F;
+    dim3 grid;
+    int rc = aov_prepare(c, cam, 1, p, mask, F, grid);
+    if (rc != RTX_OK) return rc;
+    if (const int rc2 = join_split(c); rc2 != RTX_OK) return rc2;   // (a colour frame's chain: outside the timing)
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        rc = aov_launch(c, F, grid);
+        if (rc != RTX_OK) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
+    c->aov_last = *p;
+    c->aov_last_views = 1;
+    c->aov_last_mask = mask;
     return RTX_OK;
 }
 

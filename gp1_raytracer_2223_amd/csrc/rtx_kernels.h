@@ -252,6 +252,14 @@ struct FrameArgs {
     // samples lie in one wave tile, whose epilogue resolves them.  k = 1: 0 and width x height.
     uint32_t ss_log2;
     uint32_t out_width, out_height;
+    // Hit pass (PHASE 7, rtx_render_aov*): the planes of rtx_aov_planes in HBM, view v at
+    // v * width * height elements (3 x that for the normal), and the RTX_AOV_* bits to write; a plane
+    // outside the mask is never touched (its pointer may be null).  Last, so that no field above moves.
+    uint32_t aov_mask;
+    float* __restrict__ aov_depth;
+    float* __restrict__ aov_normal;
+    uint32_t* __restrict__ aov_material;
+    uint32_t* __restrict__ aov_primitive;
 };
 
 // Light-major frames (opt-in: RTX_LIGHT_MAJOR=1 always, =auto while a launch has at most kLmSlotsPercent /

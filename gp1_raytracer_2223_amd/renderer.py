@@ -22,6 +22,31 @@ from . import abi
 from .scene import HostScene
 
 
+AOV_DEPTH, AOV_NORMAL, AOV_MATERIAL, AOV_PRIMITIVE, AOV_ALL = (abi.RTX_AOV_DEPTH, abi.RTX_AOV_NORMAL,
+                                                                 abi.RTX_AOV_MATERIAL, abi.RTX_AOV_PRIMITIVE,
+                                                                 abi.RTX_AOV_ALL)
+# plane name -> (mask bit, dtype, elements per pixel), in rtx_aov_planes' order
+AOV_PLANES = {"depth": (AOV_DEPTH, np.float32, 1), "normal": (AOV_NORMAL, np.float32, 3),
+              "material": (AOV_MATERIAL, np.uint32, 1), "primitive": (AOV_PRIMITIVE, np.uint32, 1)}
+
+
+def aov_host_planes(width: int, height: int, mask: int, n_views: int = 1) -> dict:
+    """Zeroed host planes (flat numpy arrays) for the planes of `mask`."""
+    n = int(width) * int(height) * int(n_views)
+    return {k: np.zeros(e * n, dt) for k, (bit, dt, e) in AOV_PLANES.items() if mask & bit}
+
+
+def aov_struct(planes: dict) -> abi.AovPlanes:
+    """rtx_aov_planes over a dict of host planes (a missing name = NULL: skipped)."""
+    out = abi.AovPlanes()
+    for k, (_, dt, _) in AOV_PLANES.items():
+        a = planes.get(k)
+        if a is not None:
+            assert a.dtype == dt and a.flags.c_contiguous, k
+            setattr(out, k, a.ctypes.data_as(C.POINTER(C.c_float if dt == np.float32 else C.c_uint32)))
+    return out
+
+
 class LightingMode:
     ObservedArea, Radiance, BRDF, Combined, Count = 0, 1, 2, 3, 4
 
@@ -85,6 +110,47 @@ class DeviceContext:
             rgbp = out_rgb.ctypes.data_as(C.POINTER(C.c_float))
         abi.check(self.lib.rtx_gather_async(self.h, out_px.ctypes.data_as(C.POINTER(C.c_uint32)), rgbp),
                   "rtx_gather_async", self.h)
+
+    def render_aov(self, cam: abi.Camera, params: abi.RenderParams, mask: int = AOV_ALL) -> dict:
+        """The hit pass (rtx_render_aov), blocking: {"depth", "normal", "material", "primitive"} ->
+        flat numpy planes, those of `mask` (include/rtx.h gives their values)."""
+        planes = aov_host_planes(params.width, params.height, mask)
+        out = aov_struct(planes)
+        abi.check(self.lib.rtx_render_aov(self.h, C.byref(cam), C.byref(params), int(mask), C.byref(out)),
+                  "rtx_render_aov", self.h)
+        return planes
+
+    def render_aov_async(self, cams, params: abi.RenderParams, mask: int = AOV_ALL) -> None:
+        """Queue the hit pass of one camera or a sequence of up to 8 (rtx_render_aov_async)."""
+        if isinstance(cams, abi.Camera):
+            cams = [cams]
+        arr = (abi.Camera * len(cams))(*cams)
+        abi.check(self.lib.rtx_render_aov_async(self.h, arr, len(cams), C.byref(params), int(mask)),
+                  "rtx_render_aov_async", self.h)
+
+    def gather_aov_async(self, planes: dict) -> None:
+        """Queue the D2H copy of the rows the last hit pass owns into full-frame host planes
+        (rtx_gather_aov_async); complete after synchronize()."""
+        out = aov_struct(planes)
+        abi.check(self.lib.rtx_gather_aov_async(self.h, C.byref(out)), "rtx_gather_aov_async", self.h)
+
+    def download_aov(self, planes: dict) -> dict:
+        """Copy the last hit pass's owned rows into `planes` and wait (rtx_download_aov)."""
+        out = aov_struct(planes)
+        abi.check(self.lib.rtx_download_aov(self.h, C.byref(out)), "rtx_download_aov", self.h)
+        return planes
+
+    def device_aov_buffers(self) -> dict:
+        """Device addresses of the HBM planes (0 for a plane no mask has named yet)."""
+        out = abi.AovPlanes()
+        abi.check(self.lib.rtx_device_aov_buffers(self.h, C.byref(out)), "rtx_device_aov_buffers", self.h)
+        return {k: C.cast(getattr(out, k), C.c_void_p).value or 0 for k in AOV_PLANES}
+
+    def time_aov_frames(self, cam, params, mask: int, iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_aov_frames(self.h, C.byref(cam), C.byref(params), int(mask), int(iters),
+                                               C.byref(ms)), "rtx_time_aov_frames", self.h)
+        return ms.value
 
     def time_frames(self, cam, params, iters: int) -> float:
         ms = C.c_float()
@@ -197,6 +263,14 @@ class DeviceGroup:
         self._check(rc, "rtx_group_render")
         return px, rgb
 
+    def render_aov(self, cam: abi.Camera, params: abi.RenderParams, mask: int = AOV_ALL) -> dict:
+        """The hit pass over the members' stripes (rtx_group_render_aov): the planes of `mask`."""
+        planes = aov_host_planes(params.width, params.height, mask)
+        out = aov_struct(planes)
+        self._check(self.lib.rtx_group_render_aov(self.h, C.byref(cam), C.byref(params), int(mask), C.byref(out)),
+                    "rtx_group_render_aov")
+        return planes
+
 
 class DeviceAnimation:
     """Owns one rtx_anim: Scene::Update of a host scene's turning meshes done on the device
@@ -294,14 +368,26 @@ class Renderer:
         return abi.make_params(self.m_Width, self.m_Height, self.m_CurrentLightingMode, self.m_ShadowsEnabled,
                                self.format, sr, first, step)
 
-    def Render(self, scene: HostScene, upload: bool = True, want_rgb: bool = False) -> np.ndarray:
-        """Renderer::Render (Renderer.cpp:34-98): blocking; fills self.buffer."""
+    def _view(self, scene: HostScene, upload: bool):
+        """The scene's flattened view and camera, uploaded when asked to or when it is not the
+        uploaded scene's current state."""
         s, cam = scene.view()
         same = self._scene_ref is not None and self._scene_ref() is scene and self._scene_gen == scene.generation
         if upload or not same:
             self.ctx.upload(s)
             self._scene_ref = weakref.ref(scene)
             self._scene_gen = scene.generation
+        return s, cam
+
+    def RenderAOV(self, scene: HostScene, mask: int = AOV_ALL, upload: bool = True) -> dict:
+        """The hit pass of the frame Render would render (same size, stripes and upload bookkeeping):
+        the planes of `mask` as flat numpy arrays; rows this renderer's stripes do not own stay 0."""
+        _, cam = self._view(scene, upload)
+        return self.ctx.render_aov(cam, self.params(), mask)
+
+    def Render(self, scene: HostScene, upload: bool = True, want_rgb: bool = False) -> np.ndarray:
+        """Renderer::Render (Renderer.cpp:34-98): blocking; fills self.buffer."""
+        s, cam = self._view(scene, upload)
         n = self.m_Width * self.m_Height
         rgb = np.zeros(3 * n, np.float32) if want_rgb else None
         rc = self.ctx.lib.rtx_render(self.ctx.h, C.byref(cam), C.byref(self.params()),

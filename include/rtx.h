@@ -231,6 +231,62 @@ int rtx_host_unregister(rtx_ctx* ctx, void* ptr);
  * frames queued so far are complete in it after rtx_synchronize (a repeated frame may leave
  * its split launches running after rtx_render_async returns, on a stream of its own). */
 int rtx_device_buffers(rtx_ctx* ctx, void** d_pixels, void** d_rgb);
+
+/* ---- hit-record planes (AOVs): what each pixel's primary ray hit -------------------
+ * The hit pass runs Scene::GetClosestHit (source/Scene.cpp:29-66) for every pixel's primary ray,
+ * exactly as a colour frame does, and writes the closestHit record instead of shading it: no light
+ * loop, no shadow rays, no colour.  Every plane is row-major width x height; view v starts at
+ * v*width*height elements of the plane (3x that for the normal plane).  The values are the colour
+ * frame's own, word for word the reference's record:
+ *
+ *   plane      type         hit                                             miss
+ *   depth      float        closestHit.t                                    FLT_MAX (the empty HitRecord)
+ *   normal     3 x float    closestHit.normal: a sphere's normalised as     0, 0, 0
+ *                           Scene.cpp does, a plane's or triangle's copied
+ *   material   uint32_t     closestHit.materialIndex                        0
+ *   primitive  uint32_t     kind << 30 | index                              0
+ *
+ * kind: 1 = sphere, 2 = plane, 3 = triangle.  A sphere's or plane's index is its position in
+ * rtx_scene::spheres / planes.  A triangle's is its position in the concatenation of the meshes'
+ * `indices` arrays as uploaded: mesh 0's n_indices/3 triangles first, a mesh's triangle k being its
+ * indices 3k .. 3k+2.  After a device Update (rtx_anim_update) the order within a mesh is the one
+ * rtx_anim_download returns. */
+enum { RTX_AOV_DEPTH = 1, RTX_AOV_NORMAL = 2, RTX_AOV_MATERIAL = 4, RTX_AOV_PRIMITIVE = 8, RTX_AOV_ALL = 15 };
+#define RTX_PRIM_KIND(p) ((uint32_t)(p) >> 30)
+#define RTX_PRIM_INDEX(p) ((uint32_t)(p) & 0x3fffffffu)
+typedef struct rtx_aov_planes {
+    float* depth;
+    float* normal;
+    uint32_t* material;
+    uint32_t* primitive;
+} rtx_aov_planes;
+/* Queue the hit pass of n_views (1..8) cameras on the context stream, into the context's HBM planes
+ * named by `mask` (RTX_AOV_* bits; planes are allocated when a mask first names them).  Stripes and
+ * views are exactly those of rtx_render_views_async; lighting_mode, shadows_enabled and format are
+ * ignored.  The pass is ordered with the colour frames and uploads queued on the context before and
+ * after it, writes nothing of the colour frame buffer and leaves the frame schedule as it was.
+ * Errors (the context renders on after each): mask 0 or with unknown bits RTX_E_INVALID; no scene
+ * RTX_E_STATE; a supersample factor other than 1 on the context (rtx_set_supersample)
+ * RTX_E_UNSUPPORTED: a pixel's samples may hit different primitives, and an average of ids, or of
+ * normals across them, means nothing. */
+int rtx_render_aov_async(rtx_ctx* ctx, const rtx_camera* cams, int n_views, const rtx_render_params* params,
+                         uint32_t mask);
+/* Blocking: the pass of one camera, then rtx_download_aov into `out` (whose non-NULL members must be
+ * planes of `mask`). */
+int rtx_render_aov(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_params* params, uint32_t mask,
+                   const rtx_aov_planes* out);
+/* Copy the rows the last hit pass owns (every view) into the caller's full-frame planes and wait;
+ * NULL members are skipped, one the last pass did not write returns RTX_E_STATE.  The context keeps
+ * the last pass's size, views, stripes and mask beside the last colour frame's: rtx_download /
+ * rtx_gather_async after a pass still copy the colour frame, and the reverse. */
+int rtx_download_aov(rtx_ctx* ctx, const rtx_aov_planes* out);
+/* The same copies queued on the context stream (rows the pass does not own are never written, like
+ * rtx_gather_async); complete after rtx_synchronize. */
+int rtx_gather_aov_async(rtx_ctx* ctx, const rtx_aov_planes* out);
+/* Device pointers of the HBM planes (NULL for a plane no mask has named yet); the passes queued so
+ * far are complete in them after rtx_synchronize. */
+int rtx_device_aov_buffers(rtx_ctx* ctx, rtx_aov_planes* out);
+
 /* ---- one frame over several GPUs from one process ------------------
  * The reference's Renderer::Render covers the frame with parallel_for
  * (source/Renderer.cpp:79-85); a group covers it with G render contexts instead.  Rows are
@@ -255,6 +311,10 @@ int rtx_group_render(rtx_group* group, const rtx_camera* cam, const rtx_render_p
                      uint32_t* out_pixels, float* out_rgb);
 /* rtx_set_supersample on every member (stripes stay rows of the width x height frame). */
 int rtx_group_set_supersample(rtx_group* group, uint32_t k);
+/* The hit pass (rtx_render_aov) over the group's members, the stripes dealt as rtx_group_render deals
+ * them; blocks until every non-NULL plane of `out` (planes of `mask`) is complete. */
+int rtx_group_render_aov(rtx_group* group, const rtx_camera* cam, const rtx_render_params* params, uint32_t mask,
+                         const rtx_aov_planes* out);
 
 /* ---- animated meshes: Scene::Update on the device -------------------
  * Replaces, per animated frame, the host's TriangleMesh::UpdateTransforms + BuildBVH

@@ -21,6 +21,10 @@ int rtx_time_frames(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_params
                     int iters, float* mean_ms);
 int rtx_time_views(rtx_ctx* ctx, const rtx_camera* cams, int n_views, const rtx_render_params* params,
                    int iters, float* mean_ms);
+/* The same for the hit pass (rtx_render_aov_async with one camera and `mask`): `iters` back-to-back
+ * passes, the mean device time of one in ms.  The planes then hold the pass, as after rtx_render_aov_async. */
+int rtx_time_aov_frames(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_params* params, uint32_t mask,
+                        int iters, float* mean_ms);
 /* Bytes of HBM the uploaded scene image occupies. */
 int rtx_scene_bytes(const rtx_ctx* ctx, uint64_t* bytes);
 /* Diagnostics: copy the context's current scene image (DESIGN.md §2 layout) after its queued

@@ -49,6 +49,35 @@ public:
         Render(cam);
     }
 
+    // The hit pass of the frame Render would render (rtx_render_aov; not in the reference): what every
+    // pixel's primary ray hit, the planes of `mask` filled and the others left empty (rtx.h gives the
+    // values: depth, normal, material index, primitive kind << 30 | index).
+    struct AovFrame {
+        std::vector<float> depth, normal;          // width*height, 3*width*height
+        std::vector<uint32_t> material, primitive; // width*height each
+    };
+    AovFrame RenderAov(const rtx_camera& cam, uint32_t mask = RTX_AOV_ALL) {
+        const rtx_render_params p = Params();
+        const size_t n = static_cast<size_t>(m_Width) * m_Height;
+        AovFrame f;
+        if (mask & RTX_AOV_DEPTH) f.depth.resize(n);
+        if (mask & RTX_AOV_NORMAL) f.normal.resize(3 * n);
+        if (mask & RTX_AOV_MATERIAL) f.material.resize(n);
+        if (mask & RTX_AOV_PRIMITIVE) f.primitive.resize(n);
+        const rtx_aov_planes out = {f.depth.empty() ? nullptr : f.depth.data(), f.normal.empty() ? nullptr : f.normal.data(),
+                                    f.material.empty() ? nullptr : f.material.data(),
+                                    f.primitive.empty() ? nullptr : f.primitive.data()};
+        Check(rtx_render_aov(m_Ctx, &cam, &p, mask, &out), "rtx_render_aov");
+        return f;
+    }
+    AovFrame RenderAov(rtx_host_scene* scene, uint32_t mask = RTX_AOV_ALL, bool upload = true) {
+        rtx_scene s;
+        rtx_camera cam;
+        Check(rtx_host_scene_view(scene, &s, &cam), "rtx_host_scene_view");
+        if (upload) Upload(s);
+        return RenderAov(cam, mask);
+    }
+
     void CycleLightingMode() {                                                     // Renderer.cpp:189-193
         m_CurrentLightingMode = static_cast<LightingMode>((static_cast<int>(m_CurrentLightingMode) + 1) %
                                                           static_cast<int>(LightingMode::Count));
