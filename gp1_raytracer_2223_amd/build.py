@@ -2,7 +2,8 @@
 
 Outputs (git-ignored, travel to the GPU box with the gpurun snapshot):
   gp1_raytracer_2223_amd/lib/librtx_host.so   C++ host scene layer (g++)
-  gp1_raytracer_2223_amd/lib/librtx_hip.so    HIP render path for gfx950 (hipcc)
+  gp1_raytracer_2223_amd/lib/librtx_hip.so    HIP render path for gfx950 (hipcc), linked from one
+                                              object per unit under lib/obj/ (only stale units recompile)
   oracle/_build/librtx_oracle.so              C restatement (test infrastructure)
   oracle/_ref/ref_harness                     the reference's own sources (test infra,
                                               only when /root/reference exists)
@@ -16,6 +17,7 @@ import os
 import shutil
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
@@ -54,23 +56,49 @@ def build_host(force: bool = False) -> Path:
     return out
 
 
+# The units of librtx_hip.so.  The kernel unit comes first: its object leads the link line, so its
+# code object is the first of the library's fat binary (tests/test_isa.py reads that one).
+HIP_KERNEL_UNIT = CSRC / "rtx_hip.hip"
+HIP_SOURCES = [HIP_KERNEL_UNIT, CSRC / "rtx_cull_records.hip", CSRC / "rtx_sched.hip", CSRC / "rtx_context.hip",
+               CSRC / "rtx_upload.hip", CSRC / "rtx_frame.hip", CSRC / "rtx_aov.hip", CSRC / "rtx_diag.hip",
+               CSRC / "rtx_policy.hip", CSRC / "rtx_anim.hip", CSRC / "rtx_anim_host.hip", CSRC / "rtx_group.cpp"]
+# Every unit gets every flag (the host units compute floats that reach the pixels too).
+# -fno-slp-vectorize: the SLP packer turns independent f32 ops into v_pk_* plus
+# v_mov shuffles; measured 8 % slower on the render kernel (profiles/r01/ablate_*.txt).
+# -structurizecfg-skip-uniform-regions: wave-uniform loops and branches (every loop of
+# the BVH walk) stay plain s_cbranch_scc instead of being structurized into SGPR
+# lane-mask phis (s_cselect -1/0 + s_and vcc, exec per exit): -6 % SALU per wave.
+HIP_FLAGS = [f"--offload-arch={ARCH}", "-std=c++17", "-O3", "-ffp-contract=off",
+             "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
+             "-mllvm", "-structurizecfg-skip-uniform-regions=true",
+             "-DRTX_MIN_WAVES_PER_EU=6", "-fPIC", "-pthread",
+             "-Wall", f"-I{INC}", f"-I{CSRC}"]
+HIP_JOBS = 8   # units compiled at once (fixed: a shared machine's CPU count says nothing)
+
+
+def hip_deps() -> list[Path]:
+    """What every unit's object depends on besides its own source (the flags live in this file)."""
+    return list(CSRC.glob("*.h")) + [INC / "rtx.h", INC / "rtx_diag.h", Path(__file__)]
+
+
+def build_hip_lib(out: Path, objdir: Path, srcs: list[Path], flags: list[str], force: bool = False) -> Path:
+    """Compile the stale units of `srcs` to objects under `objdir`, HIP_JOBS at a time, and link them in
+    the order given into `out`."""
+    objdir.mkdir(parents=True, exist_ok=True)
+    objs = [objdir / (s.stem + ".o") for s in srcs]
+    todo = [(s, o) for s, o in zip(srcs, objs) if force or _stale(o, [s] + hip_deps())]
+    with ThreadPoolExecutor(max_workers=HIP_JOBS) as pool:
+        for f in [pool.submit(_run, [HIPCC, *flags, "-c", s, "-o", o]) for s, o in todo]:
+            f.result()
+    _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-pthread", *objs, "-o", out])
+    return out
+
+
 def build_hip(force: bool = False) -> Path:
     LIB.mkdir(exist_ok=True)
     out = LIB / "librtx_hip.so"
-    srcs = [CSRC / "rtx_hip.hip", CSRC / "rtx_policy.hip", CSRC / "rtx_anim.hip", CSRC / "rtx_anim_host.hip",
-            CSRC / "rtx_group.cpp"]
-    deps = srcs + list(CSRC.glob("*.h")) + [INC / "rtx.h", INC / "rtx_diag.h", Path(__file__)]   # flags live here
-    if force or _stale(out, deps):
-        # -fno-slp-vectorize: the SLP packer turns independent f32 ops into v_pk_* plus
-        # v_mov shuffles; measured 8 % slower on the render kernel (profiles/r01/ablate_*.txt).
-        # -structurizecfg-skip-uniform-regions: wave-uniform loops and branches (every loop of
-        # the BVH walk) stay plain s_cbranch_scc instead of being structurized into SGPR
-        # lane-mask phis (s_cselect -1/0 + s_and vcc, exec per exit): -6 % SALU per wave.
-        _run([HIPCC, f"--offload-arch={ARCH}", "-std=c++17", "-O3", "-ffp-contract=off",
-              "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-              "-mllvm", "-structurizecfg-skip-uniform-regions=true",
-              "-DRTX_MIN_WAVES_PER_EU=6", "-fPIC", "-shared", "-pthread",
-              "-Wall", f"-I{INC}", f"-I{CSRC}", *srcs, "-o", out])
+    if force or _stale(out, HIP_SOURCES + hip_deps()):
+        build_hip_lib(out, LIB / "obj", HIP_SOURCES, HIP_FLAGS, force)
     return out
 
 

@@ -1,5 +1,5 @@
 // rtx_anim.h — Scene::Update on the device for animated meshes: the
-// interface between the C-ABI (rtx_anim_* in rtx_hip.hip) and the build kernels
+// interface between the C-ABI (rtx_anim_* in rtx_anim_host.hip) and the build kernels
 // (rtx_anim.hip).  Internal; not part of the installed headers.
 //
 // Two launches restate, in HBM and bit for bit,

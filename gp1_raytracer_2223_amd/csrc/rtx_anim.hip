@@ -1602,7 +1602,7 @@ __global__ void __launch_bounds__(kAnimThreads) rtx_anim_build(const Launch L) {
 }
 
 // ============================================================ launch 3: numbering and output
-// The split-rendering frontier of rtx_hip.hip build_parts — split the part with the most
+// The split-rendering frontier of rtx_upload.hip build_parts — split the part with the most
 // triangles (the first in frontier order on a tie) while fewer than part_cap parts exist and a
 // part is an internal node less than 31 levels deep — and the status words; workgroup
 // kOutGroups of the output launch, beside the records.

@@ -1,22 +1,26 @@
-// rtx_ctx.h — the render context (rtx_ctx, the opaque handle of include/rtx.h) and the frame
-// policies that rtx_policy.hip implements for rtx_hip.hip: the split tuner, the throughput /
-// in-flight choice, the frontier refinement and the deferred join of the split chain.  Internal to
-// librtx_hip.so.
+// rtx_ctx.h — the render context (rtx_ctx, the opaque handle of include/rtx.h) and what the host
+// units of librtx_hip.so call across each other (namespace rtxh): the frame policies of
+// rtx_policy.hip (the split tuner, the throughput / in-flight choice, the frontier refinement and
+// the deferred join of the split chain), the upload (rtx_upload.hip), the cull records
+// (rtx_cull_records.hip), the tile schedule (rtx_sched.hip) and the frame (rtx_frame.hip).  The
+// render kernel's launches are rtx_launch.h's.  Internal to librtx_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdint>
 #include <string>
 #include <vector>
 
 #include "rtx.h"
+#include "rtx_diag.h"
 #include "rtx_cull.h"
 #include "rtx_kernels.h"
 
 using namespace rtxd;
 
-// The two kinds of cull-record tree values (rtx_cull_tris / rtx_cull_nodes in rtx_hip.hip): margin +
+// The two kinds of cull-record tree values (rtx_cull_tris / rtx_cull_nodes in rtx_cull_records.hip): margin +
 // dt per triangle, a box per node slot.  Margins and dt are >= 0 or +inf (never NaN), box bounds never
 // NaN either, so the trees' min / max folds are exact in any order.
 struct alignas(8) CullMD {
@@ -290,9 +294,46 @@ struct UploadLayout {
     size_t tri_off = 0, node_off = 0, part_off = 0, mesh_off = 0;   // section offsets in the image
 };
 
-// Upload a scene into the context's next image (rtx_hip.hip; rtx_upload_scene, and the device
+// Free the device buffer `p` and allocate it again for `need` units of `elem` bytes; `cap` = the
+// units it holds (0 when the allocation fails).  No synchronisation: the caller has made sure that
+// nothing queued still reads the old buffer.
+template <class T>
+int device_grow(rtx_ctx* c, T*& p, size_t& cap, size_t need, size_t elem = sizeof(T)) {
+    (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(c, hipMalloc(&p, need * elem));
+    cap = need;
+    return RTX_OK;
+}
+
+// Upload a scene into the context's next image (rtx_upload.hip; rtx_upload_scene, and the device
 // Update's registration with `lay`).
 int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay);
+
+// rtx_cull_records.hip: at upload, the light anchors (tmax bound T[l]) of the image's cull records;
+// before a frame, the record launches its views still need; and the device's octant copies 1..7 of
+// an uploaded node array (`n2` node records per copy, copies `stride` float4 apart).
+void cull_records(rtx_ctx* c, const std::vector<float>& T, const rtx_light* lights, uint32_t n_lights);
+int cull_views(rtx_ctx* c, const FrameArgs& F);
+void octant_expand(float4* nodes, uint32_t n2, uint32_t stride, hipStream_t s);
+
+// rtx_sched.hip: queue the next frames' dispatch order and heavy set from measured frame F's tile costs.
+int sched_update(rtx_ctx* c, const FrameArgs& F);
+
+// rtx_frame.hip: the launch record shared by a colour frame and the hit pass; a colour frame's
+// checks, buffers and schedule; the HSTK variant's stacks; the frame's launches (count: 0 a frame,
+// 1 / 2 the instrumented kernels); the record of the last frame; and the D2H copy of a frame's
+// owned rows, plane by plane.
+void frame_shape(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p,
+                 const rtx_render_params& sp, uint32_t ss, FrameArgs& F, dim3& grid);
+int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p, bool want_rgb, FrameArgs& F,
+            dim3& grid);
+int ensure_hbm_stacks(rtx_ctx* c, uint32_t groups);
+int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count);
+void remember(rtx_ctx* c, const rtx_render_params* p, int n_views, bool rgb);
+struct CopyPlane { char* dst; const char* src; size_t elem; };
+int queue_rows(rtx_ctx* c, const rtx_render_params& p, int n_views, const CopyPlane* planes, int n_planes);
 
 // One step of the split-threshold tuner from a timed frame's main kernel and chain (ms).
 void split_tune(rtx_ctx* c, float main_ms, float chain_ms);

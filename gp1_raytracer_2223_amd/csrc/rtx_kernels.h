@@ -1,5 +1,6 @@
 // rtx_kernels.h — device layout of the uploaded scene and the per-frame launch record.
-// Shared by the kernels and the host-side upload code in rtx_hip.hip.
+// Shared by the kernels (rtx_hip.hip, rtx_cull_records.hip, rtx_sched.hip) and the host units
+// that fill them in (rtx_upload.hip, rtx_frame.hip, rtx_aov.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -130,6 +131,13 @@ enum Counter {
     kCullTests, kNumCounters
 };
 constexpr int kModelCounters = 12;
+
+[[maybe_unused]] constexpr int kStampWords = 8;   // + primary-hit time, shadow-walk time (RTX_STAMPS)
+// split waves' {sum, max, steps} per (phase, part) in 64 shards by wave index: one address per
+// (phase, part) took every split wave's atomics into one L2 channel and slowed the whole frame ~6x
+[[maybe_unused]] constexpr int kStampShards = 64;
+
+#define RTX_PI 3.14159265358979323846f   // MathHelpers.h:7
 
 // HBM scene image, every record 16-byte aligned so a wave-uniform index
 // becomes one s_load_dwordx4/x8 (scalar cache) instead of 64 vector loads:

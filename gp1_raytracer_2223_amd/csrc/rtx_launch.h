@@ -1,0 +1,25 @@
+// rtx_launch.h — the launches of rtx_render_kernel (rtx_hip.hip) as plain host functions: each picks
+// the instantiation from run-time facts and queues it on `s`; the caller checks hipGetLastError.
+// A combination no frame takes (one without an instantiation) aborts.  Internal to librtx_hip.so.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "rtx_kernels.h"
+
+namespace rtxh {
+
+// PHASE `phase` (0..6) of a frame in its specialised variant (index into kSpecVariants, -1: the
+// generic kernel), with the cull variant when the scene has cull records and the SS one for a
+// supersampled frame.
+void launch_render_phase(int phase, int variant, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
+                         const rtxd::FrameArgs& F);
+// The one-launch frames without a specialised variant: the counting kernels (plain, with the cull,
+// deep, deep with HBM stacks) and the deep-stack frames (deep, deep with HBM stacks).
+void launch_render_one(bool count, bool deep, bool hstk, bool cull, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
+                       const rtxd::FrameArgs& F);
+// The hit pass (PHASE 7): the generic kernel with every stack, or with the exact cull.
+void launch_hit_pass(bool deep, bool hstk, bool cull, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
+                     const rtxd::FrameArgs& F);
+
+}  // namespace rtxh

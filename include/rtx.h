@@ -28,7 +28,9 @@
  * This header is the product boundary: contexts, scene upload, rendering, the host gather, one frame
  * over several GPUs (rtx_group_*) and the device-side Update (rtx_anim_*).  Timing, work counters
  * and the scheduler's / exact cull's internals are in rtx_diag.h; the environment knobs the library
- * reads are listed in INTEGRATION.md (none of them changes a pixel).
+ * reads are listed in INTEGRATION.md (none of them changes a pixel).  In csrc/ the entry points
+ * live by topic: rtx_context.hip, rtx_upload.hip, rtx_frame.hip, rtx_aov.hip (the hit pass),
+ * rtx_group.cpp and rtx_anim_host.hip; the render kernel is rtx_hip.hip.
  */
 #ifndef RTX_H_
 #define RTX_H_

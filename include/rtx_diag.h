@@ -5,6 +5,8 @@
  * the exact cull, the device Update's phase stamps).  None of these has a counterpart in the
  * reference's Renderer (source/Renderer.h:17-61); the benchmark (bench.py), the tools and the tests
  * use them.  Same conventions as rtx.h: RTX_OK or a negative RTX_E_* code, nothing throws.
+ * (Implemented in csrc/rtx_diag.hip; the hit pass's timing in rtx_aov.hip, the device Update's
+ * stamps in rtx_anim_host.hip.)
  */
 #ifndef RTX_DIAG_H_
 #define RTX_DIAG_H_

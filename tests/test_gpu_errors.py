@@ -2,7 +2,7 @@
 rejected by rtx_upload_scene with RTX_E_INVALID and a reason in rtx_last_error, the context
 stays usable (the previous scene keeps rendering), and calls out of order are state errors.
 The BVH checks guard the kernel: an out-of-range child or a cycle would walk off the node
-array (rtx_hip.hip bvh_depth_check); a tree of any depth is accepted, the kernel variant
+array (rtx_upload.hip upload_scene); a tree of any depth is accepted, the kernel variant
 chosen by its depth (LDS stacks of 64 or 1,024 entries, or stacks in HBM)."""
 import ctypes as C
 

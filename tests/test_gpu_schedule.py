@@ -16,7 +16,7 @@ K_COST_BUCKETS = 32
 
 
 def cost_class(c: np.ndarray) -> np.ndarray:
-    """rtx_hip.hip cost_class: 2 classes per octave of the cycle count, heavier first."""
+    """rtx_sched.hip cost_class: 2 classes per octave of the cycle count, heavier first."""
     c = c.astype(np.uint64)
     lg = np.where(c > 0, np.floor(np.log2(np.maximum(c, 1))).astype(np.int64) + 1, 0)
     half = np.where((c > 0) & (lg >= 2), (c >> np.maximum(lg - 2, 0).astype(np.uint64)) & 1, 0).astype(np.int64)

@@ -1,7 +1,9 @@
 """Build an experiment variant of the render library into lib/exp/librtx_hip_<name>.so
-(same flags as build.py's product build, plus extra -D / compiler flags), optionally from
-another source file.  Usage: python tools/build_variant.py <name> [--src file.hip] [flags...]
+(build.py's units and flags, plus extra -D / compiler flags for every unit), optionally with
+another source file in place of the kernel unit (rtx_hip.hip).
+Usage: python tools/build_variant.py <name> [--src file.hip] [flags...]
 Select it at run time with RTX_HIP_LIB (kernel experiments only; tools/ab.sh)."""
+import importlib.util
 import subprocess
 import sys
 from pathlib import Path
@@ -11,22 +13,21 @@ PKG = ROOT / "gp1_raytracer_2223_amd"
 
 
 def main() -> int:
+    spec = importlib.util.spec_from_file_location("rtx_build", PKG / "build.py")
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
     name, args = sys.argv[1], sys.argv[2:]
-    src = PKG / "csrc" / "rtx_hip.hip"
+    srcs = list(b.HIP_SOURCES)
     if args[:1] == ["--src"]:
-        src, args = Path(args[1]).resolve(), args[2:]
+        srcs[srcs.index(b.HIP_KERNEL_UNIT)], args = Path(args[1]).resolve(), args[2:]
     out = PKG / "lib" / "exp" / f"librtx_hip_{name}.so"
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = {"-DRTX_MIN_WAVES_PER_EU=6"}
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "-ffp-contract=off",
-           "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-           "-mllvm", "-structurizecfg-skip-uniform-regions=true",
-           *([f for f in flags if not any(a.startswith(f.split("=")[0]) for a in args)]), "-fPIC", "-shared",
-           "-Wall", f"-I{ROOT / 'include'}", f"-I{PKG / 'csrc'}", *args, str(src),
-           str(PKG / "csrc" / "rtx_policy.hip"), str(PKG / "csrc" / "rtx_anim.hip"),
-           str(PKG / "csrc" / "rtx_anim_host.hip"), str(PKG / "csrc" / "rtx_group.cpp"), "-o", str(out)]
-    print(" ".join(cmd[-4:]), flush=True)
-    return subprocess.call(cmd)
+    # an extra -DNAME=... replaces the product's -DNAME=...
+    flags = [f for f in b.HIP_FLAGS if not (f.startswith("-D") and any(a.startswith(f.split("=")[0]) for a in args))]
+    try:   # (every unit again: the extra flags are not part of the objects' staleness check)
+        b.build_hip_lib(out, out.parent / f"obj_{name}", srcs, flags + args, force=True)
+    except subprocess.CalledProcessError as e:
+        return e.returncode
+    return 0
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 /* cull_records_ref.c — brute-force CPU restatement of the exact cull's records (test checker).
  *
  * The device builds each node slot's record from segment trees of the per-triangle values
- * (rtx_hip.hip: rtx_cull_tris_box, rtx_cull_tris_marg, rtx_cull_nodes).  This file computes the
+ * (rtx_cull_records.hip: rtx_cull_tris_box, rtx_cull_tris_marg, rtx_cull_nodes).  This file computes the
  * same records the direct way — for every slot, fold every triangle of its range — with the
  * same double-precision operations (rtx_cull.h), so tests/test_gpu_cull.py can require the
  * device records to equal these value for value.  Inputs are what rtx_cull_dump returns.

@@ -1,6 +1,6 @@
 """Moving-camera frame loop: the camera origin changes every frame, so the
 exact cull's camera-anchor records are rebuilt before every frame and the tile
-schedule runs in motion mode (rtx_hip.hip, kMotionFrames).  Per setting (product default,
+schedule runs in motion mode (rtx_frame.hip prepare(), kMotionFrames).  Per setting (product default,
 RTX_NO_CULL=1, and any extra NAME=VAR:value,... arguments) K frames of a scene along a fixed camera
 path, wall-clock timed, with F frames in flight (MC_INFLIGHT, default 2: frame k on context k mod F,
 which first waits for its previous frame — the bench's and the CLI's frame loop; 1 = the

@@ -1,6 +1,6 @@
 """Resource-usage table of the render kernel's instantiations, one commit against another.
 
-    hipcc <the flags of build.py's build_hip> --cuda-device-only -Rpass-analysis=kernel-resource-usage \
+    hipcc <build.py's HIP_FLAGS> --cuda-device-only -Rpass-analysis=kernel-resource-usage \
           -c gp1_raytracer_2223_amd/csrc/rtx_hip.hip -o /dev/null 2> usage.log      (once per commit)
     python tools/resource_table.py parent_usage.log this_usage.log
 

@@ -60,7 +60,7 @@ def inflight(ctxs, cam, p, frames=200):
 
 
 def share_tiles(W, H, st):
-    """wave tiles of rank 0's share (rtx_hip.hip prepare(): the grid of the largest owner)"""
+    """wave tiles of rank 0's share (rtx_frame.hip frame_shape(): the grid of the largest owner)"""
     tx, groups = (W + 7) // 8, (H + 7) // 8
     if st == 1:
         return tx * groups
