@@ -98,6 +98,10 @@ class AovPlanes(C.Structure):   # rtx_aov_planes (rtx.h): host or device planes,
                 ("material", C.POINTER(C.c_uint32)), ("primitive", C.POINTER(C.c_uint32))]
 
 
+class Ray(C.Structure):   # rtx_ray (rtx.h): dae::Ray{origin, direction, min, max}, 32 bytes
+    _fields_ = [("origin", F3), ("direction", F3), ("tmin", C.c_float), ("tmax", C.c_float)]
+
+
 XRGB8888 = (16, 8, 0, 0)
 
 
@@ -176,7 +180,9 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_anim_download", "rtx_scene_image", "rtx_anim_stamps", "rtx_cull_info", "rtx_cull_dump", "rtx_light_major_info",
                "rtx_inflight_info", "rtx_set_supersample", "rtx_group_set_supersample", "rtx_spec_info",
                "rtx_render_aov_async", "rtx_render_aov", "rtx_download_aov", "rtx_gather_aov_async",
-               "rtx_device_aov_buffers", "rtx_group_render_aov", "rtx_time_aov_frames"]
+               "rtx_device_aov_buffers", "rtx_group_render_aov", "rtx_time_aov_frames",
+               "rtx_trace_rays", "rtx_occluded", "rtx_trace_rays_device", "rtx_occluded_device",
+               "rtx_time_ray_queries"]
 
 
 def load_hip() -> C.CDLL:
@@ -302,6 +308,19 @@ def load_hip() -> C.CDLL:
             lib.rtx_time_aov_frames.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_int,
                                                 C.POINTER(C.c_float)]
             lib.rtx_time_aov_frames.restype = C.c_int
+        if hasattr(lib, "rtx_trace_rays"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            # (the device variants take integer device addresses: void pointers)
+            lib.rtx_trace_rays.argtypes = [VP, C.POINTER(Ray), C.c_uint32, C.c_uint32, C.POINTER(AovPlanes)]
+            lib.rtx_trace_rays.restype = C.c_int
+            lib.rtx_occluded.argtypes = [VP, C.POINTER(Ray), C.c_uint32, C.POINTER(C.c_uint8)]
+            lib.rtx_occluded.restype = C.c_int
+            lib.rtx_trace_rays_device.argtypes = [VP, VP, C.c_uint32, C.c_uint32, C.POINTER(AovPlanes)]
+            lib.rtx_trace_rays_device.restype = C.c_int
+            lib.rtx_occluded_device.argtypes = [VP, VP, C.c_uint32, VP]
+            lib.rtx_occluded_device.restype = C.c_int
+            lib.rtx_time_ray_queries.argtypes = [VP, VP, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(AovPlanes), VP,
+                                                 C.c_int, C.POINTER(C.c_float)]
+            lib.rtx_time_ray_queries.restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]
             lib.rtx_scene_image.restype = C.c_int

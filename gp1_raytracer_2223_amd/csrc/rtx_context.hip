@@ -156,6 +156,7 @@ extern "C" void rtx_destroy(rtx_ctx* c) {
     (void)hipFree(c->d_aov_normal);
     (void)hipFree(c->d_aov_material);
     (void)hipFree(c->d_aov_primitive);
+    (void)hipFree(c->d_query);
     (void)hipFree(c->d_counters);
     (void)hipFree(c->d_order);
     (void)hipFree(c->d_order_xcd);

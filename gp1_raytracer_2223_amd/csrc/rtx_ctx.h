@@ -259,6 +259,10 @@ struct rtx_ctx {
     rtx_render_params aov_last{};
     int aov_last_views = 1;
     uint32_t aov_last_mask = 0;   // 0: no pass yet
+    // Ray queries (rtx_trace_rays, rtx_occluded: rtx_query.hip): the host variants' staging buffer in
+    // HBM, the rays and then every result array of one call; query_cap = the rays it holds
+    char* d_query = nullptr;
+    size_t query_cap = 0;
 };
 
 namespace rtxh {

@@ -250,6 +250,19 @@ __device__ __forceinline__ float tri_t(const float4 A, const float4 B, const flo
     return fmaxf(rej, r.tmin - t);
 }
 
+// Vector3::Cross (Vector3.cpp:50-54) as it is written, UnitX * a - UnitY * b + UnitZ * c: a term that
+// is infinite or NaN reaches every component through its 0 * term.  The reduced form {a, -b, c} of
+// tri_t equals it only while a, b and c are finite (up to the sign of a zero).
+__device__ __forceinline__ void cross_ref(float ax, float ay, float az, float bx, float by, float bz, float& x,
+                                          float& y, float& z) {
+    const float a = ay * bz - az * by;
+    const float b = ax * bz - az * bx;
+    const float c = ax * by - ay * bx;
+    x = (1.f * a - 0.f * b) + 0.f * c;
+    y = (0.f * a - 1.f * b) + 0.f * c;
+    z = (0.f * a - 0.f * b) + 1.f * c;
+}
+
 // tri_t with two wave-uniform early exits for the lanes in `act` (the ones whose result is
 // used): after the cull test (Utils.h:114-127) and after the u range test (:160-163), the
 // rest is skipped when no lane in `act` can still be accepted — the same early returns as
@@ -259,15 +272,22 @@ __device__ __forceinline__ float tri_t(const float4 A, const float4 B, const flo
 // lane mask and rebuilt with v_cndmask + v_cmp per triangle.)
 // CB (kSpecCullBack): the mesh culls back faces, so cs is +1 for camera rays and -1 for shadow
 // rays (ANY) and cs * cullDot is +-cullDot exactly: a source negation instead of a multiply.
-template <bool FAST, bool CB = false, bool ANY = false>
+// XC (ray queries, rtx_query_kernel): both cross products as Vector3::Cross writes them (cross_ref),
+// for rays outside the reduced form's domain.
+template <bool FAST, bool CB = false, bool ANY = false, bool XC = false>
 __device__ __forceinline__ bool tri_t_wave(const float4 A, const float4 B, const float4 C, float cs, const Ray& r,
                                            unsigned long long act, float& rej_out, float& t) {
     const float cullDot = A.w * r.dx + B.w * r.dy + C.w * r.dz;
     float rej = fmaxf(FLT_EPSILON - fabsf(cullDot), CB ? (ANY ? -cullDot : cullDot) : cs * cullDot);
     if ((ballot(!(rej > 0.f)) & act) == 0) return false;
-    const float hx = r.dy * C.z - r.dz * C.y;
-    const float hy = -(r.dx * C.z - r.dz * C.x);
-    const float hz = r.dx * C.y - r.dy * C.x;
+    float hx, hy, hz;
+    if constexpr (XC) {
+        cross_ref(r.dx, r.dy, r.dz, C.x, C.y, C.z, hx, hy, hz);
+    } else {
+        hx = r.dy * C.z - r.dz * C.y;
+        hy = -(r.dx * C.z - r.dz * C.x);
+        hz = r.dx * C.y - r.dy * C.x;
+    }
     const float a = B.x * hx + B.y * hy + B.z * hz;
     rej = fmaxf(rej, FLT_EPSILON - fabsf(a));
     float ai = rcp_rn(a);
@@ -276,9 +296,14 @@ __device__ __forceinline__ bool tri_t_wave(const float4 A, const float4 B, const
     const float u = ai * (sx * hx + sy * hy + sz * hz);
     rej = fmaxf(rej, fmaxf(-u, u - 1.f));
     if ((ballot(!(rej > 0.f)) & act) == 0) return false;
-    const float qx = sy * B.z - sz * B.y;
-    const float qy = -(sx * B.z - sz * B.x);
-    const float qz = sx * B.y - sy * B.x;
+    float qx, qy, qz;
+    if constexpr (XC) {
+        cross_ref(sx, sy, sz, B.x, B.y, B.z, qx, qy, qz);
+    } else {
+        qx = sy * B.z - sz * B.y;
+        qy = -(sx * B.z - sz * B.x);
+        qz = sx * B.y - sy * B.x;
+    }
     const float v = ai * (r.dx * qx + r.dy * qy + r.dz * qz);
     rej = fmaxf(rej, fmaxf(-v, (u + v) - 1.f));
     t = ai * (C.x * qx + C.y * qy + C.z * qz);
@@ -542,7 +567,9 @@ constexpr int kPlaneCache = 8;   // planes whose shadow-ray numerators are kept 
 // COUNT (the counting variant of the culled walk, rtx_count_work_culled): per lane, the slab,
 // exact-cull and triangle tests this walk executes for the lane (a lane in the node's mask is
 // tested against both children), in `cp` — the executed work beside the reference's (bvh_walk).
-template <bool ANY, int SLAB, bool CB = false, bool CULL = false, bool COUNT = false>
+// XC (ray queries): the triangle test outside its fast domains — Vector3::Cross as written
+// (cross_ref) and the |a| > 2^60 check of tri_t<false> — whatever the slab form.
+template <bool ANY, int SLAB, bool CB = false, bool CULL = false, bool COUNT = false, bool XC = false>
 __device__ void bvh_walk_lean(const DevScene& S, const float4* nb, float cs, const Ray& r, uint32_t link,
                               uint32_t ntri, unsigned long long m, unsigned long long mask, uint32_t lane, uint4* stk,
                               float& sc_t, uint32_t& sc_tri, unsigned long long& live, const uint32_t* occ_word,
@@ -630,7 +657,7 @@ __device__ void bvh_walk_lean(const DevScene& S, const float4* nb, float cs, con
                 }
                 float t;
                 float rej;
-                if (!tri_t_wave<FAST, CB, ANY>(T.a, T.b, T.c, cs, r, ANY ? (m & live) : m, rej, t)) continue;
+                if (!tri_t_wave<FAST && !XC, CB, ANY, XC>(T.a, T.b, T.c, cs, r, ANY ? (m & live) : m, rej, t)) continue;
                 if (ANY) {
                     live &= ~(ballot(!(rej > 0.f)) & ballot(!(t >= r.tmax)) & m);
                 } else {
@@ -664,11 +691,13 @@ __device__ void bvh_walk_lean(const DevScene& S, const float4* nb, float cs, con
 // SLAB = kSlabOct: `oct` is the batch's octant (batch_octant), else ignored.
 // CULL (SLAB != kSlabExact, !COUNT): the exact cull of the anchor `cq` (cull_mask) beside every
 // slab test, the root's included.
-template <bool ANY, int SLAB, bool COUNT, bool CB = false, bool CULL = false>
+// XC: bvh_walk_lean's (ray queries; never with COUNT).
+template <bool ANY, int SLAB, bool COUNT, bool CB = false, bool CULL = false, bool XC = false>
 __device__ void mesh_traverse(const DevScene& S, const int4 M, const Ray& r, int oct, unsigned long long mask,
                               uint32_t lane, uint4* stk, unsigned long long* sT, float& sc_t, uint32_t& sc_tri,
                               unsigned long long& live, Counts& cnt, const CullRay& cq = CullRay{}) {
     static_assert(!CULL || SLAB != kSlabExact, "the cull runs in FAST batches of the lean walk only");
+    static_assert(!XC || (!COUNT && !RTX_STAMPS_WALK), "the reference's cross products are the lean walk's only");
     constexpr bool FAST = SLAB != kSlabExact;
     if (M.y == 0) return;
     const bool OCT = SLAB == kSlabOct && !COUNT && !RTX_STAMPS_WALK;
@@ -692,7 +721,7 @@ __device__ void mesh_traverse(const DevScene& S, const int4 M, const Ray& r, int
     }
     if (m == 0) return;
     if ((!COUNT || CULL) && !RTX_STAMPS_WALK)
-        bvh_walk_lean<ANY, OCT ? kSlabOct : (FAST ? kSlabFast : kSlabExact), CB, CULL, COUNT>(
+        bvh_walk_lean<ANY, OCT ? kSlabOct : (FAST ? kSlabFast : kSlabExact), CB, CULL, COUNT, XC>(
             S, nb, cull_sign(M.z, ANY), r, __float_as_uint(b1.z), __float_as_uint(b1.w), m, mask, lane, stk, sc_t,
             sc_tri, live, nullptr, 0u, cq, &cnt);
     else
@@ -1554,6 +1583,202 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
 #undef n_pl
 #undef n_mesh
 
+// ====================================================================== ray queries
+// Scene::GetClosestHit (ANY = false) and Scene::DoesHit (ANY = true) on caller-supplied rays
+// (rtx_trace_rays*, rtx_occluded*, rtx.h): rays 64w .. 64w + 63 are wave w, ray i lane i & 63, tail
+// lanes inactive; one wave is one workgroup.  Closest hit is the hit pass (PHASE 7 of render_tile) with
+// the ray read from memory and a linear output index; occlusion is the light loop's any-hit body on
+// the lane's own ray.  Both share every test and walk with the render kernel (sphere_perp / sphere_t,
+// plane_num / plane_den, mesh_traverse and below) and restate only the loops around them: with those
+// loops as helpers called from both, 94 of the render kernel's instantiations compiled to other code
+// (tools/codeobj_diff.py), and as it is they are the parent's instruction for instruction.
+// DEEP / HSTK: the DFS stacks, as there.
+// No exact cull: its records are anchored at a camera or a light, and a caller's ray has no anchor.
+//
+// A caller's ray is any eight floats, and the result is the reference's for them, so every shortcut
+// on the path that is proved for the renderer's own rays is taken per wave, when all ACTIVE lanes are
+// inside its domain, and the exact form otherwise:
+//   * rcp3_exact's domain (each |d_k| in [2^-60, 2^60]): make_ray's `slow`.  A slow lane has a zero,
+//     infinite or NaN inverse component, and v_min / v_max then drop a NaN that std::min / std::max
+//     keep: the wave takes kSlabExact.
+//   * a NaN origin makes the same NaN slab values with a finite inverse: non-finite origins count as
+//     slow.  (An infinite one gives infinite slab values of either form; it is excluded with them.)
+//   * tri_t<FAST> skips the |a| > 2^60 check for |d| < 2 and |e1||e2| <= 2^56 (DevScene::tri_fast), and
+//     its reduced cross products equal Vector3::Cross's only while their terms are finite: taken when
+//     every active lane is not slow and has |d_k| <= 1 (so |d| <= sqrt 3) and |o_k| <= 2^40, and the scene
+//     is tri_fast; otherwise XC, Vector3::Cross as written plus the check.
+//   * the octant node copies: a wave that is fast in all of the above, S.oct_bytes, batch_octant >= 0.
+//   * plane_cand (any-hit) skips the division for lanes that cannot pass t >= tmin given tmin > 0, and
+//     its "beyond" test is stated for a finite tmax: taken when every active lane has tmin > 0 and
+//     |tmax| < inf (NaN fails); otherwise t = num / den is computed and tested as HitTest_Plane does
+//     (with tmin <= 0 a zero or negative t is a hit).  Closest hit always divides, as PHASE 7 does
+//     outside the room.
+//   * the room's a / d planes, the host's camera numerators and the LDS numerator cache belong to the
+//     renderer's rays and are not used; neither are the cull (|d| = 1 +- 3u) nor the atomicMin key.
+//   * sphere_perp / sphere_t, plane_num / plane_den, the hit record's rebuild and div3_exact restate the
+//     reference for any operand.
+struct QRay {
+    float v[8];
+};
+template <bool ANY, bool DEEP, bool HSTK>
+__global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_WAVES_PER_EU)
+    rtx_query_kernel(const DevScene S, const QueryArgs Q) {
+    constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
+    __shared__ uint4 stkE[kBlockThreads / 64][kDepth];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t widx = blockIdx.x * kWavesPerBlock + wave;
+    if (widx * 64u >= Q.n) return;
+    uint4* stk = stkE[wave];
+    if constexpr (HSTK) stk = S.hstk + static_cast<size_t>(widx) * S.hstk_depth;
+    const uint32_t i = widx * 64u + lane;
+    const bool valid = i < Q.n;
+    // the lane's ray: 32 bytes with vector loads (a tail lane keeps a harmless one; it is in no mask)
+    QRay q = {{0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 0.f}};
+    if (valid) q = *reinterpret_cast<const QRay*>(Q.rays + static_cast<size_t>(i) * 8u);
+    unsigned long long slow;
+    const Ray r = make_ray(q.v[0], q.v[1], q.v[2], q.v[3], q.v[4], q.v[5], q.v[6], q.v[7], slow);
+    const unsigned long long active = ballot(valid);
+    slow |= ballot(!finite3(r.ox, r.oy, r.oz));
+    const bool slab_fast = (active & slow) == 0;
+    const bool tri_dom = fmaxf(fmaxf(fabsf(r.dx), fabsf(r.dy)), fabsf(r.dz)) <= 1.f &&
+                         fmaxf(fmaxf(fabsf(r.ox), fabsf(r.oy)), fabsf(r.oz)) <= 0x1p40f;
+    // (v_max drops a NaN component, and a lane with one is slow already)
+    const bool fast = slab_fast && S.tri_fast && (active & ~ballot(tri_dom)) == 0;
+    const int oct = (fast && S.oct_bytes) ? batch_octant(r, active) : -1;
+    Counts cnt;   // (never counted: the walks' COUNT is off)
+
+    if constexpr (ANY) {
+        // ---- Scene::DoesHit (Scene.cpp:68-96); `live` = lanes still without an occluder
+        unsigned long long live = active;
+        for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
+            const float4 s = ldcb16(S.spheres, opaque(k));
+            const SphereProj p = sphere_perp(s, r);
+            const unsigned long long near = ballot(!(s.w < p.perp)) & live;
+            if (!near) continue;
+            const float t = sphere_t(s, p);
+            live &= ~(near & ballot(!(t < r.tmin)) & ballot(!(t > r.tmax)));
+        }
+        const bool pl_dom = (active & ~ballot(r.tmin > 0.f && fabsf(r.tmax) < INFINITY)) == 0;
+        if (pl_dom) {
+            for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+                float4 p0, p1;
+                ldcb32(S.planes, opaque(k), p0, p1);
+                const float num = plane_num(p0, p1, r), den = plane_den(p1, r);
+                const unsigned long long cand = plane_cand(num, den, r.tmax) & live;
+                if (!cand) continue;   // also taken once no lane is live
+                const float t = num / den;
+                live &= ~(ballot(t >= r.tmin) & ballot(t < r.tmax) & cand);
+            }
+        } else {
+            for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+                float4 p0, p1;
+                ldcb32(S.planes, opaque(k), p0, p1);
+                const float t = plane_num(p0, p1, r) / plane_den(p1, r);
+                live &= ~(ballot(t >= r.tmin) & ballot(t < r.tmax));
+            }
+        }
+        for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
+            if (!live) break;
+            float st = 0.f;
+            uint32_t stri = 0;
+            const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
+            if (oct >= 0)
+                mesh_traverse<true, kSlabOct, false>(S, M, r, oct, live, lane, stk, nullptr, st, stri, live, cnt);
+            else if (fast)
+                mesh_traverse<true, kSlabFast, false>(S, M, r, 0, live, lane, stk, nullptr, st, stri, live, cnt);
+            else if (slab_fast)
+                mesh_traverse<true, kSlabFast, false, false, false, true>(S, M, r, 0, live, lane, stk, nullptr, st,
+                                                                          stri, live, cnt);
+            else
+                mesh_traverse<true, kSlabExact, false, false, false, true>(S, M, r, 0, live, lane, stk, nullptr, st,
+                                                                           stri, live, cnt);
+        }
+        if (valid) Q.occ[i] = static_cast<uint8_t>(((live >> lane) & 1ull) ? 0u : 1u);
+        return;
+    } else {
+        // ---- Scene::GetClosestHit (Scene.cpp:29-66), as PHASE 7 of render_tile
+        float best_t = FLT_MAX, sc_t = FLT_MAX;
+        uint32_t best_kind = 0, best_idx = 0;   // kind: 0 none, 1 sphere, 2 plane, 3 triangle; idx: BYTE offset
+        for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
+            const float4 s = ldcb16(S.spheres, opaque(k));
+            const SphereProj p = sphere_perp(s, r);
+            const unsigned long long near = ballot(!(s.w < p.perp)) & active;
+            if (!near) continue;
+            const float t = sphere_t(s, p);
+            const bool h = ((near >> lane) & 1ull) & !(t < r.tmin) & !(t > r.tmax);
+            sc_t = h ? t : sc_t;
+            const bool b = h & (t < best_t);
+            best_t = b ? t : best_t;
+            best_kind = b ? 1u : best_kind;
+            best_idx = b ? k : best_idx;
+        }
+        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+            float4 p0, p1;
+            ldcb32(S.planes, opaque(k), p0, p1);
+            const float t = plane_num(p0, p1, r) / plane_den(p1, r);
+            const bool h = valid & (t >= r.tmin) & (t < r.tmax);
+            sc_t = h ? t : sc_t;
+            const bool b = h & (t < best_t);
+            best_t = b ? t : best_t;
+            best_kind = b ? 2u : best_kind;
+            best_idx = b ? k : best_idx;
+        }
+        for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
+            const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
+            uint32_t sc_tri = 0;
+            unsigned long long unused = 0;
+            if (oct >= 0)
+                mesh_traverse<false, kSlabOct, false>(S, M, r, oct, active, lane, stk, nullptr, sc_t, sc_tri, unused,
+                                                      cnt);
+            else if (fast)
+                mesh_traverse<false, kSlabFast, false>(S, M, r, 0, active, lane, stk, nullptr, sc_t, sc_tri, unused,
+                                                       cnt);
+            else if (slab_fast)
+                mesh_traverse<false, kSlabFast, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr,
+                                                                           sc_t, sc_tri, unused, cnt);
+            else
+                mesh_traverse<false, kSlabExact, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr,
+                                                                            sc_t, sc_tri, unused, cnt);
+            if (sc_t < best_t) { best_t = sc_t; best_kind = 3; best_idx = sc_tri; }
+        }
+        // ---- hit record (rebuilt from t: ray.origin + t * ray.direction, Utils.h:62-64)
+        const bool did = best_kind != 0;
+        float nx = 0.f, ny = 0.f, nz = 0.f;
+        uint32_t mat = 0;
+        if (did) {
+            if (best_kind == 1) {
+                const float hx = r.ox + r.dx * best_t, hy = r.oy + r.dy * best_t, hz = r.oz + r.dz * best_t;
+                const float4 s = ldcb16(S.spheres, best_idx);
+                nx = hx - s.x; ny = hy - s.y; nz = hz - s.z;
+                const float m = sqrtf(nx * nx + ny * ny + nz * nz);   // closestHit.normal.Normalize()
+                div3_exact(nx, ny, nz, m);
+                mat = ldc(S.sphere_mat, best_idx >> 4);
+            } else if (best_kind == 2) {
+                float4 p0, p1;
+                ldcb32(S.planes, best_idx, p0, p1);
+                nx = p1.x; ny = p1.y; nz = p1.z;
+                mat = __float_as_uint(p0.w);
+            } else {
+                Tri T;
+                ldcb64(S.tris, best_idx, T.a, T.b, T.c, T.d);
+                nx = T.a.w; ny = T.b.w; nz = T.c.w;
+                mat = __float_as_uint(T.d.x);
+            }
+        }
+        if (valid) {
+            const size_t o = i;
+            const uint32_t m = uni(Q.mask);
+            if (m & RTX_AOV_DEPTH) Q.depth[o] = best_t;   // (a miss: the empty HitRecord's FLT_MAX)
+            if (m & RTX_AOV_NORMAL) {
+                Q.normal[3 * o] = nx; Q.normal[3 * o + 1] = ny; Q.normal[3 * o + 2] = nz;
+            }
+            if (m & RTX_AOV_MATERIAL) Q.material[o] = mat;
+            // best_idx is the record's byte offset: 16 B per sphere, 32 per plane, 64 per triangle
+            if (m & RTX_AOV_PRIMITIVE) Q.primitive[o] = did ? (best_kind << 30) | (best_idx >> (best_kind + 3u)) : 0u;
+        }
+    }
+}
+
 // ====================================================================== launches
 namespace {
 
@@ -1638,6 +1863,18 @@ void launch_hit_pass(bool deep, bool hstk, bool cull, dim3 grid, hipStream_t s, 
     case 0: hipLaunchKernelGGL((rtx_render_kernel<false, 7>), grid, dim3(kBlockThreads), 0, s, d, F); break;
     default: no_instantiation("this hit pass");
     }
+}
+
+template <bool ANY>
+static void launch_query_t(bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene& d, const QueryArgs& Q) {
+    if (hstk) hipLaunchKernelGGL((rtx_query_kernel<ANY, true, true>), grid, dim3(kBlockThreads), 0, s, d, Q);
+    else if (deep) hipLaunchKernelGGL((rtx_query_kernel<ANY, true, false>), grid, dim3(kBlockThreads), 0, s, d, Q);
+    else hipLaunchKernelGGL((rtx_query_kernel<ANY, false, false>), grid, dim3(kBlockThreads), 0, s, d, Q);
+}
+
+void launch_query(bool any, bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene& d, const QueryArgs& Q) {
+    if (any) launch_query_t<true>(deep, hstk, grid, s, d, Q);
+    else launch_query_t<false>(deep, hstk, grid, s, d, Q);
 }
 
 }  // namespace rtxh

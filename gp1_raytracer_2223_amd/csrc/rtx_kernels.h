@@ -1,6 +1,6 @@
 // rtx_kernels.h — device layout of the uploaded scene and the per-frame launch record.
 // Shared by the kernels (rtx_hip.hip, rtx_cull_records.hip, rtx_sched.hip) and the host units
-// that fill them in (rtx_upload.hip, rtx_frame.hip, rtx_aov.hip).
+// that fill them in (rtx_upload.hip, rtx_frame.hip, rtx_aov.hip, rtx_query.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -268,6 +268,23 @@ struct FrameArgs {
     float* __restrict__ aov_normal;
     uint32_t* __restrict__ aov_material;
     uint32_t* __restrict__ aov_primitive;
+};
+
+// Ray queries (rtx_trace_rays*, rtx_occluded*): one launch of rtx_query_kernel over `n`
+// caller-supplied rays (rtx_ray: 8 floats each), ray i = lane i & 63 of wave i / 64.  Closest hit writes
+// element i of the planes `mask` names (a plane outside the mask is never touched, its pointer may be
+// null); occlusion writes byte i of `occ`.
+constexpr uint32_t kQueryChunkRays = 1u << 24;   // rays per launch (the ray index stays far below 2^32)
+constexpr size_t kQueryStackBytes = size_t(256) << 20;   // HBM stacks a query launch may ask for (HSTK)
+struct QueryArgs {
+    const float* __restrict__ rays;
+    uint32_t n;
+    uint32_t mask;
+    float* __restrict__ depth;
+    float* __restrict__ normal;
+    uint32_t* __restrict__ material;
+    uint32_t* __restrict__ primitive;
+    uint8_t* __restrict__ occ;
 };
 
 // Light-major frames (opt-in: RTX_LIGHT_MAJOR=1 always, =auto while a launch has at most kLmSlotsPercent /

@@ -1,0 +1,184 @@
+// rtx_query.hip — ray queries behind the C-ABI: rtx_trace_rays*, rtx_occluded* (rtx_query_kernel,
+// rtx_hip.hip): their checks, the host variants' staging buffer and the launches.
+#include <algorithm>
+
+#include "rtx_ctx.h"
+#include "rtx_launch.h"
+
+using namespace rtxh;
+
+namespace {
+
+// the staging buffer's sections for `cap` rays: the rays, the four planes, the occlusion bytes
+constexpr size_t kOffDepth = 32, kOffNormal = 36, kOffMaterial = 48, kOffPrimitive = 52, kOffOcc = 56, kPerRay = 57;
+
+int query_check(rtx_ctx* c, const void* rays, uint32_t n, const void* out) {
+    if (!c) return RTX_E_INVALID;
+    if (n > 0 && (!rays || !out)) return fail(c, RTX_E_INVALID, "a ray query needs rays and an output");
+    return RTX_OK;
+}
+
+int mask_check(rtx_ctx* c, uint32_t mask, const rtx_aov_planes* out) {
+    if (mask == 0 || (mask & ~static_cast<uint32_t>(RTX_AOV_ALL)))
+        return fail(c, RTX_E_INVALID, "a ray query's mask must be a non-empty set of RTX_AOV_* bits (got " +
+                                          std::to_string(mask) + ")");
+    if (!out) return RTX_OK;   // (n == 0)
+    const uint32_t given = (out->depth ? RTX_AOV_DEPTH : 0u) | (out->normal ? RTX_AOV_NORMAL : 0u) |
+                           (out->material ? RTX_AOV_MATERIAL : 0u) | (out->primitive ? RTX_AOV_PRIMITIVE : 0u);
+    if (given & ~mask)
+        return fail(c, RTX_E_INVALID, "a ray query's planes (mask " + std::to_string(given) +
+                                          ") must be planes of its mask (" + std::to_string(mask) + ")");
+    return RTX_OK;
+}
+
+// Queue the launches of one query on the context stream, behind the last frame's split chain like the
+// hit pass; nothing of the frames' state is read or written.  A large n is cut into launches of at most
+// kQueryChunkRays rays, and with HBM stacks into launches whose stacks stay below kQueryStackBytes.
+int query_launch(rtx_ctx* c, bool any, QueryArgs Q) {
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    uint32_t chunk = kQueryChunkRays;
+    if (c->hbm_stack) {
+        const size_t per_wave = (static_cast<size_t>(c->max_depth) + 1u) * (sizeof(uint4) + sizeof(unsigned long long));
+        const size_t waves = std::max<size_t>(kQueryStackBytes / per_wave, static_cast<size_t>(kWavesPerBlock));
+        chunk = static_cast<uint32_t>(std::min<size_t>(chunk, waves / kWavesPerBlock * kWavesPerBlock * 64u));
+    }
+    const uint32_t total = Q.n;
+    for (uint32_t first = 0; first < total; first += chunk) {
+        const uint32_t n = std::min(chunk, total - first);
+        const uint32_t waves = (n + 63u) / 64u;
+        const dim3 grid((waves + kWavesPerBlock - 1u) / kWavesPerBlock);
+        if (c->hbm_stack) {
+            if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
+        }
+        Q.n = n;
+        launch_query(any, c->deep_stack || c->hbm_stack, c->hbm_stack, grid, c->stream, c->dev, Q);
+        HIP_TRY(c, hipGetLastError());
+        Q.rays += static_cast<size_t>(n) * 8u;
+        if (Q.depth) Q.depth += n;
+        if (Q.normal) Q.normal += static_cast<size_t>(n) * 3u;
+        if (Q.material) Q.material += n;
+        if (Q.primitive) Q.primitive += n;
+        if (Q.occ) Q.occ += n;
+    }
+    return RTX_OK;
+}
+
+QueryArgs trace_args(const rtx_ray* d_rays, uint32_t n, uint32_t mask, const rtx_aov_planes& d) {
+    QueryArgs Q{};
+    Q.rays = reinterpret_cast<const float*>(d_rays);
+    Q.n = n;
+    Q.mask = mask;
+    Q.depth = d.depth;
+    Q.normal = d.normal;
+    Q.material = d.material;
+    Q.primitive = d.primitive;
+    return Q;
+}
+
+// The staging buffer for n rays (grown on demand: the queries queued so far are waited for first).
+int stage(rtx_ctx* c, const rtx_ray* rays, uint32_t n) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n > c->query_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const size_t cap = (static_cast<size_t>(n) + 63u) / 64u * 64u;
+        if (const int rc = device_grow(c, c->d_query, c->query_cap, cap, kPerRay); rc != RTX_OK) return rc;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_query, rays, static_cast<size_t>(n) * sizeof(rtx_ray), hipMemcpyHostToDevice,
+                              c->stream));
+    return RTX_OK;
+}
+
+}  // namespace
+
+extern "C" int rtx_trace_rays_device(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n, uint32_t mask,
+                                     const rtx_aov_planes* d_out) {
+    if (const int rc = query_check(c, d_rays, n, d_out); rc != RTX_OK) return rc;
+    if (const int rc = mask_check(c, mask, d_out); rc != RTX_OK) return rc;
+    if (n == 0) return RTX_OK;
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    // (a plane of the mask the caller left NULL is not asked for)
+    const uint32_t given = (d_out->depth ? RTX_AOV_DEPTH : 0u) | (d_out->normal ? RTX_AOV_NORMAL : 0u) |
+                           (d_out->material ? RTX_AOV_MATERIAL : 0u) | (d_out->primitive ? RTX_AOV_PRIMITIVE : 0u);
+    if (given == 0) return RTX_OK;
+    return query_launch(c, false, trace_args(d_rays, n, given, *d_out));
+}
+
+extern "C" int rtx_occluded_device(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n, uint8_t* d_out) {
+    if (const int rc = query_check(c, d_rays, n, d_out); rc != RTX_OK) return rc;
+    if (n == 0) return RTX_OK;
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    QueryArgs Q{};
+    Q.rays = reinterpret_cast<const float*>(d_rays);
+    Q.n = n;
+    Q.occ = d_out;
+    return query_launch(c, true, Q);
+}
+
+extern "C" int rtx_time_ray_queries(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n, int what, uint32_t mask,
+                                    const rtx_aov_planes* d_out, uint8_t* d_occ, int iters, float* mean_ms) {
+    if (!c || !d_rays || !mean_ms || iters <= 0 || n == 0 || what < 0 || what > 2) return RTX_E_INVALID;
+    if (what == 2) {   // the staging buffer's ray section as the copy's target
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (n > c->query_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            const size_t cap = (static_cast<size_t>(n) + 63u) / 64u * 64u;
+            if (const int rc = device_grow(c, c->d_query, c->query_cap, cap, kPerRay); rc != RTX_OK) return rc;
+        }
+    }
+    const auto once = [&]() -> int {
+        if (what == 0) return rtx_trace_rays_device(c, d_rays, n, mask, d_out);
+        if (what == 1) return rtx_occluded_device(c, d_rays, n, d_occ);
+        HIP_TRY(c, hipMemcpyAsync(c->d_query, d_rays, static_cast<size_t>(n) * sizeof(rtx_ray), hipMemcpyDeviceToDevice,
+                                  c->stream));
+        return RTX_OK;
+    };
+    if (const int rc = once(); rc != RTX_OK) return rc;   // (checks, a pending chain's join: outside the timing)
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i)
+        if (const int rc = once(); rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
+    return RTX_OK;
+}
+
+extern "C" int rtx_trace_rays(rtx_ctx* c, const rtx_ray* rays, uint32_t n, uint32_t mask, const rtx_aov_planes* out) {
+    if (const int rc = query_check(c, rays, n, out); rc != RTX_OK) return rc;
+    if (const int rc = mask_check(c, mask, out); rc != RTX_OK) return rc;
+    if (n == 0) return RTX_OK;
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    if (const int rc = stage(c, rays, n); rc != RTX_OK) return rc;
+    const size_t cap = c->query_cap;
+    rtx_aov_planes d{};
+    if (out->depth) d.depth = reinterpret_cast<float*>(c->d_query + kOffDepth * cap);
+    if (out->normal) d.normal = reinterpret_cast<float*>(c->d_query + kOffNormal * cap);
+    if (out->material) d.material = reinterpret_cast<uint32_t*>(c->d_query + kOffMaterial * cap);
+    if (out->primitive) d.primitive = reinterpret_cast<uint32_t*>(c->d_query + kOffPrimitive * cap);
+    if (const int rc = rtx_trace_rays_device(c, reinterpret_cast<const rtx_ray*>(c->d_query), n, mask, &d); rc != RTX_OK)
+        return rc;
+    const size_t N = n;
+    if (out->depth) HIP_TRY(c, hipMemcpyAsync(out->depth, d.depth, N * 4u, hipMemcpyDeviceToHost, c->stream));
+    if (out->normal) HIP_TRY(c, hipMemcpyAsync(out->normal, d.normal, N * 12u, hipMemcpyDeviceToHost, c->stream));
+    if (out->material) HIP_TRY(c, hipMemcpyAsync(out->material, d.material, N * 4u, hipMemcpyDeviceToHost, c->stream));
+    if (out->primitive)
+        HIP_TRY(c, hipMemcpyAsync(out->primitive, d.primitive, N * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+extern "C" int rtx_occluded(rtx_ctx* c, const rtx_ray* rays, uint32_t n, uint8_t* out) {
+    if (const int rc = query_check(c, rays, n, out); rc != RTX_OK) return rc;
+    if (n == 0) return RTX_OK;
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    if (const int rc = stage(c, rays, n); rc != RTX_OK) return rc;
+    uint8_t* d_occ = reinterpret_cast<uint8_t*>(c->d_query + kOffOcc * c->query_cap);
+    if (const int rc = rtx_occluded_device(c, reinterpret_cast<const rtx_ray*>(c->d_query), n, d_occ); rc != RTX_OK)
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, d_occ, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}

@@ -146,6 +146,52 @@ class DeviceContext:
         abi.check(self.lib.rtx_device_aov_buffers(self.h, C.byref(out)), "rtx_device_aov_buffers", self.h)
         return {k: C.cast(getattr(out, k), C.c_void_p).value or 0 for k in AOV_PLANES}
 
+    @staticmethod
+    def _rays(rays) -> np.ndarray:
+        """(n, 8) float32 rows {origin, direction, tmin, tmax} (rtx_ray), C-contiguous."""
+        a = np.ascontiguousarray(rays, np.float32)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError(f"rays must be (n, 8) float32 rows of origin, direction, tmin, tmax; got {a.shape}")
+        return a
+
+    def trace_rays(self, rays, mask: int = AOV_ALL) -> dict:
+        """Scene::GetClosestHit on caller-supplied rays (rtx_trace_rays), blocking: the planes of `mask`,
+        keyed as render_aov's, element i = ray i's record.  Nothing about a ray is interpreted: the
+        direction is not normalised and nothing is validated (include/rtx.h)."""
+        a = self._rays(rays)
+        n = a.shape[0]
+        planes = {k: np.zeros(e * n, dt) for k, (bit, dt, e) in AOV_PLANES.items() if mask & bit}
+        out = aov_struct(planes)
+        abi.check(self.lib.rtx_trace_rays(self.h, a.ctypes.data_as(C.POINTER(abi.Ray)), n, int(mask), C.byref(out)),
+                  "rtx_trace_rays", self.h)
+        return planes
+
+    def occluded(self, rays) -> np.ndarray:
+        """Scene::DoesHit on caller-supplied rays (rtx_occluded), blocking: uint8[n], 1 = something lies
+        in the ray's [tmin, tmax]."""
+        a = self._rays(rays)
+        n = a.shape[0]
+        out = np.zeros(n, np.uint8)
+        abi.check(self.lib.rtx_occluded(self.h, a.ctypes.data_as(C.POINTER(abi.Ray)), n,
+                                        out.ctypes.data_as(C.POINTER(C.c_uint8))), "rtx_occluded", self.h)
+        return out
+
+    def trace_rays_device(self, d_rays: int, n: int, mask: int, d_planes: dict) -> None:
+        """rtx_trace_rays_device: `d_rays` and the values of `d_planes` (plane name -> address, a missing
+        name or 0 = not asked for) are device addresses; queued, complete after synchronize()."""
+        out = abi.AovPlanes()
+        for k, (_, dt, _) in AOV_PLANES.items():
+            if d_planes.get(k):
+                setattr(out, k, C.cast(C.c_void_p(int(d_planes[k])),
+                                       C.POINTER(C.c_float if dt == np.float32 else C.c_uint32)))
+        abi.check(self.lib.rtx_trace_rays_device(self.h, C.c_void_p(int(d_rays)), int(n), int(mask), C.byref(out)),
+                  "rtx_trace_rays_device", self.h)
+
+    def occluded_device(self, d_rays: int, n: int, d_out: int) -> None:
+        """rtx_occluded_device: device addresses; queued, complete after synchronize()."""
+        abi.check(self.lib.rtx_occluded_device(self.h, C.c_void_p(int(d_rays)), int(n), C.c_void_p(int(d_out))),
+                  "rtx_occluded_device", self.h)
+
     def time_aov_frames(self, cam, params, mask: int, iters: int) -> float:
         ms = C.c_float()
         abi.check(self.lib.rtx_time_aov_frames(self.h, C.byref(cam), C.byref(params), int(mask), int(iters),
@@ -384,6 +430,17 @@ class Renderer:
         the planes of `mask` as flat numpy arrays; rows this renderer's stripes do not own stay 0."""
         _, cam = self._view(scene, upload)
         return self.ctx.render_aov(cam, self.params(), mask)
+
+    def TraceRays(self, scene: HostScene, rays, mask: int = AOV_ALL, upload: bool = True) -> dict:
+        """Scene::GetClosestHit on the caller's (n, 8) rays against `scene` (same upload bookkeeping as
+        Render): the planes of `mask`, element i = ray i's record."""
+        self._view(scene, upload)
+        return self.ctx.trace_rays(rays, mask)
+
+    def Occluded(self, scene: HostScene, rays, upload: bool = True) -> np.ndarray:
+        """Scene::DoesHit on the caller's (n, 8) rays against `scene`: uint8[n]."""
+        self._view(scene, upload)
+        return self.ctx.occluded(rays)
 
     def Render(self, scene: HostScene, upload: bool = True, want_rgb: bool = False) -> np.ndarray:
         """Renderer::Render (Renderer.cpp:34-98): blocking; fills self.buffer."""

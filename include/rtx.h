@@ -30,7 +30,7 @@
  * and the scheduler's / exact cull's internals are in rtx_diag.h; the environment knobs the library
  * reads are listed in INTEGRATION.md (none of them changes a pixel).  In csrc/ the entry points
  * live by topic: rtx_context.hip, rtx_upload.hip, rtx_frame.hip, rtx_aov.hip (the hit pass),
- * rtx_group.cpp and rtx_anim_host.hip; the render kernel is rtx_hip.hip.
+ * rtx_query.hip (ray queries), rtx_group.cpp and rtx_anim_host.hip; the render kernel is rtx_hip.hip.
  */
 #ifndef RTX_H_
 #define RTX_H_
@@ -288,6 +288,44 @@ int rtx_gather_aov_async(rtx_ctx* ctx, const rtx_aov_planes* out);
 /* Device pointers of the HBM planes (NULL for a plane no mask has named yet); the passes queued so
  * far are complete in them after rtx_synchronize. */
 int rtx_device_aov_buffers(rtx_ctx* ctx, rtx_aov_planes* out);
+
+/* ---- ray queries: closest hit and occlusion for caller-supplied rays ---------------
+ * The traversal behind a frame's rays, for rays the caller makes: a line-of-sight test, a pick ray,
+ * visibility from surface points, a bounce, a custom camera.
+ *
+ * A ray is eight floats and nothing about it is interpreted.  The library builds the reference's
+ * dae::Ray{origin, direction, min, max} (DataTypes.h:539-565) from them as its constructor does,
+ * inversedDir = 1 / direction per component, and runs the reference's function on it.  It does not
+ * normalise the direction (t is in units of its length) and validates nothing: the result for a zero,
+ * denormal, huge, infinite or NaN component, for tmin <= 0, for tmax < tmin and for a tmax of FLT_MAX
+ * or inf is whatever the reference computes for that ray.  The tolerance is zero: every output word
+ * is the reference's, except that a NaN float may be any NaN.
+ *
+ * Errors (the context keeps working after each): NULL ctx, or NULL rays / out with n > 0, mask 0 or
+ * with unknown bits, or a non-NULL plane of `out` that `mask` does not name: RTX_E_INVALID; no scene
+ * uploaded: RTX_E_STATE.  n == 0 returns RTX_OK and launches nothing.
+ *
+ * A query is queued on the context stream behind a pending split chain, like the hit pass, and is
+ * ordered with the frames, passes, uploads and device Updates queued on the context before and after
+ * it: a query after rtx_upload_scene or rtx_anim_update sees the new geometry.  It reads and writes
+ * nothing of the colour frame buffer, the hit-pass planes and their last-pass record, or the frame
+ * schedule; a supersample factor on the context does not matter (queries are not frames).  Rays are
+ * dispatched in the caller's order, 64 consecutive rays to a wave: coherent neighbours are faster,
+ * and the library neither sorts nor compacts them. */
+typedef struct rtx_ray { float origin[3]; float direction[3]; float tmin, tmax; } rtx_ray;   /* 32 B */
+/* Scene::GetClosestHit (Scene.cpp:29-66) on each ray: element i of every plane of `mask` (3 floats for
+ * the normal) is ray i's record in the hit pass's terms (rtx_aov_planes above: depth = t or FLT_MAX,
+ * normal, material, primitive = kind << 30 | index; a miss is FLT_MAX / 0,0,0 / 0 / 0).  Host pointers;
+ * staged through buffers of the context that grow on demand; returns when `out` is filled. */
+int rtx_trace_rays(rtx_ctx* ctx, const rtx_ray* rays, uint32_t n, uint32_t mask, const rtx_aov_planes* out);
+/* Scene::DoesHit (Scene.cpp:68-96) on each ray: out[i] = 1 if anything lies in [tmin, tmax] as DoesHit
+ * decides it (the any-hit front/back cull swap of Utils.h:114-127 included), else 0. */
+int rtx_occluded(rtx_ctx* ctx, const rtx_ray* rays, uint32_t n, uint8_t* out);
+/* The same two with DEVICE pointers (of the context's device), queued on the context stream and
+ * returning at once; complete after rtx_synchronize.  The caller makes the rays visible before the
+ * call and keeps every buffer alive until then. */
+int rtx_trace_rays_device(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, uint32_t mask, const rtx_aov_planes* d_out);
+int rtx_occluded_device(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, uint8_t* d_out);
 
 /* ---- one frame over several GPUs from one process ------------------
  * The reference's Renderer::Render covers the frame with parallel_for

@@ -27,6 +27,12 @@ int rtx_time_views(rtx_ctx* ctx, const rtx_camera* cams, int n_views, const rtx_
  * passes, the mean device time of one in ms.  The planes then hold the pass, as after rtx_render_aov_async. */
 int rtx_time_aov_frames(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_params* params, uint32_t mask,
                         int iters, float* mean_ms);
+/* The same for a ray query on device pointers (rtx.h): `iters` back-to-back queries of the same n rays,
+ * the mean device time of one in ms.  what 0: rtx_trace_rays_device(d_rays, n, mask, d_out); 1:
+ * rtx_occluded_device(d_rays, n, d_occ); 2: the yardstick, a device-to-device copy of the n rays (32 n
+ * bytes) into the context's staging buffer. */
+int rtx_time_ray_queries(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, int what, uint32_t mask,
+                         const rtx_aov_planes* d_out, uint8_t* d_occ, int iters, float* mean_ms);
 /* Bytes of HBM the uploaded scene image occupies. */
 int rtx_scene_bytes(const rtx_ctx* ctx, uint64_t* bytes);
 /* Diagnostics: copy the context's current scene image (DESIGN.md §2 layout) after its queued

@@ -78,6 +78,44 @@ public:
         return RenderAov(cam, mask);
     }
 
+    // Ray queries against the uploaded scene (rtx_trace_rays / rtx_occluded; not in the reference's
+    // Renderer): Scene::GetClosestHit and Scene::DoesHit on the caller's rays, uninterpreted (rtx.h).
+    // TraceRays: element i of every plane of `mask` is ray i's record, the other planes stay empty.
+    AovFrame TraceRays(const std::vector<rtx_ray>& rays, uint32_t mask = RTX_AOV_ALL) {
+        const size_t n = rays.size();
+        AovFrame f;
+        if (mask & RTX_AOV_DEPTH) f.depth.resize(n);
+        if (mask & RTX_AOV_NORMAL) f.normal.resize(3 * n);
+        if (mask & RTX_AOV_MATERIAL) f.material.resize(n);
+        if (mask & RTX_AOV_PRIMITIVE) f.primitive.resize(n);
+        const rtx_aov_planes out = {f.depth.empty() ? nullptr : f.depth.data(), f.normal.empty() ? nullptr : f.normal.data(),
+                                    f.material.empty() ? nullptr : f.material.data(),
+                                    f.primitive.empty() ? nullptr : f.primitive.data()};
+        Check(rtx_trace_rays(m_Ctx, rays.data(), static_cast<uint32_t>(n), mask, &out), "rtx_trace_rays");
+        return f;
+    }
+    AovFrame TraceRays(rtx_host_scene* scene, const std::vector<rtx_ray>& rays, uint32_t mask = RTX_AOV_ALL,
+                       bool upload = true) {
+        rtx_scene s;
+        rtx_camera cam;
+        Check(rtx_host_scene_view(scene, &s, &cam), "rtx_host_scene_view");
+        if (upload) Upload(s);
+        return TraceRays(rays, mask);
+    }
+    // Occluded: element i is 1 when anything lies in ray i's [tmin, tmax] as DoesHit decides it.
+    std::vector<uint8_t> Occluded(const std::vector<rtx_ray>& rays) {
+        std::vector<uint8_t> out(rays.size());
+        Check(rtx_occluded(m_Ctx, rays.data(), static_cast<uint32_t>(rays.size()), out.data()), "rtx_occluded");
+        return out;
+    }
+    std::vector<uint8_t> Occluded(rtx_host_scene* scene, const std::vector<rtx_ray>& rays, bool upload = true) {
+        rtx_scene s;
+        rtx_camera cam;
+        Check(rtx_host_scene_view(scene, &s, &cam), "rtx_host_scene_view");
+        if (upload) Upload(s);
+        return Occluded(rays);
+    }
+
     void CycleLightingMode() {                                                     // Renderer.cpp:189-193
         m_CurrentLightingMode = static_cast<LightingMode>((static_cast<int>(m_CurrentLightingMode) + 1) %
                                                           static_cast<int>(LightingMode::Count));

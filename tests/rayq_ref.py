@@ -1,0 +1,141 @@
+"""Ray queries (include/rtx.h: rtx_trace_rays, rtx_occluded) on the CPU — TEST INFRASTRUCTURE (the
+checker of tests/test_rayq_cpu.py and tests/test_gpu_rayq.py).
+
+tests/rayq_ref.c includes tests/aov_ref.c, and through it oracle/rtx_oracle.c, both unchanged: per ray
+the oracle's own closest_hit (plus aov_ref.c's id-tracking copy, checked against it bit for bit) and
+does_hit.  `build` compiles it as aov_ref.build compiles its own; rays are (n, 8) float32 rows
+{origin, direction, tmin, tmax}; results compare with aov_ref.same (word for word, a NaN float equals
+any NaN)."""
+from __future__ import annotations
+
+import ctypes as C
+import subprocess
+from pathlib import Path
+
+import numpy as np
+
+import aov_ref
+from gp1_raytracer_2223_amd import abi
+
+ROOT = Path(__file__).resolve().parents[1]
+NAMES = aov_ref.NAMES
+GOLDEN = ROOT / "tests" / "golden" / "rayq"
+
+
+def build(outdir) -> C.CDLL:
+    so = Path(outdir) / "librayq_ref.so"
+    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
+                    f"-I{ROOT / 'include'}", str(ROOT / "tests" / "rayq_ref.c"), "-o", str(so), "-lm", "-lpthread"],
+                   check=True)
+    lib = C.CDLL(str(so))
+    P = C.POINTER
+    fp, up = P(C.c_float), P(C.c_uint32)
+    lib.rayq_ref_trace.argtypes = [P(abi.Scene), fp, C.c_uint32, fp, fp, up, up]
+    lib.rayq_ref_trace.restype = C.c_int
+    lib.rayq_ref_occluded.argtypes = [P(abi.Scene), fp, C.c_uint32, P(C.c_uint8)]
+    lib.rayq_ref_occluded.restype = None
+    lib.rayq_ref_primary.argtypes = [P(abi.Camera), C.c_uint32, C.c_uint32, fp]
+    lib.rayq_ref_primary.restype = None
+    lib.rayq_ref_shadow.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, C.c_uint32, fp, up]
+    lib.rayq_ref_shadow.restype = C.c_uint32
+    # aov_ref.c's own export, for the comparison with the hit pass's checker
+    lib.aov_ref_planes.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, fp, fp, up, up]
+    lib.aov_ref_planes.restype = C.c_int
+    return lib
+
+
+def _rays(rays) -> np.ndarray:
+    a = np.ascontiguousarray(rays, np.float32)
+    assert a.ndim == 2 and a.shape[1] == 8, a.shape
+    return a
+
+
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def trace(lib: C.CDLL, scene: abi.Scene, rays) -> dict:
+    """Scene::GetClosestHit per ray: the four planes, element i = ray i's record."""
+    a = _rays(rays)
+    n = a.shape[0]
+    out = {"depth": np.zeros(n, np.float32), "normal": np.zeros(3 * n, np.float32),
+           "material": np.zeros(n, np.uint32), "primitive": np.zeros(n, np.uint32)}
+    up = C.POINTER(C.c_uint32)
+    rc = lib.rayq_ref_trace(C.byref(scene), _fp(a), n, _fp(out["depth"]), _fp(out["normal"]),
+                            out["material"].ctypes.data_as(up), out["primitive"].ctypes.data_as(up))
+    assert rc == 0, f"the id-tracking walk left the oracle's closest_hit at ray {-rc - 1}"
+    return out
+
+
+def occluded(lib: C.CDLL, scene: abi.Scene, rays) -> np.ndarray:
+    """Scene::DoesHit per ray: uint8[n]."""
+    a = _rays(rays)
+    out = np.zeros(a.shape[0], np.uint8)
+    lib.rayq_ref_occluded(C.byref(scene), _fp(a), a.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out
+
+
+def primary(lib: C.CDLL, cam: abi.Camera, width: int, height: int) -> np.ndarray:
+    """The primary rays of a width x height frame, row-major."""
+    rays = np.zeros((width * height, 8), np.float32)
+    lib.rayq_ref_primary(C.byref(cam), width, height, _fp(rays))
+    return rays
+
+
+def shadow(lib: C.CDLL, scene: abi.Scene, cam: abi.Camera, width: int, height: int, light: int = 0):
+    """(rays, pixel): the renderer's shadow ray toward `light` of every pixel that hits, and each ray's
+    pixel index."""
+    rays = np.zeros((width * height, 8), np.float32)
+    pixel = np.zeros(width * height, np.uint32)
+    n = lib.rayq_ref_shadow(C.byref(scene), C.byref(cam), width, height, light, _fp(rays),
+                            pixel.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return rays[:n].copy(), pixel[:n].copy()
+
+
+def prefix(planes: dict, n: int) -> dict:
+    """The first n rays' part of a trace result."""
+    return {k: (v[:3 * n] if k == "normal" else v[:n]) for k, v in planes.items()}
+
+
+# tests/golden/rayq/<case>.npz: rays, the checker's four planes and its occlusion bytes.  Two catalogue
+# scenes and the fuzz families `open` 12 (misses), `ties` 0 (equal t) and `nonfinite` 0 (non-finite
+# geometry).  `python tests/rayq_ref.py` rewrites them.
+GOLDEN_CASES = ("W1", "W4_Bunny", "open_12", "ties_0", "nonfinite_0")
+GOLDEN_SEED = 20240611
+
+
+def golden_view(case: str, tmp_dir):
+    """(keep-alive, flattened scene, camera) of a golden case."""
+    from gp1_raytracer_2223_amd.scene import HostScene
+    if "_" in case and case.rsplit("_", 1)[1].isdigit() and not case.startswith("W"):
+        family, seed = case.rsplit("_", 1)
+        return aov_ref.golden_view(family, int(seed), tmp_dir)
+    hs = HostScene(case)
+    return (hs, *hs.view())
+
+
+def golden_rays(scene: abi.Scene) -> np.ndarray:
+    """Every set that needs no camera, 1,568 rays."""
+    import rayq_rays
+    return np.concatenate([rayq_rays.scatter(GOLDEN_SEED, 384), rayq_rays.aimed(scene, GOLDEN_SEED + 1, 384),
+                           rayq_rays.octant(scene, GOLDEN_SEED + 2), rayq_rays.nonfinite(scene, GOLDEN_SEED + 3)])
+
+
+def golden_of(lib: C.CDLL, scene: abi.Scene) -> dict:
+    rays = golden_rays(scene)
+    out = {"rays": rays, "occluded": occluded(lib, scene, rays)}
+    out.update(trace(lib, scene, rays))
+    return out
+
+
+if __name__ == "__main__":
+    import sys
+    import tempfile
+    sys.path.insert(0, str(ROOT / "tests"))
+    GOLDEN.mkdir(parents=True, exist_ok=True)
+    with tempfile.TemporaryDirectory() as td:
+        lib_ = build(td)
+        for case_ in GOLDEN_CASES:
+            keep_, s_, _ = golden_view(case_, td)
+            np.savez_compressed(GOLDEN / f"{case_}.npz", **golden_of(lib_, s_))
+            del keep_

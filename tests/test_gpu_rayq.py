@@ -1,0 +1,395 @@
+"""Ray queries (rtx_trace_rays*, rtx_occluded*: rtx_query_kernel) on the GPU against the checker of
+tests/rayq_ref.py: every output word equals the checker's (a NaN float equals any NaN), on the
+catalogue scenes, the fuzz scenes and the committed goldens, with every ray set of tests/rayq_rays.py
+and the lengths around a wave boundary, through every walk (octant copies, fast, exact, deep stacks in
+LDS and in HBM), the device variants, beside frames and passes they must not disturb, after a device
+Update, through the Python Renderer, and on the error paths."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch   # at collection, before librtx_hip.so is loaded: imported after it, torch finds no device
+
+import aov_ref
+import oracle_bind
+import rayq_rays
+import rayq_ref
+from gp1_raytracer_2223_amd import abi
+from gp1_raytracer_2223_amd.renderer import (AOV_ALL, AOV_DEPTH, AOV_MATERIAL, AOV_NORMAL, AOV_PRIMITIVE, AOV_PLANES,
+                                             DeviceAnimation, DeviceContext, Renderer, aov_host_planes)
+from gp1_raytracer_2223_amd.scene import HostScene
+
+pytestmark = pytest.mark.gpu
+
+DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
+W, H = 37, 23
+SEED = 7
+NAMES = aov_ref.NAMES
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    return rayq_ref.build(tmp_path_factory.mktemp("rayq_ref"))
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = DeviceContext(DEV)
+    yield c
+    c.close()
+
+
+_scenes = {}
+_cases = {}
+
+
+def _scene(name, t=-1.0):
+    if (name, t) not in _scenes:
+        hs = HostScene(name)
+        if t >= 0:
+            hs.update(t)
+        _scenes[(name, t)] = (hs, *hs.view())
+    return _scenes[(name, t)][1:]
+
+
+def _frozen(rays, planes, occ):
+    for a in (rays, occ, *planes.values()):
+        a.setflags(write=False)
+    return rays, planes, occ
+
+
+def _sets(checker, name, t=-1.0):
+    """{set: (rays, the checker's planes, the checker's occlusion bytes)} of a catalogue scene: every set
+    that applies to it, computed once and never written to."""
+    key = (name, t)
+    if key not in _cases:
+        s, cam = _scene(name, t)
+        sets = {"primary": rayq_ref.primary(checker, cam, W, H), "scatter": rayq_rays.scatter(SEED, 512),
+                "nonfinite": rayq_rays.nonfinite(s, SEED)}
+        if s.n_lights:
+            sets["shadow"] = rayq_ref.shadow(checker, s, cam, W, H, 0)[0]
+        if s.n_meshes:
+            sets["aimed"] = rayq_rays.aimed(s, SEED, 512)
+            sets["octant"] = rayq_rays.octant(s, SEED)
+        _cases[key] = {k: _frozen(r, rayq_ref.trace(checker, s, r), rayq_ref.occluded(checker, s, r))
+                       for k, r in sets.items()}
+    return _cases[key]
+
+
+def _check(c, rays, planes, occ, what):
+    """Both queries on the whole set and on its four short prefixes."""
+    for n in (rays.shape[0],) + tuple(k for k in rayq_rays.LENGTHS if k < rays.shape[0]):
+        got = c.trace_rays(rays[:n])
+        assert sorted(got) == sorted(NAMES)
+        bad = aov_ref.diff(got, rayq_ref.prefix(planes, n))
+        assert not bad, f"{what}, n = {n}: planes {bad} differ"
+        o = c.occluded(rays[:n])
+        assert o.dtype == np.uint8 and np.array_equal(o, occ[:n]), \
+            f"{what}, n = {n}: occlusion differs at rays {np.nonzero(o != occ[:n])[0][:8].tolist()}"
+
+
+PARITY = [("W1", -1.0), ("W2", -1.0), ("W3", -1.0), ("W4_Reference", -1.0), ("W4_Bunny", -1.0), ("W4_Bunny", 1.3),
+          ("W4_Optional", -1.0)]
+
+
+@pytest.mark.parametrize("name,t", PARITY)
+def test_parity(ctx, checker, name, t):
+    s, _ = _scene(name, t)
+    ctx.upload(s)
+    for k, (rays, planes, occ) in _sets(checker, name, t).items():
+        assert 65 < rays.shape[0] <= 2048, (k, rays.shape)
+        _check(ctx, rays, planes, occ, f"{name}/t{t}/{k}")
+
+
+CASES = aov_ref.golden_cases()
+
+
+@pytest.mark.parametrize("family,seed", CASES, ids=[f"{f}_{s}" for f, s in CASES])
+def test_fuzz_scenes(ctx, checker, tmp_path, family, seed):
+    keep, s, cam = aov_ref.golden_view(family, seed, tmp_path)
+    ctx.upload(s)
+    rays = np.concatenate([rayq_ref.golden_rays(s), rayq_ref.primary(checker, cam, aov_ref.GOLDEN_W, aov_ref.GOLDEN_H)[:448]])
+    assert rays.shape[0] <= 2048
+    _check(ctx, rays, rayq_ref.trace(checker, s, rays), rayq_ref.occluded(checker, s, rays), f"{family}_{seed}")
+    del keep
+
+
+@pytest.mark.parametrize("case", rayq_ref.GOLDEN_CASES)
+def test_committed_goldens(ctx, tmp_path, case):
+    keep, s, _ = rayq_ref.golden_view(case, tmp_path)
+    g = np.load(rayq_ref.GOLDEN / f"{case}.npz")
+    ctx.upload(s)
+    bad = aov_ref.diff(ctx.trace_rays(g["rays"]), {k: g[k] for k in NAMES})
+    assert not bad, f"{case}: planes {bad} differ from the golden"
+    assert np.array_equal(ctx.occluded(g["rays"]), g["occluded"]), case
+    del keep
+
+
+@pytest.mark.parametrize("name", ["W4_Bunny", "W3"])
+def test_primary_rays_equal_the_hit_pass(ctx, checker, name):
+    s, cam = _scene(name)
+    ctx.upload(s)
+    want = ctx.render_aov(cam, abi.make_params(W, H))
+    got = ctx.trace_rays(_sets(checker, name)["primary"][0])
+    assert not aov_ref.diff(got, want)
+
+
+@pytest.mark.parametrize("T", [300, 1100])
+def test_deep_stack_variants(ctx, checker, T):
+    """T = 300: the deep LDS stack (DEEP); 1100: the stacks in HBM (DEEP + HSTK)."""
+    from test_gpu_deep_bvh import deep_scene
+    s, cam, keep = deep_scene(T)
+    ctx.upload(s)
+    rays = np.concatenate([rayq_rays.aimed(s, SEED, 512), rayq_rays.octant(s, SEED), rayq_rays.nonfinite(s, SEED)])
+    planes = rayq_ref.trace(checker, s, rays)
+    tri = aov_ref.kind(planes["primitive"]) == 3
+    assert tri.mean() >= 0.05 and (aov_ref.index(planes["primitive"])[tri] < T).all()
+    _check(ctx, rays, planes, rayq_ref.occluded(checker, s, rays), f"chain of {T}")
+    del keep
+
+
+def test_hbm_stacks_cut_a_large_query_into_launches(ctx, checker):
+    """A 2,500-level chain needs 60 KB of HBM stack per wave, and a query asks for at most 256 MB of
+    stacks per launch: 300,000 rays are two launches (286,208 + 13,792).  The rays are 2,048 distinct
+    ones repeated, so the checker's planes repeated are the expectation for every launch's part."""
+    from test_gpu_deep_bvh import deep_scene
+    T, n = 2500, 300_000
+    s, cam, keep = deep_scene(T)
+    ctx.upload(s)
+    base = rayq_rays.aimed(s, SEED, 2048)
+    planes, occ = rayq_ref.trace(checker, s, base), rayq_ref.occluded(checker, s, base)
+    assert (aov_ref.kind(planes["primitive"]) == 3).mean() >= 0.05 and 0.05 <= occ.mean() <= 0.95
+    reps = -(-n // 2048)
+    rays = np.tile(base, (reps, 1))[:n]
+    want = {k: np.tile(v, reps)[:(3 * n if k == "normal" else n)] for k, v in planes.items()}
+    assert not aov_ref.diff(ctx.trace_rays(rays), want)
+    assert np.array_equal(ctx.occluded(rays), np.tile(occ, reps)[:n])
+    del keep
+
+
+def _torch():
+    assert torch.cuda.is_available(), "torch sees no GPU (was librtx_hip.so loaded before torch was imported?)"
+    return torch, torch.device("cuda", DEV)
+
+
+SENT_F = np.float32(-7.5)
+
+
+def test_device_variants_and_mask_subsets(ctx, checker):
+    """Rays and outputs as torch tensors.  The four planes and the occlusion bytes lie in one sentinel-
+    filled buffer with guard words between them: a query writes the planes of its mask and nothing else."""
+    torch, dev = _torch()
+    s, _ = _scene("W4_Bunny")
+    ctx.upload(s)
+    rays, planes, occ = _sets(checker, "W4_Bunny")["aimed"]
+    for n in (rays.shape[0], 65, 1):
+        d_rays = torch.from_numpy(np.array(rays[:n])).to(dev)
+        guard = 64
+        off, total = {}, guard
+        for k, (_, _, e) in AOV_PLANES.items():
+            off[k] = total
+            total += e * n + guard
+        want = rayq_ref.prefix(planes, n)
+        for mask in (AOV_ALL, AOV_DEPTH, AOV_NORMAL | AOV_PRIMITIVE, AOV_MATERIAL):
+            buf = torch.full((total,), float(SENT_F), dtype=torch.float32, device=dev)
+            d_occ = torch.full((n + guard,), 0xAB, dtype=torch.uint8, device=dev)
+            named = [k for k, (bit, _, _) in AOV_PLANES.items() if mask & bit]
+            torch.cuda.synchronize()
+            ctx.trace_rays_device(d_rays.data_ptr(), n, mask, {k: buf.data_ptr() + 4 * off[k] for k in named})
+            ctx.occluded_device(d_rays.data_ptr(), n, d_occ.data_ptr())
+            ctx.synchronize()
+            host = buf.cpu().numpy()
+            keep = np.ones(total, bool)
+            for k in named:
+                e = AOV_PLANES[k][2]
+                got = host[off[k]:off[k] + e * n].view(AOV_PLANES[k][1])
+                assert aov_ref.same(got, want[k]), (n, mask, k)
+                keep[off[k]:off[k] + e * n] = False
+            assert (host[keep] == SENT_F).all(), (n, mask)
+            o = d_occ.cpu().numpy()
+            assert np.array_equal(o[:n], occ[:n]) and (o[n:] == 0xAB).all(), (n, mask)
+    # the host variant returns the planes of its mask only
+    got = ctx.trace_rays(rays, AOV_NORMAL | AOV_MATERIAL)
+    assert sorted(got) == ["material", "normal"] and not aov_ref.diff(got, planes, ["normal", "material"])
+
+
+def _colour_ok(c, s, cam, w=W, h=H):
+    """A colour frame of the pow-free Bunny scene equals the oracle's."""
+    gpx, grgb = c.render(cam, abi.make_params(w, h))
+    rpx, rrgb = oracle_bind.render(s, cam, abi.make_params(w, h))
+    assert np.array_equal(gpx, rpx) and np.array_equal(grgb.view(np.uint32), rrgb.view(np.uint32))
+
+
+def test_frames_and_passes_are_untouched(checker):
+    torch, dev = _torch()
+    s, cam = _scene("W4_Bunny")
+    rays, planes, occ = _sets(checker, "W4_Bunny")["aimed"]
+    p = abi.make_params(W, H)
+    c = DeviceContext(DEV)
+    try:
+        c.upload(s)
+        _colour_ok(c, s, cam)
+        spec, sched = c.spec_info(), c.split_info()
+        pass_planes = c.render_aov(cam, p)
+        assert not aov_ref.diff(c.trace_rays(rays), planes)
+        assert np.array_equal(c.occluded(rays), occ)
+        # the hit pass's planes and its last-pass record
+        again = c.download_aov(aov_host_planes(W, H, AOV_ALL))
+        assert not aov_ref.diff(again, pass_planes)
+        # the colour frame buffer and the last-frame record
+        px = np.full(W * H, 0xDEADBEEF, np.uint32)
+        c.gather_async(px)
+        c.synchronize()
+        assert np.array_equal(px, oracle_bind.render(s, cam, p)[0])
+        _colour_ok(c, s, cam)
+        assert c.spec_info() == spec and c.split_info() == sched
+        # a query between two frames in flight changes neither
+        cam2 = abi.Camera()
+        C.memmove(C.byref(cam2), C.byref(cam), C.sizeof(abi.Camera))
+        cam2.origin[0] = cam.origin[0] + 0.5
+        d_rays = torch.from_numpy(np.array(rays)).to(dev)
+        d_occ = torch.zeros(rays.shape[0], dtype=torch.uint8, device=dev)
+        d_depth = torch.zeros(rays.shape[0], dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        pa, pb = np.zeros(W * H, np.uint32), np.zeros(W * H, np.uint32)
+        c.render_async(cam, p)
+        c.gather_async(pa)
+        c.trace_rays_device(d_rays.data_ptr(), rays.shape[0], AOV_DEPTH, {"depth": d_depth.data_ptr()})
+        c.occluded_device(d_rays.data_ptr(), rays.shape[0], d_occ.data_ptr())
+        c.render_async(cam2, p)
+        c.gather_async(pb)
+        c.synchronize()
+        assert np.array_equal(pa, oracle_bind.render(s, cam, p)[0])
+        assert np.array_equal(pb, oracle_bind.render(s, cam2, p)[0])
+        assert aov_ref.same(d_depth.cpu().numpy(), planes["depth"]) and np.array_equal(d_occ.cpu().numpy(), occ)
+        # queries are not frames: a supersample factor does not matter
+        c.set_supersample(2)
+        assert not aov_ref.diff(c.trace_rays(rays), planes) and np.array_equal(c.occluded(rays), occ)
+        c.set_supersample(1)
+        _colour_ok(c, s, cam)
+    finally:
+        c.close()
+
+
+def test_device_update(checker):
+    """After a device Update a query sees the rebuilt mesh: the checker runs on rtx_anim_download's
+    geometry (its triangle order is the primitive plane's)."""
+    dev_scene = HostScene("W4_Bunny")
+    s0, _ = dev_scene.view()
+    c = DeviceContext(DEV)
+    anim = DeviceAnimation(dev_scene, c)
+    try:
+        anim.update(1.3, c)
+        assert list(anim.status(0)[:1]) == [0] and len(anim.mesh_ids) == 1 and s0.n_meshes == 1
+        g = anim.download(0)
+        used = int(anim.status(0)[2])
+        nodes = (abi.BVHNode * used)()
+        raw = np.ascontiguousarray(g["nodes"][:used], np.uint32)
+        C.memmove(nodes, raw.ctypes.data, used * C.sizeof(abi.BVHNode))
+        pos, idx, nrm = (np.ascontiguousarray(g[k]) for k in ("tpositions", "indices", "tnormals"))
+        m = abi.Mesh()
+        m.positions, m.n_positions = pos.ctypes.data_as(C.POINTER(C.c_float)), pos.size // 3
+        m.indices, m.n_indices = idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size
+        m.normals = nrm.ctypes.data_as(C.POINTER(C.c_float))
+        m.nodes, m.n_nodes = nodes, used
+        m.cull_mode, m.material = s0.meshes[0].cull_mode, s0.meshes[0].material
+        meshes = (abi.Mesh * 1)(m)
+        s = abi.Scene()
+        C.memmove(C.byref(s), C.byref(s0), C.sizeof(abi.Scene))
+        s.meshes = meshes
+        rays = np.concatenate([rayq_rays.aimed(s, SEED, 512), rayq_rays.octant(s, SEED)])
+        planes = rayq_ref.trace(checker, s, rays)
+        assert (aov_ref.kind(planes["primitive"]) == 3).mean() >= 0.25
+        _check(c, rays, planes, rayq_ref.occluded(checker, s, rays), "after a device Update")
+        # ... and the turned mesh is not the uploaded one
+        still = rayq_ref.trace(checker, s0, rays)
+        assert aov_ref.diff(planes, still)
+    finally:
+        anim.close()
+        c.close()
+
+
+def test_renderer(checker):
+    rays, planes, occ = _sets(checker, "W4_Bunny")["aimed"]
+    r = Renderer(W, H, device=DEV)
+    try:
+        hs = HostScene("W4_Bunny")
+        assert not aov_ref.diff(r.TraceRays(hs, rays), planes)
+        got = r.TraceRays(hs, rays, AOV_PRIMITIVE, upload=False)
+        assert list(got) == ["primitive"] and aov_ref.same(got["primitive"], planes["primitive"])
+        assert np.array_equal(r.Occluded(hs, rays, upload=False), occ)
+        assert np.array_equal(r.Occluded(hs, rays), occ)
+    finally:
+        r.ctx.close()
+
+
+def test_errors_leave_the_context_usable(checker):
+    s, cam = _scene("W4_Bunny")
+    rays, planes, occ = _sets(checker, "W4_Bunny")["aimed"]
+    n = rays.shape[0]
+    c = DeviceContext(DEV)
+    lib, h = c.lib, c.h
+    rp = np.array(rays).ctypes.data_as(C.POINTER(abi.Ray))
+    depth, normal = np.zeros(n, np.float32), np.zeros(3 * n, np.float32)
+    out_occ = np.zeros(n, np.uint8)
+    op = out_occ.ctypes.data_as(C.POINTER(C.c_uint8))
+    out = abi.AovPlanes()
+    out.depth = depth.ctypes.data_as(C.POINTER(C.c_float))
+
+    def still_works(after):
+        assert not aov_ref.diff(c.trace_rays(rays), planes), after
+        assert np.array_equal(c.occluded(rays), occ), after
+
+    try:
+        # no scene uploaded
+        assert lib.rtx_trace_rays(h, rp, n, AOV_DEPTH, C.byref(out)) == abi.RTX_E_STATE
+        assert b"no scene" in lib.rtx_last_error(h)
+        assert lib.rtx_occluded(h, rp, n, op) == abi.RTX_E_STATE
+        assert lib.rtx_trace_rays_device(h, 256, n, AOV_DEPTH, C.byref(out)) == abi.RTX_E_STATE
+        assert lib.rtx_occluded_device(h, 256, n, 256) == abi.RTX_E_STATE
+        c.upload(s)
+        still_works("the calls without a scene")
+        # NULL arguments
+        assert lib.rtx_trace_rays(None, rp, n, AOV_DEPTH, C.byref(out)) == abi.RTX_E_INVALID
+        assert lib.rtx_occluded(None, rp, n, op) == abi.RTX_E_INVALID
+        assert lib.rtx_trace_rays(h, None, n, AOV_DEPTH, C.byref(out)) == abi.RTX_E_INVALID
+        assert lib.rtx_trace_rays(h, rp, n, AOV_DEPTH, None) == abi.RTX_E_INVALID
+        assert lib.rtx_occluded(h, None, n, op) == abi.RTX_E_INVALID
+        assert lib.rtx_occluded(h, rp, n, None) == abi.RTX_E_INVALID
+        assert lib.rtx_trace_rays_device(h, None, n, AOV_DEPTH, C.byref(out)) == abi.RTX_E_INVALID
+        assert lib.rtx_occluded_device(h, None, n, 256) == abi.RTX_E_INVALID
+        assert lib.rtx_occluded_device(h, 256, n, None) == abi.RTX_E_INVALID
+        still_works("the NULL arguments")
+        # empty and unknown masks
+        for mask in (0, 16, AOV_ALL | 32):
+            assert lib.rtx_trace_rays(h, rp, n, mask, C.byref(out)) == abi.RTX_E_INVALID, mask
+            assert b"mask" in lib.rtx_last_error(h), mask
+            assert lib.rtx_trace_rays_device(h, 256, n, mask, C.byref(out)) == abi.RTX_E_INVALID, mask
+        still_works("the bad masks")
+        # a plane the mask does not name
+        both = abi.AovPlanes()
+        both.depth = out.depth
+        both.normal = normal.ctypes.data_as(C.POINTER(C.c_float))
+        assert lib.rtx_trace_rays(h, rp, n, AOV_DEPTH, C.byref(both)) == abi.RTX_E_INVALID
+        assert b"mask" in lib.rtx_last_error(h)
+        assert lib.rtx_trace_rays_device(h, 256, n, AOV_NORMAL, C.byref(out)) == abi.RTX_E_INVALID
+        assert (depth == 0).all() and (normal == 0).all() and (out_occ == 0).all()
+        still_works("the unnamed plane")
+        # n == 0: nothing launched, nothing needed
+        assert lib.rtx_trace_rays(h, None, 0, AOV_ALL, None) == abi.RTX_OK
+        assert lib.rtx_occluded(h, None, 0, None) == abi.RTX_OK
+        assert lib.rtx_trace_rays_device(h, None, 0, AOV_ALL, None) == abi.RTX_OK
+        assert lib.rtx_occluded_device(h, None, 0, None) == abi.RTX_OK
+        empty = c.trace_rays(np.zeros((0, 8), np.float32))
+        assert sorted(empty) == sorted(NAMES) and all(v.size == 0 for v in empty.values())
+        assert c.occluded(np.zeros((0, 8), np.float32)).size == 0
+        with pytest.raises(ValueError):
+            c.trace_rays(np.zeros((4, 7), np.float32))
+        still_works("the empty queries")
+        # a good call through the raw entry point fills only what it was given
+        assert lib.rtx_trace_rays(h, rp, n, AOV_DEPTH, C.byref(out)) == abi.RTX_OK
+        assert aov_ref.same(depth, planes["depth"]) and (normal == 0).all()
+        _colour_ok(c, s, cam)
+    finally:
+        c.close()
