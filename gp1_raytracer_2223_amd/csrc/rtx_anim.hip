@@ -658,12 +658,15 @@ __device__ __forceinline__ void node_small(const Store<LDS>& St, TmpNode* nodes,
         (&sl.bl[0][0][0])[i] = FLT_MAX;
         (&sl.bh[0][0][0])[i] = FLT_MIN;
     }
-    // 2. centroid bounds (DataTypes.h:404-419), order-free
+    // 2. centroid bounds (DataTypes.h:404-419), order-free.  The folds start from FLT_MAX and
+    //    FLT_MIN as the reference's do: with all 128 positions taken no lane brings the start
+    //    values in for an absent element, and centroids that are all negative must still give
+    //    maxBounds = FLT_MIN (the wave reductions fold the lanes' values only)
     float mn3[3], mx3[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        mn3[a] = fminf(v[0] ? c[0][a] : FLT_MAX, v[1] ? c[1][a] : FLT_MAX);
-        mx3[a] = fmaxf(v[0] ? c[0][a] : FLT_MIN, v[1] ? c[1][a] : FLT_MIN);
+        mn3[a] = fminf(FLT_MAX, fminf(v[0] ? c[0][a] : FLT_MAX, v[1] ? c[1][a] : FLT_MAX));
+        mx3[a] = fmaxf(FLT_MIN, fmaxf(v[0] ? c[0][a] : FLT_MIN, v[1] ? c[1][a] : FLT_MIN));
     }
     wred_min(mn3);
     wred_max(mx3);

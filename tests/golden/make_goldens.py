@@ -19,6 +19,10 @@ the reference's own functions:
                         harness with the reference's own classes
   fuzz/<family>_<seed>.rtxscene, .npz   the seeded adversarial scenes of tests/scene_fuzz.py (the
                         generated text) and the reference's 44x28 frames of them, modes (3,1), (2,0)
+  meshfuzz/<family>_<seed>.npz   the adversarial meshes of tests/mesh_fuzz.py (written by
+                        make_mesh_goldens.py, not by this script): per-mesh digests after every prefix
+                        of the case's Update list, shape facts of the reference's trees (nodes, largest
+                        leaf, depth, inf and -0 words) and its 44x28 frames, modes (3,1), (0,1)
 
 Usage:  python tests/golden/make_goldens.py [--scene-files-only | --configs-only | --fuzz-only]
 

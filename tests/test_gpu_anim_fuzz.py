@@ -1,0 +1,166 @@
+"""The device Update (rtx_anim_*, csrc/rtx_anim.hip) on the adversarial meshes of tests/mesh_fuzz.py:
+trees of one node, of three nodes with a leaf of 5,000 triangles, roots that never split above every
+LDS capacity, partitions without a cost, exact SAH ties — shapes the bundled meshes never produce
+(DESIGN.md §7a).  The host layer is the authority: tests/test_mesh_fuzz_golden.py pins it to the
+reference on these very cases.  Every comparison is bit-exact:
+  * state: after each Update of a case's list the device state equals the host's
+    (test_gpu_anim._compare_state) and no mesh reports an error — under the default settings, with
+    the build records in HBM, with the task cut at 8 and at 100000, and with the serial frontier;
+  * image: the scene image after the list equals the upload of the host-updated scene word for word
+    (the frontier parts of 1-node and 3-node trees included);
+  * frames: colour frames (three per context: later ones run cost-ordered or split) equal the
+    reference's own golden frame, and the hit planes equal the CPU checker's (tests/aov_ref.py) — the
+    primitive id exposes a wrong triangle order inside a leaf that pixels can hide — both from the
+    device-animated context and from a plain upload of the host-updated scene (the render kernel's
+    leaf loop on leaves of thousands, without the device builder in the way).
+An error status (timeout, capacity) on any of these meshes is a failure, never retried."""
+import functools
+import os
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import aov_ref
+import mesh_fuzz
+from gp1_raytracer_2223_amd import abi
+from gp1_raytracer_2223_amd.renderer import DeviceAnimation, DeviceContext
+from gp1_raytracer_2223_amd.scene import HostScene
+from test_gpu_anim import _compare_state, _image
+
+pytestmark = pytest.mark.gpu
+
+DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
+G = Path(__file__).resolve().parent / "golden" / "meshfuzz"
+W, H = 44, 28
+FRAMES = [(3, 1), (0, 1)]
+CASES = list(mesh_fuzz.COMMITTED)
+IDS = [f"{f}_{s}" for f, s in CASES]
+KNOBS = {"default": {}, "hbm": {"RTX_ANIM_HBM": "1"}, "cut8": {"RTX_ANIM_CUT": "8"},
+         "cut100000": {"RTX_ANIM_CUT": "100000"}, "serial_frontier": {"RTX_ANIM_SERIAL_FRONTIER": "1"}}
+# the serial frontier: the cases above its 4,096-triangle threshold, and two below it
+SERIAL = [("dup", 0), ("caps", 3), ("flat_grid", 0), ("mixed", 0)]
+STATE = ([(c, k) for c in CASES for k in ("default", "hbm", "cut8", "cut100000")] +
+         [(c, "serial_frontier") for c in SERIAL])
+
+
+@functools.lru_cache(maxsize=None)
+def _case(family, seed):
+    return mesh_fuzz.make(family, seed)
+
+
+@pytest.fixture(scope="module")
+def assets(tmp_path_factory):
+    """folder(case): the case's OBJ and scene files, written once."""
+    root, done = tmp_path_factory.mktemp("meshfuzz"), {}
+
+    def folder(case):
+        if case.name not in done:
+            d = root / case.name
+            d.mkdir()
+            done[case.name] = (d, case.write(d))
+        return done[case.name]
+    return folder
+
+
+def _host(assets, case):
+    d, scene = assets(case)
+    return HostScene(f"file:{scene}", asset_dir=str(d))
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    return aov_ref.build(tmp_path_factory.mktemp("aov_ref"))
+
+
+@pytest.fixture(scope="module")
+def two_ctx():
+    a, b = DeviceContext(DEV), DeviceContext(DEV)
+    yield a, b
+    a.close()
+    b.close()
+
+
+def _no_error(anim, what):
+    for k in range(len(anim.mesh_ids)):
+        assert int(anim.status(k)[0]) == 0, (what, k)
+
+
+@pytest.mark.parametrize("case,knob", STATE, ids=[f"{f}_{s}-{k}" for (f, s), k in STATE])
+def test_state_matches_host(gpu_ctx, assets, monkeypatch, case, knob):
+    for name, value in KNOBS[knob].items():
+        monkeypatch.setenv(name, value)     # read at rtx_anim_create
+    c = _case(*case)
+    dev_scene, host_scene = _host(assets, c), _host(assets, c)
+    anim = DeviceAnimation(dev_scene, gpu_ctx)
+    try:
+        assert [anim.n_tris[k] for k in range(len(anim.mesh_ids))] == list(c.triangles.values())[:len(anim.mesh_ids)]
+        for i, t in enumerate(c.times):
+            anim.update(t, gpu_ctx)
+            host_scene.update(t)
+            _no_error(anim, f"update {i}")
+            for k in range(len(anim.mesh_ids)):
+                _compare_state(anim, host_scene, k)
+    finally:
+        anim.close()
+
+
+IMAGE = [(c, False) for c in CASES] + [(c, True) for c in SERIAL]
+
+
+@pytest.mark.parametrize("case,serial", IMAGE, ids=[f"{f}_{s}-{'serial' if x else 'parallel'}" for (f, s), x in IMAGE])
+def test_image_equals_host_built_image(two_ctx, assets, monkeypatch, case, serial):
+    if serial:
+        monkeypatch.setenv("RTX_ANIM_SERIAL_FRONTIER", "1")     # read at rtx_anim_create
+    c = _case(*case)
+    d, h = _host(assets, c), _host(assets, c)
+    c1, c2 = two_ctx
+    a1 = DeviceAnimation(d, c1)
+    a2 = None
+    try:
+        for t in c.times:
+            a1.update(t, c1)
+            h.update(t)
+        _no_error(a1, "after the list")
+        a2 = DeviceAnimation(h, c2)     # registration = the upload path's layout of the host build
+        i1, i2 = _image(c1), _image(c2)
+        assert len(i1) == len(i2)
+        bad = np.nonzero(i1 != i2)[0]
+        assert len(bad) == 0, f"{len(bad)} words differ, first at byte {4 * bad[0]}"
+    finally:
+        a1.close()
+        if a2 is not None:
+            a2.close()
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_frames_and_hit_planes(two_ctx, assets, checker, case):
+    c = _case(*case)
+    g = np.load(G / f"{c.name}.npz")
+    dev_scene, host_scene = _host(assets, c), _host(assets, c)
+    a, b = two_ctx
+    anim = DeviceAnimation(dev_scene, a)
+    try:
+        for t in c.times:
+            anim.update(t, a)
+            host_scene.update(t)
+        _no_error(anim, "after the list")
+        s, cam = host_scene.view()
+        b.upload(s)     # the static render: a plain upload of the same state
+        want = aov_ref.planes(checker, s, cam, W, H)
+        if c.family != "overflow":      # (at 1e19 Moller-Trumbore overflows: no ray hits, on any side)
+            assert (aov_ref.kind(want["primitive"]) == 3).any(), "the frame does not show the mesh"
+        for ctx, who in ((a, "device Update"), (b, "host upload")):
+            for mode, sh in FRAMES:
+                p = abi.make_params(W, H, mode, sh)
+                gpx, grgb = g[f"pixels_m{mode}s{sh}"], g[f"rgb_m{mode}s{sh}"]
+                for frame in range(3):
+                    px, rgb = ctx.render(cam, p)
+                    what = f"{who}, mode {mode}, frame {frame}"
+                    assert np.array_equal(px, gpx), f"{what}: {(px != gpx).sum()} pixels differ from the reference"
+                    assert np.array_equal(rgb.view(np.uint32), grgb.view(np.uint32)), f"{what}: colour words differ"
+            got = ctx.render_aov(cam, abi.make_params(W, H))
+            bad = aov_ref.diff(got, want)
+            assert not bad, f"{who}: planes {bad} differ from the checker"
+    finally:
+        anim.close()
