@@ -182,7 +182,7 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_render_aov_async", "rtx_render_aov", "rtx_download_aov", "rtx_gather_aov_async",
                "rtx_device_aov_buffers", "rtx_group_render_aov", "rtx_time_aov_frames",
                "rtx_trace_rays", "rtx_occluded", "rtx_trace_rays_device", "rtx_occluded_device",
-               "rtx_time_ray_queries"]
+               "rtx_time_ray_queries", "rtx_room_info"]
 
 
 def load_hip() -> C.CDLL:
@@ -261,6 +261,9 @@ def load_hip() -> C.CDLL:
         if hasattr(lib, "rtx_spec_info"):   # absent only in older experiment builds (RTX_HIP_LIB)
             lib.rtx_spec_info.argtypes = [VP, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
             lib.rtx_spec_info.restype = C.c_int
+        if hasattr(lib, "rtx_room_info"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_room_info.argtypes = [VP, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+            lib.rtx_room_info.restype = C.c_int
         if hasattr(lib, "rtx_split_info"):   # absent only in older experiment builds (RTX_HIP_LIB)
             lib.rtx_split_info.argtypes = [VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
             lib.rtx_split_info.restype = C.c_int

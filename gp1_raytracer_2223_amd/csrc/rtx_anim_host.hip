@@ -42,6 +42,8 @@ struct rtx_anim {
     bool split_ok = false;
     int spec = 0;
     float room_p0[5] = {};   // rtx_ctx::room_p0 of the registration upload
+    bool room_fact = false;  // ... and its room skip fact (lights and planes do not animate)
+    float room_M = 0.f;
     std::string sig;
     hipEvent_t ev = nullptr;              // the last update
     // RTX_ANIM_OWN_STREAM=1: the updates run on the anim's own stream (high priority;
@@ -199,6 +201,8 @@ extern "C" int rtx_anim_create(rtx_anim** out, rtx_ctx* c, const rtx_scene* s, c
     a->split_ok = c->split_ok;
     a->spec = c->scene_spec;
     std::memcpy(a->room_p0, c->room_p0, sizeof a->room_p0);
+    a->room_fact = c->room_fact;
+    a->room_M = c->room_M;
     a->sig = c->scene_sig;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t id = static_cast<uint32_t>(ids[i]);
@@ -354,6 +358,8 @@ extern "C" int rtx_anim_update(rtx_anim* a, rtx_ctx* c, const float* transforms)
     c->split_ok = a->split_ok;
     c->scene_spec = a->spec;
     std::memcpy(c->room_p0, a->room_p0, sizeof c->room_p0);
+    c->room_fact = a->room_fact;
+    c->room_M = a->room_M;
     c->has_scene = true;
     ++c->scene_gen;
     c->scene_sig = a->sig;

@@ -55,6 +55,7 @@ extern "C" int rtx_create(rtx_ctx** out, int device_id) {
         c->sched_period = std::max<uint32_t>(1u, static_cast<uint32_t>(std::strtoul(e, nullptr, 10)));
     // RTX_SPLIT=0 renders heavy tiles in one piece; RTX_SPLIT=force splits every tile
     if (const char* e = std::getenv("RTX_NO_SPEC")) c->no_spec = std::strcmp(e, "0") != 0;
+    if (const char* e = std::getenv("RTX_ROOM_SKIP")) c->room_skip_off = std::strcmp(e, "0") == 0;
     if (const char* e = std::getenv("RTX_NO_CULL")) c->no_cull = std::strcmp(e, "0") != 0;
     if (const char* e = std::getenv("RTX_CULL_RATIO")) {
         const double v = std::atof(e);

@@ -185,6 +185,11 @@ struct rtx_ctx {
     size_t hstk_entries = 0;
     int scene_spec = 0;              // kSpec* facts of the uploaded scene (kernel specialisation)
     float room_p0[5] = {};           // kSpecRoomPlanes: plane k's origin on axis kRoomAxes[k]
+    // room skip (rtx_upload.hip, room_skip): every light strictly inside the room, and the bound on the
+    // shadow origins' plane distances; RTX_ROOM_SKIP=0: off (the fact is then reported false)
+    bool room_fact = false;
+    float room_M = 0.f;
+    bool room_skip_off = false;
     bool no_spec = false;            // RTX_NO_SPEC=1: always the generic kernel (tests)
     int last_facts = 0;              // rtx_spec_info: the facts and the kSpecVariants index (-1: the
     int last_variant = -1;           // generic kernel) of the last frame launched

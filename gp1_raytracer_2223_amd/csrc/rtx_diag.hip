@@ -115,6 +115,13 @@ extern "C" int rtx_spec_info(rtx_ctx* c, uint32_t* facts, int32_t* last_variant)
     return RTX_OK;
 }
 
+extern "C" int rtx_room_info(rtx_ctx* c, uint32_t* fact, float* room_M) {
+    if (!c) return RTX_E_INVALID;
+    if (fact) *fact = c->room_fact ? 1u : 0u;
+    if (room_M) *room_M = c->room_M;
+    return RTX_OK;
+}
+
 extern "C" int rtx_cull_dump(rtx_ctx* c, uint32_t anchor, uint32_t* n_slots, uint32_t* n_tris, float* anchor_p,
                              float* records, uint32_t* ranges, float* nodes, float* tris) {
     if (!c || anchor >= static_cast<uint32_t>(kMaxViews + kMaxCullLights)) return RTX_E_INVALID;

@@ -1252,9 +1252,45 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         // originOffset = hit.origin + hit.normal * 0.0001f (Renderer.cpp:126)
         const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
         const float vx = -dx, vy = -dy, vz = -dz;
+        // Room skip: a wave whose shadow origins all lie strictly inside the room, every light being
+        // strictly inside it too (the host's fact, rtx_upload.hip room_skip), runs no shadow-ray plane
+        // test, because the reference's own binary32 test (HitTest_Plane on Ray{o, d, 1e-4, tmax},
+        // l = RN(L - o) per component, tmax = |l| as computed, d = RN(l / tmax)) provably fails.
+        // Plane k, axis A, normal component s = +-1; exact alpha = s * (o_A - p0_A), exact margin
+        // m = s * (L_A - p0_A) >= mmin > 0; the lane condition is s * a < 0 for a = RN(p0_A - o_A) (the
+        // sign of a binary32 difference is exact: alpha > 0) and |a| <= M <= 2^20 * mmin; u = 2^-24.
+        //   * o is finite (|a| <= M), so the reference's num and den are s * a and s * d_A (room_a).
+        //     A hit needs t = RN(a / d_A) >= tmin > 0: d_A non-zero with s * d_A < 0.  d_A has the sign of
+        //     l_A (tmax > 0) and l_A that of the exact L_A - o_A, so s * (L_A - o_A) = m - alpha < 0 and
+        //     |L_A - o_A| = alpha - m: the ray approaches the plane, and the light lies before it.
+        //   * tmax = 0 makes d infinite and t = 0 < tmin; tmax = inf makes d_A = 0 and t infinite or
+        //     NaN.  Otherwise tmax is a positive float, whatever the rounding, underflow or contraction
+        //     in its sum of squares: d_A was divided by the same float that t is compared with.
+        //   * t < tmax fails when |a| >= |d_A| * tmax, RN being monotone and tmax a float.  |d_A| =
+        //     RN(|l_A| / tmax) <= (|l_A| / tmax)(1 + u) + 2^-150 (the second term: a denormal or zero
+        //     d_A), |l_A| <= (alpha - m)(1 + u) and |a| >= alpha (1 - u) (a denormal difference is
+        //     exact), so it suffices that
+        //         alpha (1 - u) - (alpha - m)(1 + u)^2 >= 2^-150 tmax,
+        //     whose left side is at least m - alpha (3u + u^2) >= m (1 - 2^20 (1 + 2u)(3u + u^2)) > 0.8 m,
+        //     since alpha <= |a| / (1 - u) <= 2^20 (1 + 2u) m: the roundings take 3/16 of m at 2^20.
+        //   * the right side: every axis B has a plane, so |L_B - o_B| <= (its margin) + (its alpha) <=
+        //     (2^20 + 2) mmax, and tmax <= sqrt(3)(1 + 3u)(2^20 + 2) mmax < 2^21 mmax (squares that
+        //     underflow only leave tmax < 2^-61, and m >= 2^-149 as a non-zero difference of floats).
+        //     The host's fact requires mmax <= 2^100 mmin, hence 2^-150 tmax < 2^-29 m.
+        // The lane condition is an interval per axis, found on the host by evaluating it (room_skip):
+        // the record behind the planes is {lo, M}, {hi, 0}, empty (lo = +inf, hi = -inf) when the fact
+        // does not hold, and a NaN or infinite coordinate fails the compares, so room_clear implies
+        // room_s's finiteness.  6 VALU per pixel for 15 plane tests in the headline.
+        bool room_clear = false;
+        if constexpr (kRoom && !COUNT && PHASE != 2 && !RTX_ABL_SPLANE) {
+            float4 q0, q1;
+            ldcb32(S.planes, 5 * 32u, q0, q1);
+            const bool inside = (q0.x < oox) & (oox < q1.x) & (q0.y < ooy) & (ooy < q1.y) & (q0.z < ooz) & (ooz < q1.z);
+            room_clear = (hitmask & ~ballot(inside)) == 0;
+        }
         // shadow rays start at originOffset for every light: one finiteness test for all of them
-        const bool room_s =
-            kRoom && PHASE != 2 && !RTX_ABL_SPLANE && (hitmask & ~ballot(finite3(oox, ooy, ooz))) == 0;
+        const bool room_s = kRoom && PHASE != 2 && !RTX_ABL_SPLANE && !room_clear &&
+                            (hitmask & ~ballot(finite3(oox, ooy, ooz))) == 0;
         for (uint32_t li = l_first; li < l_end; ++li) {
             float4 L0, L1;
             ldcb32(S.lights, opaque(li * 32u), L0, L1);
@@ -1299,9 +1335,10 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
                 // the same originOffset for every light: the first light computes it and keeps it
                 // in LDS, the others read it back (same value, bit for bit).  One loop version
                 // per case, so no per-plane select.
-                const uint32_t np = (RTX_ABL_SPLANE || PHASE == 2 || room_s) ? 0u : n_pl * 32u;
+                const uint32_t np = (RTX_ABL_SPLANE || PHASE == 2 || room_s || room_clear) ? 0u : n_pl * 32u;
                 const bool cache_ok = !COUNT && np <= static_cast<uint32_t>(kPlaneCache) * 32u;
-                if (room_s) {   // a / d (room_a): cheaper than the cached numerator
+                if (room_clear) {   // no room plane can occlude any light (room skip, above)
+                } else if (room_s) {   // a / d (room_a): cheaper than the cached numerator
                     for_room_planes([&](auto kc) {
                         constexpr int k = decltype(kc)::value;
                         constexpr int A = kRoomAxes[k];

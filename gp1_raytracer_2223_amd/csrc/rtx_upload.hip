@@ -3,6 +3,7 @@
 // Every float computed here that reaches a pixel restates the reference in binary32 (same flags as
 // the kernels: -ffp-contract=off).
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -91,6 +92,99 @@ bool build_parts(const std::vector<float4>& nodes, uint32_t root, uint32_t mesh,
     return true;
 }
 
+// the room's planes (kSpecRoomPlanes): normal +-1 on axis kRoomAxes[k], zero elsewhere,
+// origins finite within 2^64
+bool room_planes(const rtx_scene* s) {
+    bool room = s->n_planes == 5;
+    for (uint32_t i = 0; room && i < 5; ++i) {
+        const rtx_plane& p = s->planes[i];
+        for (int a = 0; a < 3; ++a) {
+            const float n = p.normal[a], o = p.origin[a];
+            room = room && (a == kRoomAxes[i] ? (n == 1.f || n == -1.f) : n == 0.f) && std::isfinite(o) &&
+                   std::fabs(o) <= 0x1p64f;
+        }
+    }
+    return room;
+}
+
+// binary32 values as integers in the floats' own order (-inf .. +inf, -0 below +0), and back
+inline uint32_t fkey(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline float fkey_inv(uint32_t k) { return bits((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// The room skip's host fact (render_tile's room_clear).  The five planes bound a convex
+// room; when every light lies strictly inside it, a shadow ray that starts strictly inside cannot meet
+// a room plane before its light.  The kernel may skip the reference's plane tests only where the
+// reference's own binary32 test provably fails, which render_tile's comment derives for a shadow
+// origin o with, for every plane k (axis A, normal component s = +-1, a_k = RN(p0_A - o_A)):
+//     s * a_k < 0   and   |a_k| <= M,   M = RD(2^20 * min margin),
+// the margin of light L at plane k being m_k(L) = s * (L_A - p0_A) (in double: the sign is exact, the
+// value within 2^-53, far inside the proof's slack), provided also max margin <= 2^100 * min margin
+// (the proof's bound on a denormal direction component).
+// Both conditions are monotone in o_A (RN(x - p0) is non-decreasing in x), so per axis they hold on an
+// interval of floats, whose open ends lo_A < o_A < hi_A are found here by bisection over the floats'
+// order, evaluating the very predicate: 6 compares per lane in the kernel instead of 5 differences,
+// 5 sign tests and 5 magnitude tests, and a NaN or infinite origin fails them.  When the fact does
+// not hold (or RTX_ROOM_SKIP=0) the interval is empty (lo = +inf, hi = -inf) and M = 0.
+struct RoomSkip {
+    bool fact = false;
+    float M = 0.f;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+};
+RoomSkip room_skip(const rtx_scene* s, bool room, bool off) {
+    RoomSkip r;
+    if (!room || off || s->n_lights == 0) return r;
+    double mmin = INFINITY, mmax = 0.0;
+    for (uint32_t i = 0; i < s->n_lights; ++i) {
+        if (s->lights[i].type != RTX_LIGHT_POINT) return r;
+        for (int k = 0; k < 5; ++k) {
+            const int A = kRoomAxes[k];
+            const double m = static_cast<double>(s->planes[k].normal[A]) *
+                             (static_cast<double>(s->lights[i].origin[A]) - static_cast<double>(s->planes[k].origin[A]));
+            if (!(std::isfinite(m) && m > 0.0)) return r;
+            mmin = std::fmin(mmin, m);
+            mmax = std::fmax(mmax, m);
+        }
+    }
+    if (!(mmax <= 0x1p100 * mmin)) return r;
+    const double Md = std::fmin(0x1p20 * mmin, static_cast<double>(FLT_MAX));
+    float M = static_cast<float>(Md);
+    if (static_cast<double>(M) > Md) M = std::nextafter(M, 0.f);   // rounded down
+    if (!(M > 0.f)) return r;
+    float lo[3] = {-INFINITY, -INFINITY, -INFINITY}, hi[3] = {INFINITY, INFINITY, INFINITY};
+    for (int k = 0; k < 5; ++k) {
+        const int A = kRoomAxes[k];
+        const float p0 = s->planes[k].origin[A];
+        const bool up = s->planes[k].normal[A] == 1.f;   // inside: o > p0 (else o < p0)
+        // |a_k| <= M as the kernel's binary32 difference would have it
+        auto near = [&](float o) {
+            const volatile float a = up ? o - p0 : p0 - o;
+            return a <= M;
+        };
+        // the float farthest from p0 on the inside that is still `near` (p0 itself is)
+        uint32_t in = fkey(p0), out = fkey(up ? INFINITY : -INFINITY);
+        while ((up ? out - in : in - out) > 1u) {
+            const uint32_t mid = up ? in + (out - in) / 2u : out + (in - out) / 2u;
+            (near(fkey_inv(mid)) ? in : out) = mid;
+        }
+        const float far = fkey_inv(out);   // the first float beyond it: an open end
+        if (up) {
+            lo[A] = std::fmax(lo[A], p0);
+            hi[A] = std::fmin(hi[A], far);
+        } else {
+            hi[A] = std::fmin(hi[A], p0);
+            lo[A] = std::fmax(lo[A], far);
+        }
+    }
+    r.fact = true;
+    r.M = M;
+    for (int a = 0; a < 3; ++a) { r.lo[a] = lo[a]; r.hi[a] = hi[a]; }
+    return r;
+}
+
 }  // namespace
 
 extern "C" int rtx_upload_scene(rtx_ctx* c, const rtx_scene* s) {
@@ -156,6 +250,14 @@ int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay) {
         if (p.material >= nm) return fail(c, RTX_E_INVALID, "plane material out of range");
         pl.push_back(f4(p.origin[0], p.origin[1], p.origin[2], bits(p.material)));
         pl.push_back(f4(p.normal[0], p.normal[1], p.normal[2], 0.f));
+    }
+    // the room skip's record behind the room's five planes (inside the section's padding, so no
+    // offset moves): {lo, M}, {hi, 0}
+    const bool room = room_planes(s);
+    const RoomSkip rs = room_skip(s, room, c->room_skip_off);
+    if (room) {
+        pl.push_back(f4(rs.lo[0], rs.lo[1], rs.lo[2], rs.M));
+        pl.push_back(f4(rs.hi[0], rs.hi[1], rs.hi[2], 0.f));
     }
     for (uint32_t mi = 0; mi < s->n_meshes; ++mi) {
         const rtx_mesh& m = s->meshes[mi];
@@ -509,18 +611,10 @@ int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay) {
         for (uint32_t i = 0; i < s->n_lights; ++i) point = point && s->lights[i].type == RTX_LIGHT_POINT;
         bool cull_back = true;   // kSpecCullBack: every mesh culls back faces
         for (uint32_t i = 0; i < s->n_meshes; ++i) cull_back = cull_back && s->meshes[i].cull_mode == RTX_CULL_BACK;
-        // the room's planes (kSpecRoomPlanes): normal +-1 on axis kRoomAxes[k], zero elsewhere,
-        // origins finite within 2^64
-        bool room = s->n_planes == 5;
-        for (uint32_t i = 0; room && i < 5; ++i) {
-            const rtx_plane& p = s->planes[i];
-            for (int a = 0; a < 3; ++a) {
-                const float n = p.normal[a], o = p.origin[a];
-                room = room && (a == kRoomAxes[i] ? (n == 1.f || n == -1.f) : n == 0.f) && std::isfinite(o) &&
-                       std::fabs(o) <= 0x1p64f;
-            }
-        }
+        // the room's planes (kSpecRoomPlanes, room_planes above) and the room skip's fact
         for (uint32_t i = 0; room && i < 5; ++i) c->room_p0[i] = s->planes[i].origin[kRoomAxes[i]];
+        c->room_fact = rs.fact;
+        c->room_M = rs.M;
         c->scene_spec = kinds | (point ? kSpecPoint : 0) | (s->n_spheres == 0 ? kSpecNoSpheres : 0) |
                         (s->n_planes == 5 ? kSpecFivePlanes : 0) | (s->n_meshes == 1 ? kSpecOneMesh : 0) |
                         (s->n_meshes == 0 ? kSpecNoMesh : 0) | (room ? kSpecRoomPlanes : 0) |

@@ -246,6 +246,12 @@ class DeviceContext:
         abi.check(self.lib.rtx_spec_info(self.h, C.byref(f), C.byref(v)), "rtx_spec_info", self.h)
         return f.value, v.value
 
+    def room_info(self) -> tuple[bool, float]:
+        """(the uploaded scene's room-skip fact, room_M: the bound on a shadow origin's plane distances)."""
+        f, m = C.c_uint32(), C.c_float()
+        abi.check(self.lib.rtx_room_info(self.h, C.byref(f), C.byref(m)), "rtx_room_info", self.h)
+        return bool(f.value), float(m.value)
+
     def count_work(self, cam, params) -> np.ndarray:
         out = (C.c_uint64 * 12)()
         abi.check(self.lib.rtx_count_work(self.h, C.byref(cam), C.byref(params), out), "rtx_count_work", self.h)

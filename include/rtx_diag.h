@@ -95,6 +95,13 @@ int rtx_cull_info(rtx_ctx* ctx, uint32_t* enabled, uint64_t* camera_updates);
  * BVH, RTX_NO_SPEC=1).  After an upload and before the next frame: the scene's facts and -1.  Host
  * bookkeeping at the launch site only. */
 int rtx_spec_info(rtx_ctx* ctx, uint32_t* facts, int32_t* last_variant);
+/* Room skip (no reference counterpart: shadow-ray room-plane tests the reference's own binary32
+ * arithmetic provably fails are not executed).  Reports the uploaded scene's fact (the
+ * five planes are the room, every light is a point light strictly inside it, and the light margins
+ * span at most 2^100) and room_M = RD(2^20 x the smallest light margin): a wave skips the tests when
+ * every shadow origin in it lies strictly inside the room within room_M of every plane.  Fact 0 and
+ * room_M 0 when it does not hold or RTX_ROOM_SKIP=0 (read at rtx_create) turned the skip off. */
+int rtx_room_info(rtx_ctx* ctx, uint32_t* fact, float* room_M);
 /* Diagnostics of the exact cull (tests): waits for the context stream, then copies the current
  * image's records of record copy `anchor` (view v < 8: its camera; 8 + l: light l) — n_slots x
  * 8 floats, {c, E.x}, {E.y, E.z, dt, flag bits} — and their inputs: per slot the triangle range
