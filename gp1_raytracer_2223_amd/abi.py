@@ -182,7 +182,7 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_render_aov_async", "rtx_render_aov", "rtx_download_aov", "rtx_gather_aov_async",
                "rtx_device_aov_buffers", "rtx_group_render_aov", "rtx_time_aov_frames",
                "rtx_trace_rays", "rtx_occluded", "rtx_trace_rays_device", "rtx_occluded_device",
-               "rtx_time_ray_queries", "rtx_room_info"]
+               "rtx_time_ray_queries", "rtx_room_info", "rtx_schedule_xcd_order"]
 
 
 def load_hip() -> C.CDLL:
@@ -271,6 +271,9 @@ def load_hip() -> C.CDLL:
             lib.rtx_schedule_state.argtypes = [VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
                                                C.POINTER(C.c_uint32)]
             lib.rtx_schedule_state.restype = C.c_int
+        if hasattr(lib, "rtx_schedule_xcd_order"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_schedule_xcd_order.argtypes = [VP, C.POINTER(C.c_uint32), C.c_uint32]
+            lib.rtx_schedule_xcd_order.restype = C.c_int
         if hasattr(lib, "rtx_group_create"):   # absent only in older experiment builds
             lib.rtx_gather_async.argtypes = [VP, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
             lib.rtx_gather_async.restype = C.c_int

@@ -101,6 +101,18 @@ extern "C" int rtx_schedule_state(rtx_ctx* c, uint32_t* order, uint32_t* cost, u
     return RTX_OK;
 }
 
+extern "C" int rtx_schedule_xcd_order(rtx_ctx* c, uint32_t* order, uint32_t n) {
+    if (!c || !order) return RTX_E_INVALID;
+    if (!c->xcd_order || !c->sched_ready || !c->d_order_xcd)
+        return fail(c, RTX_E_STATE, "the context has no XCD order (RTX_XCD_ORDER=1 and a measured frame)");
+    if (n > c->sched_cap) return fail(c, RTX_E_INVALID, "n exceeds the schedule size");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(order, c->d_order_xcd, n * 4, hipMemcpyDeviceToHost));
+    return RTX_OK;
+}
+
 extern "C" int rtx_cull_info(rtx_ctx* c, uint32_t* enabled, uint64_t* camera_updates) {
     if (!c) return RTX_E_INVALID;
     if (enabled) *enabled = c->dev.cull_stride ? 1u : 0u;

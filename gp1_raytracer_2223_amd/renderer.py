@@ -146,6 +146,13 @@ class DeviceContext:
         abi.check(self.lib.rtx_device_aov_buffers(self.h, C.byref(out)), "rtx_device_aov_buffers", self.h)
         return {k: C.cast(getattr(out, k), C.c_void_p).value or 0 for k in AOV_PLANES}
 
+    def device_buffers(self) -> tuple[int, int]:
+        """Device addresses (d_px, d_rgb) of the colour frame buffer (rtx_device_buffers; 0 for a plane
+        no frame has asked for yet).  A larger frame reallocates them: fetch them afresh."""
+        px, rgb = C.c_void_p(), C.c_void_p()
+        abi.check(self.lib.rtx_device_buffers(self.h, C.byref(px), C.byref(rgb)), "rtx_device_buffers", self.h)
+        return px.value or 0, rgb.value or 0
+
     @staticmethod
     def _rays(rays) -> np.ndarray:
         """(n, 8) float32 rows {origin, direction, tmin, tmax} (rtx_ray), C-contiguous."""

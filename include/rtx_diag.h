@@ -116,6 +116,11 @@ int rtx_cull_dump(rtx_ctx* ctx, uint32_t anchor, uint32_t* n_slots, uint32_t* n_
  * sorted by (`cost`).  *n_tiles = tiles of the current schedule (0 = none measured yet;
  * then nothing is copied). */
 int rtx_schedule_state(rtx_ctx* ctx, uint32_t* order, uint32_t* cost, uint32_t n, uint32_t* n_tiles);
+/* Diagnostics of the XCD-affine re-deal (tests): the first n slots of the permutation the render
+ * kernel consumes on a context created under RTX_XCD_ORDER=1, i.e. rtx_schedule_state's `order`
+ * re-dealt by rtx_sched_xcd.  RTX_E_STATE when the context has no XCD order (the knob is off, or no
+ * frame of the current schedule has been measured yet). */
+int rtx_schedule_xcd_order(rtx_ctx* ctx, uint32_t* order, uint32_t n);
 
 /* Diagnostics: 128 status words of the last update of registered mesh i (0-3 as above,
  * 4-6 subtrees / task-split ids / nodes split as tasks, 8-27 phase stamps of the device build

@@ -7,6 +7,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import devbuf
 import oracle_bind
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene, RENDERABLE
@@ -101,6 +102,8 @@ def test_cost_ordered_dispatch_is_output_invariant(gpu_ctx, name):
     gpu_ctx.upload(s)
     first, first_rgb = gpu_ctx.render(cam, p)
     for _ in range(3):
+        # the buffer still holds the first frame: a tile this frame skips must not read back as correct
+        devbuf.poison(gpu_ctx, p.width * p.height, rgb=True)
         px, rgb = gpu_ctx.render(cam, p)
         assert np.array_equal(px, first)
         assert np.array_equal(rgb.view(np.uint32), first_rgb.view(np.uint32))
@@ -138,8 +141,13 @@ def test_split_rendering(split_ctx, gpu_ctx, name, t, mode, shadows):
     split_ctx.render(cam, p)                      # measured frame: selects the heavy set
     heavy, parts = split_ctx.split_info()
     assert parts > 1 and heavy == 32 * 18, (heavy, parts)   # every 8x8 wave tile
+    # (the measured frame left the right pixels in the buffer: a heavy tile the split launches never
+    # write must not read back as correct)
+    devbuf.poison(split_ctx, p.width * p.height, rgb=True)
     spx, srgb = split_ctx.render(cam, p)          # rendered by the split launches
     gpu_ctx.upload(s)
+    gpu_ctx.render(cam, p)                        # (a frame of this shape: the poisoned range is allocated)
+    devbuf.poison(gpu_ctx, p.width * p.height, rgb=True)
     gpx, grgb = gpu_ctx.render(cam, p)
     assert np.array_equal(spx, gpx), f"{name}: {(spx != gpx).sum()} pixels differ from the one-piece kernel"
     assert np.array_equal(srgb.view(np.uint32), grgb.view(np.uint32))

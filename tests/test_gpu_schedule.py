@@ -51,3 +51,52 @@ def test_dispatch_order_is_stable_counting_sort(gpu_ctx, name, W, H, views):
     expect = np.lexsort((np.arange(ntiles), cls)).astype(np.uint32)   # by class, then tile index
     assert np.array_equal(order, expect)
     assert cost.max() > 0
+
+
+@pytest.fixture(scope="module")
+def xcd_ctx():
+    """A context that dispatches in the XCD-affine re-deal of the cost order (RTX_XCD_ORDER=1)."""
+    import os
+    from gp1_raytracer_2223_amd.renderer import DeviceContext
+    os.environ["RTX_XCD_ORDER"] = "1"
+    try:
+        ctx = DeviceContext(int(os.environ.get("RTX_TEST_DEVICE", "0")))
+    finally:
+        del os.environ["RTX_XCD_ORDER"]
+    yield ctx
+    ctx.close()
+
+
+# tiles_x, tiles_y, views (8 x 8 wave tiles): tests/test_xcd_model.py's shapes
+XCD_SHAPES = [(41, 33, 1), (41, 25, 1), (5, 4, 1), (12, 9, 3), (64, 16, 1), (1, 1, 1)]
+
+
+@pytest.mark.parametrize("tx,ty,views", XCD_SHAPES)
+def test_xcd_order_is_the_model_redeal_of_the_cost_order(xcd_ctx, gpu_ctx, tx, ty, views):
+    """rtx_sched_xcd's output, the permutation the render kernel consumes under RTX_XCD_ORDER=1, equals
+    the numpy model (tests/xcd_model.py) applied to the cost order of the same measured frame."""
+    import xcd_model
+    hs = HostScene("W4_Bunny")
+    s, cam = hs.view()
+    xcd_ctx.upload(s)
+    p = abi.make_params(8 * tx, 8 * ty)
+    cams = (abi.Camera * views)(*([cam] * views))
+    lib = xcd_ctx.lib
+    ntiles = tx * ty * views
+    got = np.full(ntiles, 0xDEADBEEF, np.uint32)
+    up = C.POINTER(C.c_uint32)
+    for _ in range(2):   # frame 1 measures; frame 2 runs in the re-dealt order
+        abi.check(lib.rtx_render_views_async(xcd_ctx.h, cams, views, C.byref(p), 0), "render", xcd_ctx.h)
+    xcd_ctx.synchronize()
+    order = np.zeros(ntiles, np.uint32)
+    cost = np.zeros(ntiles, np.uint32)
+    n = C.c_uint32()
+    abi.check(lib.rtx_schedule_state(xcd_ctx.h, order.ctypes.data_as(up), cost.ctypes.data_as(up), ntiles, C.byref(n)),
+              "schedule_state", xcd_ctx.h)
+    assert n.value >= ntiles
+    assert np.array_equal(np.sort(order), np.arange(ntiles, dtype=np.uint32)), "the cost order is not a permutation"
+    abi.check(lib.rtx_schedule_xcd_order(xcd_ctx.h, got.ctypes.data_as(up), ntiles), "schedule_xcd_order", xcd_ctx.h)
+    assert np.array_equal(np.sort(got), np.arange(ntiles, dtype=np.uint32)), "the XCD order is not a permutation"
+    assert np.array_equal(got, xcd_model.redeal(order, tx, ty))
+    # a context without the knob has no XCD order
+    assert lib.rtx_schedule_xcd_order(gpu_ctx.h, got.ctypes.data_as(up), 1) == abi.RTX_E_STATE
