@@ -288,14 +288,7 @@ extern "C" int rtx_anim_update(rtx_anim* a, rtx_ctx* c, const float* transforms)
         ANIM_TRY(a, hipEventSynchronize(B.done));
         B.pending = false;
     }
-    if (a->total > B.cap) {
-        (void)hipFree(B.d);
-        if (B.h) (void)hipHostFree(B.h);
-        B.d = nullptr; B.h = nullptr; B.cap = 0;
-        ANIM_TRY(a, hipMalloc(&B.d, a->total));
-        ANIM_TRY(a, hipHostMalloc(&B.h, a->total));
-        B.cap = a->total;
-    }
+    if (a->total > B.cap) ANIM_TRY(a, B.grow(a->total));
     // (image B's earlier renders on this context have completed: B.done above)
     hipStream_t s = a->stream ? a->stream : c->stream;
     if (a->built) ANIM_TRY(a, hipStreamWaitEvent(s, a->ev, 0));

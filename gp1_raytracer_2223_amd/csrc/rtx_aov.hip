@@ -10,10 +10,8 @@ namespace {
 
 // One more plane of `n` elements of `elem` bytes (the frames queued on the stream may still write the old one).
 template <class T>
-int aov_alloc(rtx_ctx* c, T*& d, size_t n, size_t elem) {
-    if (d) return RTX_OK;
-    HIP_TRY(c, hipMalloc(&d, n * elem));
-    return RTX_OK;
+int aov_alloc(rtx_ctx* c, DevBuf<T>& d, size_t n, size_t elem) {
+    return d ? RTX_OK : d.grow(c, n, elem);
 }
 
 // Checks, the planes of `mask` and the launch record of a pass; nothing of the colour frames' state
@@ -40,10 +38,8 @@ int aov_prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rende
                     (c->d_aov_material ? RTX_AOV_MATERIAL : 0u) | (c->d_aov_primitive ? RTX_AOV_PRIMITIVE : 0u);
     if (npx > c->aov_cap) {   // larger planes: all of them again, at the new size
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_aov_depth); (void)hipFree(c->d_aov_normal);
-        (void)hipFree(c->d_aov_material); (void)hipFree(c->d_aov_primitive);
-        c->d_aov_depth = c->d_aov_normal = nullptr;
-        c->d_aov_material = c->d_aov_primitive = nullptr;
+        c->d_aov_depth.free(); c->d_aov_normal.free();
+        c->d_aov_material.free(); c->d_aov_primitive.free();
         c->aov_last_mask = 0;   // (their contents are gone)
         c->aov_cap = npx;
     }
@@ -97,10 +93,10 @@ int queue_aov_copy(rtx_ctx* c, const rtx_aov_planes* out) {
                                         ") did not write every plane asked for (mask " + std::to_string(want) + ")");
     HIP_TRY(c, hipSetDevice(c->device));
     const CopyPlane planes[4] = {
-        {reinterpret_cast<char*>(out->depth), reinterpret_cast<const char*>(c->d_aov_depth), 4},
-        {reinterpret_cast<char*>(out->normal), reinterpret_cast<const char*>(c->d_aov_normal), 12},
-        {reinterpret_cast<char*>(out->material), reinterpret_cast<const char*>(c->d_aov_material), 4},
-        {reinterpret_cast<char*>(out->primitive), reinterpret_cast<const char*>(c->d_aov_primitive), 4}};
+        {reinterpret_cast<char*>(out->depth), reinterpret_cast<const char*>(c->d_aov_depth.get()), 4},
+        {reinterpret_cast<char*>(out->normal), reinterpret_cast<const char*>(c->d_aov_normal.get()), 12},
+        {reinterpret_cast<char*>(out->material), reinterpret_cast<const char*>(c->d_aov_material.get()), 4},
+        {reinterpret_cast<char*>(out->primitive), reinterpret_cast<const char*>(c->d_aov_primitive.get()), 4}};
     return queue_rows(c, c->aov_last, c->aov_last_views, planes, 4);
 }
 

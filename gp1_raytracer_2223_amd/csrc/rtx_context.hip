@@ -38,15 +38,15 @@ extern "C" int rtx_create(rtx_ctx** out, int device_id) {
     c->device = device_id;
     // RTX_TILE_ORDER=0 disables cost-ordered tile dispatch (identity order every frame)
     if (const char* e = std::getenv("RTX_TILE_ORDER")) c->sched_enabled = std::strcmp(e, "0") != 0;
-    if (const char* e = std::getenv("RTX_MOTION")) c->motion_off = std::strcmp(e, "0") == 0;
+    if (const char* e = std::getenv("RTX_MOTION")) c->motion.off = std::strcmp(e, "0") == 0;
     if (const char* e = std::getenv("RTX_XCD_ORDER")) c->xcd_order = std::strcmp(e, "1") == 0;
     if (const char* e = std::getenv("RTX_THROUGHPUT")) c->throughput_off = std::strcmp(e, "0") == 0;
-    if (const char* e = std::getenv("RTX_REFINE")) c->refine_off = std::strcmp(e, "0") == 0;
-    if (const char* e = std::getenv("RTX_DEFER_JOIN")) c->join_off = std::strcmp(e, "0") == 0;
+    if (const char* e = std::getenv("RTX_REFINE")) c->refine.off = std::strcmp(e, "0") == 0;
+    if (const char* e = std::getenv("RTX_DEFER_JOIN")) c->join.off = std::strcmp(e, "0") == 0;
     if (const char* e = std::getenv("RTX_DEFER_INFLIGHT")) c->defer_inflight = std::strcmp(e, "0") != 0;
-    if (const char* e = std::getenv("RTX_REFINE_ROUNDS")) c->refine_rounds = static_cast<uint32_t>(std::atoi(e));
-    if (const char* e = std::getenv("RTX_REFINE_SPLITS")) c->refine_splits = static_cast<uint32_t>(std::atoi(e));
-    if (const char* e = std::getenv("RTX_REFINE_TOP")) c->refine_top = static_cast<uint32_t>(std::atoi(e));
+    if (const char* e = std::getenv("RTX_REFINE_ROUNDS")) c->refine.rounds = static_cast<uint32_t>(std::atoi(e));
+    if (const char* e = std::getenv("RTX_REFINE_SPLITS")) c->refine.splits = static_cast<uint32_t>(std::atoi(e));
+    if (const char* e = std::getenv("RTX_REFINE_TOP")) c->refine.top = static_cast<uint32_t>(std::atoi(e));
     if (const char* e = std::getenv("RTX_INFLIGHT_CRIT")) {
         const double f = std::atof(e);
         if (f >= 0 && f < 1e6) c->inflight_crit = static_cast<uint32_t>(f * 1000.0);
@@ -80,9 +80,9 @@ extern "C" int rtx_create(rtx_ctx** out, int device_id) {
     }
     if (const char* e = std::getenv("RTX_SPLIT_FACTOR")) {
         const double f = std::atof(e);
-        if (f > 0 && f < 1e6) { c->split_permille = static_cast<uint32_t>(f * 1000.0); c->tune_on = false; }
+        if (f > 0 && f < 1e6) { c->tuner.permille = static_cast<uint32_t>(f * 1000.0); c->tuner.on = false; }
     }
-    if (const char* e = std::getenv("RTX_SPLIT_TUNE")) c->tune_on = c->tune_on && std::strcmp(e, "0") != 0;
+    if (const char* e = std::getenv("RTX_SPLIT_TUNE")) c->tuner.on = c->tuner.on && std::strcmp(e, "0") != 0;
     if (const char* e = std::getenv("RTX_SPLIT_MIN_US")) {
         const double us = std::atof(e);
         if (us >= 0 && us < 1e6) c->split_min = static_cast<uint32_t>(us * kSplitMinCost / kSplitMinUs);
@@ -102,28 +102,23 @@ extern "C" int rtx_create(rtx_ctx** out, int device_id) {
     RTX_CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     RTX_CREATE_TRY(hipEventCreate(&c->ev0));
     RTX_CREATE_TRY(hipEventCreate(&c->ev1));
-    RTX_CREATE_TRY(hipEventCreateWithFlags(&c->ev_heavy, hipEventDisableTiming));
-    RTX_CREATE_TRY(hipEventCreateWithFlags(&c->sb[0].done, hipEventDisableTiming));
-    RTX_CREATE_TRY(hipEventCreateWithFlags(&c->sb[1].done, hipEventDisableTiming));
-    RTX_CREATE_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    RTX_CREATE_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    RTX_CREATE_TRY(hipEventCreateWithFlags(&c->ev_frame, hipEventDisableTiming));
+    for (hipEvent_t* e : {&c->ev_heavy, &c->sb[0].done, &c->sb[1].done, &c->ev_fork, &c->ev_join, &c->ev_frame})
+        RTX_CREATE_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     for (auto& e : c->ev_tune) RTX_CREATE_TRY(hipEventCreate(&e));
     for (auto& e : c->ev_win) RTX_CREATE_TRY(hipEventCreate(&e));
     RTX_CREATE_TRY(hipEventCreateWithFlags(&c->ev_refine, hipEventDisableTiming));
     RTX_CREATE_TRY(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
     if (const char* e = std::getenv("RTX_SPLIT_PRIO"); e && std::strcmp(e, "0") == 0) hi_prio = lo_prio;
     RTX_CREATE_TRY(hipStreamCreateWithPriority(&c->split_stream, hipStreamNonBlocking, hi_prio));
-    RTX_CREATE_TRY(hipMalloc(&c->d_counters, sizeof(unsigned long long) * kNumCounters));
+    RTX_CREATE_TRY(c->d_counters.alloc(kNumCounters));
     // {heavy tiles, max tile cost (rtx_sched_count), max tile cost, cost per wave slot (rtx_sched_scan)}
-    RTX_CREATE_TRY(hipMalloc(&c->d_heavy_n, 16));
+    RTX_CREATE_TRY(c->d_heavy_n.alloc(4));
     RTX_CREATE_TRY(hipMemset(c->d_heavy_n, 0, 16));
-    RTX_CREATE_TRY(hipMalloc(&c->d_thr, 8));
+    RTX_CREATE_TRY(c->d_thr.alloc(1));
     RTX_CREATE_TRY(hipHostMalloc(&c->h_heavy_n, 16));
-    RTX_CREATE_TRY(hipMalloc(&c->d_heavy_list[0], 4 * kMaxHeavyTiles));
-    RTX_CREATE_TRY(hipMalloc(&c->d_heavy_list[1], 4 * kMaxHeavyTiles));
-    RTX_CREATE_TRY(hipMalloc(&c->d_hit_key, 8 * heavy_px));
-    RTX_CREATE_TRY(hipMalloc(&c->d_occ, 4 * heavy_px));
+    for (auto& l : c->d_heavy_list) RTX_CREATE_TRY(l.alloc(kMaxHeavyTiles));
+    RTX_CREATE_TRY(c->d_hit_key.alloc(heavy_px));
+    RTX_CREATE_TRY(c->d_occ.alloc(heavy_px));
     RTX_CREATE_TRY(hipMemset(c->d_hit_key, 0xff, 8 * heavy_px));
     RTX_CREATE_TRY(hipMemset(c->d_occ, 0, 4 * heavy_px));
     // (null-stream memsets are asynchronous to the host and the context's non-blocking streams do
@@ -143,52 +138,18 @@ extern "C" void rtx_destroy(rtx_ctx* c) {
     if (!c) return;
     frames_forget(c);
     (void)hipSetDevice(c->device);
-    if (c->split_stream) (void)hipStreamSynchronize(c->split_stream);   // (a deferred chain, join_pending)
+    if (c->split_stream) (void)hipStreamSynchronize(c->split_stream);   // (a deferred chain, rtx_ctx::join)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& B : c->sb) {
-        (void)hipFree(B.d);
-        (void)hipFree(B.cull);
-        if (B.h) (void)hipHostFree(B.h);
+        B.free();
+        B.cull.free();
         if (B.done) (void)hipEventDestroy(B.done);
     }
-    (void)hipFree(c->d_px);
-    (void)hipFree(c->d_rgb);
-    (void)hipFree(c->d_aov_depth);
-    (void)hipFree(c->d_aov_normal);
-    (void)hipFree(c->d_aov_material);
-    (void)hipFree(c->d_aov_primitive);
-    (void)hipFree(c->d_query);
-    (void)hipFree(c->d_counters);
-    (void)hipFree(c->d_order);
-    (void)hipFree(c->d_order_xcd);
-    (void)hipFree(c->d_cost);
-    (void)hipFree(c->d_saved_cost);
-    (void)hipFree(c->d_hist);
-    (void)hipFree(c->d_csum);
-    (void)hipFree(c->d_thr);
-    for (int k = 0; k < 2; ++k) { (void)hipFree(c->d_heavy_flag[k]); (void)hipFree(c->d_heavy_list[k]); }
-    (void)hipFree(c->d_heavy_n);
+    for (DevMem* b : c->bufs) b->free();
     if (c->h_heavy_n) (void)hipHostFree(c->h_heavy_n);
-    (void)hipFree(c->d_hit_key);
-    (void)hipFree(c->d_occ);
-    (void)hipFree(c->d_lm_rec);
-    (void)hipFree(c->d_lm_mask);
-    (void)hipFree(c->d_hstk);
-    (void)hipFree(c->d_hstkT);
-    (void)hipFree(c->d_cull_btree);
-    (void)hipFree(c->d_cull_mtree);
-    (void)hipFree(c->d_cull_nbox);
-    (void)hipFree(c->d_cull_arrive);
-    if (c->ev_heavy) (void)hipEventDestroy(c->ev_heavy);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_frame) (void)hipEventDestroy(c->ev_frame);
-    for (auto& e : c->ev_tune)
+    for (hipEvent_t e : {c->ev_heavy, c->ev_fork, c->ev_join, c->ev_frame, c->ev_tune[0], c->ev_tune[1], c->ev_tune[2],
+                         c->ev_win[0], c->ev_win[1], c->ev_refine})
         if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_win)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_refine) (void)hipEventDestroy(c->ev_refine);
-    (void)hipFree(c->d_part_max);
     if (c->split_stream) {
         (void)hipStreamSynchronize(c->split_stream);
         (void)hipStreamDestroy(c->split_stream);

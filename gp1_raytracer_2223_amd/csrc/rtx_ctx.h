@@ -1,9 +1,10 @@
 // rtx_ctx.h — the render context (rtx_ctx, the opaque handle of include/rtx.h) and what the host
-// units of librtx_hip.so call across each other (namespace rtxh): the frame policies of
-// rtx_policy.hip (the split tuner, the throughput / in-flight choice, the frontier refinement and
-// the deferred join of the split chain), the upload (rtx_upload.hip), the cull records
-// (rtx_cull_records.hip), the tile schedule (rtx_sched.hip) and the frame (rtx_frame.hip).  The
-// render kernel's launches are rtx_launch.h's.  Internal to librtx_hip.so.
+// units of librtx_hip.so call across each other (namespace rtxh): the frame policies (their state
+// and pure transitions are rtx_policy.h's structs, one per policy; rtx_policy.hip makes their HIP
+// calls: the split tuner, the throughput / in-flight choice, the frontier refinement and the
+// deferred join of the split chain), the context's device buffers (DevBuf), the upload
+// (rtx_upload.hip), the cull records (rtx_cull_records.hip), the tile schedule (rtx_sched.hip) and
+// the frame (rtx_frame.hip).  The render kernel's launches are rtx_launch.h's.  Internal to librtx_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "rtx_diag.h"
 #include "rtx_cull.h"
 #include "rtx_kernels.h"
+#include "rtx_policy.h"
 
 using namespace rtxd;
 
@@ -30,7 +32,36 @@ struct alignas(16) CullBox {
     float lo[3], pad0, hi[3], pad1;
 };
 
+static_assert(kPolicyMaxViews == kMaxViews, "rtx_policy.h's cameras per frame");
+
+// A device buffer: its pointer and the units (elements, unless grow is told another size) it holds.
+// One constructed with rtx_ctx::bufs is the context's: rtx_destroy frees every one of those.  Explicit
+// lifetime, no destructor: a free needs the context's device current.
+struct DevMem {
+    void* p = nullptr;
+    size_t cap = 0;
+    void free() { (void)hipFree(p); p = nullptr; cap = 0; }
+};
+template <class T>
+struct DevBuf : DevMem {
+    DevBuf() = default;   // (a scene image's own: rtx_ctx::SceneBuf)
+    explicit DevBuf(std::vector<DevMem*>& owner) { owner.push_back(this); }
+    DevBuf(const DevBuf&) = delete;
+    T* get() const { return static_cast<T*>(p); }
+    operator T*() const { return get(); }
+    // Free the buffer and allocate it again for `need` units of `elem` bytes (cap 0 when the allocation
+    // fails).  No synchronisation: the caller has made sure that nothing queued still reads the old one.
+    int grow(rtx_ctx* c, size_t need, size_t elem = sizeof(T));
+    hipError_t alloc(size_t need, size_t elem = sizeof(T)) {   // ... with HIP's own error (for rtx_create's report)
+        free();
+        const hipError_t e = hipMalloc(&p, need * elem);
+        if (e == hipSuccess) cap = need;
+        return e;
+    }
+};
+
 struct rtx_ctx {
+    std::vector<DevMem*> bufs;   // every DevBuf below (first: they register as they are constructed)
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -45,8 +76,20 @@ struct rtx_ctx {
         size_t cap = 0;
         hipEvent_t done = nullptr;   // recorded after the last frame that reads this image
         bool pending = false;
-        float4* cull = nullptr;      // the image's cull records (DevScene::cull), device only
-        size_t cull_cap = 0;
+        DevBuf<float4> cull;         // the image's cull records (DevScene::cull), device only; cap in bytes
+        void free() {                // (the image and its staging: explicit, like DevBuf's)
+            (void)hipFree(d);
+            if (h) (void)hipHostFree(h);
+            d = h = nullptr;
+            cap = 0;
+        }
+        hipError_t grow(size_t total) {
+            free();
+            hipError_t e = hipMalloc(&d, total);
+            if (e == hipSuccess) e = hipHostMalloc(&h, total);
+            if (e == hipSuccess) cap = total;
+            return e;
+        }
     };
     SceneBuf sb[2];
     int sb_cur = -1;
@@ -55,34 +98,33 @@ struct rtx_ctx {
     DevScene dev{};
     bool has_scene = false;
     // frame buffer in HBM
-    uint32_t* d_px = nullptr;
-    float* d_rgb = nullptr;
-    size_t px_cap = 0, rgb_cap = 0;
+    DevBuf<uint32_t> d_px{bufs};
+    DevBuf<float> d_rgb{bufs};   // 3 floats a pixel
     // supersampling (rtx_set_supersample): log2 of the k x k samples per pixel of every later frame;
     // the frame buffer stays width x height per view (FrameArgs::ss_log2)
     uint32_t ss_log2 = 0;
-    unsigned long long* d_counters = nullptr;
+    DevBuf<unsigned long long> d_counters{bufs};
     // last render
     // cost-ordered tile dispatch
-    uint32_t* d_order = nullptr;
-    uint32_t* d_order_xcd = nullptr;    // the XCD-affine re-deal of d_order (rtx_sched_xcd)
-    bool xcd_order = false;             // RTX_XCD_ORDER=1
-    uint32_t* d_cost = nullptr;
-    uint32_t* d_saved_cost = nullptr;   // last one-piece cost per tile
-    uint32_t* d_hist = nullptr;         // per (class, chunk) tile counts -> slot bases (rtx_sched_*)
-    unsigned long long* d_csum = nullptr;   // per chunk cost sums
-    unsigned long long* d_thr = nullptr;    // heavy threshold of the measured frame
-    uint32_t sched_cap = 0;
+    DevBuf<uint32_t> d_order{bufs};
+    DevBuf<uint32_t> d_order_xcd{bufs};   // the XCD-affine re-deal of d_order (rtx_sched_xcd)
+    bool xcd_order = false;               // RTX_XCD_ORDER=1
+    DevBuf<uint32_t> d_cost{bufs};
+    DevBuf<uint32_t> d_saved_cost{bufs};  // last one-piece cost per tile
+    DevBuf<uint32_t> d_hist{bufs};        // per (class, chunk) tile counts -> slot bases (rtx_sched_*)
+    DevBuf<unsigned long long> d_csum{bufs};   // per chunk cost sums
+    DevBuf<unsigned long long> d_thr{bufs};    // heavy threshold of the measured frame
+    uint32_t sched_cap = 0;               // tiles the schedule arrays and d_heavy_flag hold (set once all have grown)
     std::string sched_key;
     bool sched_ready = false;
     bool sched_enabled = true;
     uint64_t sched_frame = 0;
     uint64_t scene_gen = 0;
-    // split rendering of heavy tiles: double-buffered flag/list sets (the reorder kernel
-    // fills the staging set; the host adopts it, with its count, at the next frame)
-    uint32_t* d_heavy_flag[2] = {nullptr, nullptr};
-    uint32_t* d_heavy_list[2] = {nullptr, nullptr};
-    uint32_t* d_heavy_n = nullptr;
+    // split rendering of heavy tiles: double-buffered flag/list sets (HeavySet)
+    DevBuf<uint32_t> d_heavy_flag[2] = {DevBuf<uint32_t>{bufs}, DevBuf<uint32_t>{bufs}};
+    DevBuf<uint32_t> d_heavy_list[2] = {DevBuf<uint32_t>{bufs}, DevBuf<uint32_t>{bufs}};
+    DevBuf<uint32_t> d_heavy_n{bufs};
+    rtxh::HeavySet heavy;
     uint32_t* h_heavy_n = nullptr;   // pinned
     hipEvent_t ev_heavy = nullptr;
     hipStream_t split_stream = nullptr;   // split launches run beside the main kernel
@@ -100,89 +142,38 @@ struct rtx_ctx {
     // serialized measurement (cost units), the threshold (RTX_INFLIGHT_CRIT), and whether the last
     // frame rendered one piece because of it
     uint32_t max_cost_serial = 0;
-    // deferred join (rtx_ctx::join_pending): the last frame's split chain has not been joined into the
-    // frame stream; the next frame's main kernel may start beside it when it repeats the frame exactly
-    // (same parameters, cameras, scene image and heavy set: the two write disjoint tiles) — anything
-    // else joins first (join_split).  join_*: that frame's identity.
-    bool join_pending = false;
-    bool join_off = false;                      // RTX_DEFER_JOIN=0
+    rtxh::DeferredJoin join;                    // the deferred join of the last frame's split chain (join_split)
     // frames in flight defer too, except while the in-flight overlap window is timed (RTX_DEFER_INFLIGHT=0: never)
     bool defer_inflight = true;
-    rtx_render_params join_p{};
-    rtx_camera join_cams[kMaxViews]{};
-    int join_views = 0;
-    uint64_t join_gen = 0;
-    int join_sb = -1;
-    uint32_t join_ss = 0;
-    const uint32_t* join_heavy = nullptr;
-    uint32_t join_heavy_n = 0;
-    // the split frames' interval in flight on this context's stream (inflight_onepiece): 0 skipping
-    // kInflightWindowSkip frames, 2 timing kInflightWindow frames, 3 waiting for the end event, 4 done
-    uint32_t win_state = 0;
-    uint32_t win_frames = 0;
-    int win_rec = -1;                           // the ev_win slot this frame's end records (-1 none)
-    float win_interval_ms = 0.f;
+    rtxh::InflightWindow window;                // the split frames' interval in flight (inflight_onepiece)
     hipEvent_t ev_win[2] = {};
     uint32_t inflight_crit = kInflightCritPermille;
     bool frame_onepiece = false;
-    int heavy_cur = 0;
-    uint32_t heavy_n = 0;
-    bool heavy_pending = false;
     uint32_t split_mode = 1;         // 0 off, 1 auto, 2 force (RTX_SPLIT=0 / unset / force)
     uint32_t split_slots = 0;        // concurrent render waves on this device
-    uint32_t split_permille = kSplitPermille;   // RTX_SPLIT_FACTOR (fixes it: no tuner)
     uint32_t split_min = kSplitMinCost;         // RTX_SPLIT_MIN_US: the least cost (16-cycle units) a split tile has
-    // Split-threshold tuner: the frame is max(main kernel, split chain), and the
-    // threshold that balances the two is the fastest (Synthetic100k: factor 2.0, W4_Optional 1.5).
-    // A measured frame with split tiles times both (ev_tune: fork, main kernel end, chain end); at
-    // its adoption the factor the timed set was selected with moves toward the balance, by steps
-    // that shrink when the direction flips, until the two are within 4 % or the step is < 1.5 %.
-    bool tune_on = true;                        // RTX_SPLIT_TUNE=0 / RTX_SPLIT_FACTOR: off
-    bool tune_done = false;
-    bool tune_rec = false;                      // the measured frame in flight recorded ev_tune
-    uint32_t tune_rec_permille = 0;             // ... and the factor its (current) heavy set was selected with
-    uint32_t set_permille[2] = {0, 0};          // per heavy set: the factor the schedule selected it with
-    uint32_t tune_steps = 0;
-    int tune_dir = 0;
-    float tune_step = 1.15f;
-    float tune_main_ms = 0.f, tune_chain_ms = 0.f;   // the last timed frame (rtx_split_tune_info)
-    float tune_best_span = 0.f;                 // the fastest max(main, chain) seen, and its factor
-    uint32_t tune_best_permille = 0;
+    rtxh::SplitTuner tuner;                     // the split factor and its tuner
     hipEvent_t ev_tune[3] = {nullptr, nullptr, nullptr};
     uint32_t sched_period = kSchedPeriod;       // RTX_SCHED_PERIOD (tuning)
-    // motion mode (kMotionFrames): frames left, and the previous frame's cameras it compares
-    uint32_t motion_left = 0;
+    rtxh::Motion motion;                        // motion mode (kMotionFrames)
     bool frame_motion = false;                  // the frame being prepared / launched is in motion mode
-    bool motion_off = false;                    // RTX_MOTION=0: always the static schedule (A/B)
-    int prev_views = 0;
-    ViewCam prev_cam[kMaxViews] = {};
     uint32_t split_parts = kPartsPerMesh;            // RTX_SPLIT_PARTS (tuning)
     // frontier refinement (kRefineRounds): the current image's parts (host copy of the real entries;
-    // the image reserves kMaxParts), its parts section, the round and state (0 waiting for a split
-    // frame, 1 measured frame queued, 2 done), frames to wait, the last round's longest part wave
+    // the image reserves kMaxParts), its parts section, and the rounds' state
     bool refinable = false;
-    bool refine_off = false;                         // RTX_REFINE=0
-    // RTX_REFINE_ROUNDS / _SPLITS / _TOP (permille): the kRefine* constants (tuning)
-    uint32_t refine_rounds = kRefineRounds, refine_splits = kRefineSplits, refine_top = kRefineTopPermille;
+    rtxh::Refinement refine;
     std::vector<int4> h_parts;
     std::vector<int4> h_parts_base;                  // the upload's frontier (each launch shape starts from it)
     int4* parts_dev = nullptr;
-    uint32_t refine_round = 0;
-    int refine_state = 2;
-    uint32_t refine_wait = 0;
-    uint32_t refine_quiet = 0;                       // frames of this shape still to wait
-    uint32_t refine_prev_max = 0;
-    bool refine_rec = false;
     hipEvent_t ev_refine = nullptr;
-    uint32_t* d_part_max = nullptr;
+    DevBuf<uint32_t> d_part_max{bufs};
     std::vector<uint32_t> h_part_max;
     bool split_ok = false;           // the uploaded scene admits split rendering
     bool deep_stack = false;         // the uploaded scene needs rtx_render_kernel<..., DEEP = true>
     bool hbm_stack = false;          // ... with its stacks in HBM (HSTK = true): kStackDepthDeep or more levels
     uint32_t max_depth = 0;          // deepest BVH level of the uploaded scene
-    uint4* d_hstk = nullptr;         // the HBM stacks (and the instrumented variant's masks), grown on demand
-    unsigned long long* d_hstkT = nullptr;
-    size_t hstk_entries = 0;
+    DevBuf<uint4> d_hstk{bufs};      // the HBM stacks (and the instrumented variant's masks), grown on demand
+    DevBuf<unsigned long long> d_hstkT{bufs};
     int scene_spec = 0;              // kSpec* facts of the uploaded scene (kernel specialisation)
     float room_p0[5] = {};           // kSpecRoomPlanes: plane k's origin on axis kRoomAxes[k]
     // room skip (rtx_upload.hip, room_skip): every light strictly inside the room, and the bound on the
@@ -193,17 +184,16 @@ struct rtx_ctx {
     bool no_spec = false;            // RTX_NO_SPEC=1: always the generic kernel (tests)
     int last_facts = 0;              // rtx_spec_info: the facts and the kSpecVariants index (-1: the
     int last_variant = -1;           // generic kernel) of the last frame launched
-    unsigned long long* d_hit_key = nullptr;
-    uint32_t* d_occ = nullptr;
+    DevBuf<unsigned long long> d_hit_key{bufs};
+    DevBuf<uint32_t> d_occ{bufs};
     // Light-major frames (FrameArgs::lm_*, DESIGN.md §6, opt-in): lm_mode 0 never (default), 1 auto
     // (RTX_LIGHT_MAJOR=auto: a launch of at most lm_tiles wave tiles, kLmSlotsPercent of the resident
     // wave slots, RTX_LIGHT_MAJOR_TILES), 2 always (RTX_LIGHT_MAJOR=1)
     uint32_t lm_mode = 0;
     uint32_t lm_tiles = 0;
     uint32_t lm_waves = 0;                      // PHASE 5's persistent waves: every resident slot (32 per CU)
-    float4* d_lm_rec = nullptr;                 // 2 float4 per tile pixel
-    unsigned long long* d_lm_mask = nullptr;    // per (tile, light)
-    size_t lm_rec_tiles = 0, lm_mask_cap = 0;
+    DevBuf<float4> d_lm_rec{bufs};              // 2 float4 per tile pixel; cap in tiles
+    DevBuf<unsigned long long> d_lm_mask{bufs}; // per (tile, light)
     bool frame_lm = false;                      // the frame being launched is light-major
     // exact cull (DevScene::cull): on for host uploads (RTX_NO_CULL=1: off); the
     // scratch of its record launches (the segment trees of the per-triangle boxes and of each
@@ -221,10 +211,6 @@ struct rtx_ctx {
     bool cull_animated = true;
     uint32_t renders_since_upload = 0;
     uint32_t short_uploads = 0;
-    // An upload in that pattern (the previous upload was rendered at most once too) moves the
-    // geometry under a fixed tile schedule as a moving camera does: the next frame starts motion
-    // mode when the scene has split tiles (prepare; RTX_MOTION=0 turns both off).
-    bool upload_motion = false;
     // The cull's worth estimate (upload_scene: the surface areas of every node's reference box and
     // tight box, tens of us of host time per upload) is reused by the uploads of such a loop for
     // kCullWorthReuse uploads while the scene's counts stay the same: the decision only picks the
@@ -232,14 +218,12 @@ struct rtx_ctx {
     int cull_worth = -1;
     uint32_t cull_worth_age = 0;
     std::string cull_worth_sig;
-    CullBox* d_cull_btree = nullptr;      // 2n entries
-    CullMD* d_cull_mtree = nullptr;       // 2n entries per anchor of one launch
-    size_t cull_mtree_cap = 0;            // entries d_cull_mtree holds
+    DevBuf<CullBox> d_cull_btree{bufs};   // 2n entries; cap = the leaves n it holds
+    DevBuf<CullMD> d_cull_mtree{bufs};    // 2n entries per anchor of one launch
     uint32_t cull_failures = 0;           // record builds that failed (the image then renders unculled)
     uint32_t cull_fail_at = 0, cull_launches = 0;   // RTX_CULL_FAIL=k: the k-th record build fails (tests)
-    CullBox* d_cull_nbox = nullptr;       // per node slot of the current image
-    uint32_t* d_cull_arrive = nullptr;    // per tree (kCullMaxAnchors margin trees, then the box tree)
-    size_t cull_tree_cap = 0, cull_nbox_cap = 0;   // leaves n the trees hold, slots nbox holds
+    DevBuf<CullBox> d_cull_nbox{bufs};    // per node slot of the current image
+    DevBuf<uint32_t> d_cull_arrive{bufs}; // per tree (kCullMaxAnchors margin trees, then the box tree)
     uint32_t cull_top_lds = kCullTopLds;  // RTX_CULL_TOP_LDS (tests: the global-memory top levels)
     const uint2* cull_rng = nullptr;
     uint32_t cull_nslots = 0, cull_ntris = 0, cull_n = 0;
@@ -256,18 +240,15 @@ struct rtx_ctx {
     // Hit pass (rtx_render_aov*): the planes in HBM (each allocated when a mask first asks for it;
     // aov_cap = the elements each allocated one holds) and the last pass's own record beside the
     // colour frame's `last`, so a colour gather after a pass still copies the colour frame's rows
-    float* d_aov_depth = nullptr;
-    float* d_aov_normal = nullptr;
-    uint32_t* d_aov_material = nullptr;
-    uint32_t* d_aov_primitive = nullptr;
+    DevBuf<float> d_aov_depth{bufs}, d_aov_normal{bufs};
+    DevBuf<uint32_t> d_aov_material{bufs}, d_aov_primitive{bufs};
     size_t aov_cap = 0;
     rtx_render_params aov_last{};
     int aov_last_views = 1;
     uint32_t aov_last_mask = 0;   // 0: no pass yet
     // Ray queries (rtx_trace_rays, rtx_occluded: rtx_query.hip): the host variants' staging buffer in
-    // HBM, the rays and then every result array of one call; query_cap = the rays it holds
-    char* d_query = nullptr;
-    size_t query_cap = 0;
+    // HBM, the rays and then every result array of one call; its cap = the rays it holds
+    DevBuf<char> d_query{bufs};
 };
 
 namespace rtxh {
@@ -281,7 +262,7 @@ inline int fail(rtx_ctx* c, int code, const std::string& msg) {
     do {                                                                                    \
         hipError_t e_ = (call);                                                             \
         if (e_ != hipSuccess)                                                               \
-            return fail((ctx), RTX_E_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
+            return rtxh::fail((ctx), RTX_E_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
 // The other contexts on c's device with a frame still in flight, and the registry of contexts
@@ -302,19 +283,6 @@ struct UploadLayout {
     uint32_t oct_bytes = 0;
     size_t tri_off = 0, node_off = 0, part_off = 0, mesh_off = 0;   // section offsets in the image
 };
-
-// Free the device buffer `p` and allocate it again for `need` units of `elem` bytes; `cap` = the
-// units it holds (0 when the allocation fails).  No synchronisation: the caller has made sure that
-// nothing queued still reads the old buffer.
-template <class T>
-int device_grow(rtx_ctx* c, T*& p, size_t& cap, size_t need, size_t elem = sizeof(T)) {
-    (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(c, hipMalloc(&p, need * elem));
-    cap = need;
-    return RTX_OK;
-}
 
 // Upload a scene into the context's next image (rtx_upload.hip; rtx_upload_scene, and the device
 // Update's registration with `lay`).
@@ -344,11 +312,9 @@ void remember(rtx_ctx* c, const rtx_render_params* p, int n_views, bool rgb);
 struct CopyPlane { char* dst; const char* src; size_t elem; };
 int queue_rows(rtx_ctx* c, const rtx_render_params& p, int n_views, const CopyPlane* planes, int n_planes);
 
-// One step of the split-threshold tuner from a timed frame's main kernel and chain (ms).
-void split_tune(rtx_ctx* c, float main_ms, float chain_ms);
-// Join the last frame's deferred split chain into the frame stream (rtx_ctx::join_pending).
+// Join the last frame's deferred split chain into the frame stream (rtx_ctx::join).
 int join_split(rtx_ctx* c);
-// One round of the frontier refinement once its measured frame has completed (rtx_ctx::refine_*).
+// One round of the frontier refinement once its measured frame has completed (rtx_ctx::refine).
 int refine_round(rtx_ctx* c);
 // The heaviest tile's serialized one-piece time over the split frame's serialized span (0 until known).
 float inflight_ratio(const rtx_ctx* c);
@@ -356,3 +322,9 @@ float inflight_ratio(const rtx_ctx* c);
 bool inflight_onepiece(rtx_ctx* c, uint32_t k);
 
 }  // namespace rtxh
+
+template <class T>
+int DevBuf<T>::grow(rtx_ctx* c, size_t need, size_t elem) {
+    HIP_TRY(c, alloc(need, elem));
+    return RTX_OK;
+}

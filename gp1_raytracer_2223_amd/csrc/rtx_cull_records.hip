@@ -299,18 +299,18 @@ int cull_launch(rtx_ctx* c, const CullAnchors& A, bool boxes) {
     // the anchors' margin trees: 2n entries per anchor of THIS launch (an upload's first launch has the
     // lights and the views, later ones the views that moved), grown on demand
     const size_t mtree_need = 2 * static_cast<size_t>(n) * std::max<uint32_t>(A.n, 1u);
-    if (n > c->cull_tree_cap || mtree_need > c->cull_mtree_cap || c->cull_nslots > c->cull_nbox_cap ||
+    if (n > c->d_cull_btree.cap || mtree_need > c->d_cull_mtree.cap || c->cull_nslots > c->d_cull_nbox.cap ||
         !c->d_cull_arrive) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         int rc = RTX_OK;
-        if (n > c->cull_tree_cap) rc = device_grow(c, c->d_cull_btree, c->cull_tree_cap, n, 2 * sizeof(CullBox));
-        if (rc == RTX_OK && mtree_need > c->cull_mtree_cap)
-            rc = device_grow(c, c->d_cull_mtree, c->cull_mtree_cap, mtree_need);
-        if (rc == RTX_OK && c->cull_nslots > c->cull_nbox_cap)
-            rc = device_grow(c, c->d_cull_nbox, c->cull_nbox_cap, c->cull_nslots);
+        if (n > c->d_cull_btree.cap) rc = c->d_cull_btree.grow(c, n, 2 * sizeof(CullBox));
+        if (rc == RTX_OK && mtree_need > c->d_cull_mtree.cap)
+            rc = c->d_cull_mtree.grow(c, mtree_need);
+        if (rc == RTX_OK && c->cull_nslots > c->d_cull_nbox.cap)
+            rc = c->d_cull_nbox.grow(c, c->cull_nslots);
         if (rc != RTX_OK) return rc;
         if (!c->d_cull_arrive) {
-            HIP_TRY(c, hipMalloc(&c->d_cull_arrive, (kCullMaxAnchors + 1) * sizeof(uint32_t)));
+            if (const int rc2 = c->d_cull_arrive.grow(c, kCullMaxAnchors + 1); rc2 != RTX_OK) return rc2;
             // on the context stream: a plain hipMemset runs on the null stream, which this
             // non-blocking stream does not wait for (the first tree launch then read whatever the
             // recycled allocation held as its arrival counts)

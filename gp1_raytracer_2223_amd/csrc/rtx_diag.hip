@@ -155,17 +155,17 @@ extern "C" int rtx_cull_dump(rtx_ctx* c, uint32_t anchor, uint32_t* n_slots, uin
 
 extern "C" int rtx_split_tune_info(rtx_ctx* c, float* factor, float* main_ms, float* chain_ms, uint32_t* done) {
     if (!c) return RTX_E_INVALID;
-    if (factor) *factor = static_cast<float>(c->split_permille) / 1000.f;
-    if (main_ms) *main_ms = c->tune_main_ms;
-    if (chain_ms) *chain_ms = c->tune_chain_ms;
-    if (done) *done = (!c->tune_on ? 2u : (c->tune_done ? 1u : 0u));
+    if (factor) *factor = static_cast<float>(c->tuner.permille) / 1000.f;
+    if (main_ms) *main_ms = c->tuner.main_ms;
+    if (chain_ms) *chain_ms = c->tuner.chain_ms;
+    if (done) *done = (!c->tuner.on ? 2u : (c->tuner.done ? 1u : 0u));
     return RTX_OK;
 }
 
 extern "C" int rtx_inflight_info(rtx_ctx* c, uint32_t* concurrent, uint32_t* onepiece, float* crit,
                                  float* crit_threshold, float* split_interval_ms) {
     if (!c) return RTX_E_INVALID;
-    if (split_interval_ms) *split_interval_ms = c->win_interval_ms;
+    if (split_interval_ms) *split_interval_ms = c->window.interval_ms;
     if (concurrent) *concurrent = c->concurrent ? 1u : 0u;
     if (onepiece) *onepiece = c->frame_onepiece ? 1u : 0u;
     if (crit) *crit = inflight_ratio(c);
@@ -182,11 +182,11 @@ extern "C" int rtx_light_major_info(rtx_ctx* c, uint32_t* last_frame, uint32_t* 
 
 extern "C" int rtx_split_info(rtx_ctx* c, uint32_t* heavy_tiles, uint32_t* parts) {
     if (!c) return RTX_E_INVALID;
-    if (c->heavy_pending) {   // a measured frame is in flight: report the set it selects
+    if (c->heavy.pending) {   // a measured frame is in flight: report the set it selects
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipEventSynchronize(c->ev_heavy));
     }
-    const uint32_t n = c->heavy_pending ? std::min<uint32_t>(c->h_heavy_n[0], kMaxHeavyTiles) : c->heavy_n;
+    const uint32_t n = c->heavy.pending ? std::min<uint32_t>(c->h_heavy_n[0], kMaxHeavyTiles) : c->heavy.n;
     const bool on = c->split_mode != 0 && c->split_ok && c->sched_enabled;
     if (heavy_tiles) *heavy_tiles = on ? n : 0u;
     if (parts) *parts = c->split_ok ? c->dev.n_parts : 0u;

@@ -91,8 +91,10 @@ void frame_shape(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rend
     grid = dim3(nblocks, 1, 1);
 }
 
-int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p, bool want_rgb, FrameArgs& F,
-            dim3& grid) {
+namespace {
+
+// ---- prepare's steps, in its order --------------------------------------------------------------
+int check_params(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p) {
     if (!c || !cams || !p) return RTX_E_INVALID;
     if (n_views < 1 || n_views > kMaxViews) return fail(c, RTX_E_INVALID, "n_views must be 1..8");
     if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
@@ -104,231 +106,227 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
     const bool striped = p->stripe_rows != 0 && p->stripe_step > 1;
     if (striped && (p->stripe_rows % 16 != 0 || p->stripe_first >= p->stripe_step))
         return fail(c, RTX_E_INVALID, "stripe_rows must be a multiple of 16 and stripe_first < stripe_step");
-    // Supersampling (rtx_set_supersample): the launch renders the k*width x k*height sample frame `sp`
-    // (the reference's frame of that size; stripes stay output rows, k*stripe_rows sample rows: whole
-    // wave-tile rows) and resolves it into the width x height frame buffer.  The sample frame's sides
-    // stay inside div_rn's divisor domain like a plain frame's.
+    // the sample frame's sides stay inside div_rn's divisor domain like a plain frame's
     const uint32_t ss = c->ss_log2;
     if ((static_cast<uint64_t>(p->width) << ss) > 65536 || (static_cast<uint64_t>(p->height) << ss) > 65536)
         return fail(c, RTX_E_INVALID, "bad image size: supersampled " + std::to_string(1u << ss) + "x" +
                                           std::to_string(1u << ss) + ", the sample frame exceeds 65536 per side");
+    return RTX_OK;
+}
+
+// The frame buffer (and the colour plane when asked for) of npx pixels.
+int frame_buffers(rtx_ctx* c, size_t npx, bool want_rgb) {
+    if (npx > c->d_px.cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (const int rc = c->d_px.grow(c, npx); rc != RTX_OK) return rc;
+    }
+    if (want_rgb && npx > c->d_rgb.cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (const int rc = c->d_rgb.grow(c, npx, 12); rc != RTX_OK) return rc;
+    }
+    return RTX_OK;
+}
+
+// Cost-ordered dispatch (see the kernel): one order/cost pair per launch shape, for ntiles tiles.
+int sched_buffers(rtx_ctx* c, uint32_t ntiles) {
+    if (ntiles <= c->sched_cap) return RTX_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->sched_cap = 0;
+    const size_t nch = (ntiles + kSchedChunk - 1) / kSchedChunk;
+    int rc = c->d_order.grow(c, ntiles);
+    c->d_order_xcd.free();
+    if (rc == RTX_OK && c->xcd_order) rc = c->d_order_xcd.grow(c, ntiles);
+    if (rc == RTX_OK) rc = c->d_cost.grow(c, ntiles);
+    for (auto& f : c->d_heavy_flag)
+        if (rc == RTX_OK) rc = f.grow(c, ntiles);
+    if (rc == RTX_OK) rc = c->d_saved_cost.grow(c, ntiles);
+    if (rc == RTX_OK) rc = c->d_hist.grow(c, nch * kCostBuckets);
+    if (rc == RTX_OK) rc = c->d_csum.grow(c, nch);
+    if (rc != RTX_OK) return rc;
+    c->sched_cap = ntiles;
+    c->sched_key.clear();
+    return RTX_OK;
+}
+
+// A new launch shape or scene: identity order, fresh costs, no split, and every policy from its start.
+int new_shape(rtx_ctx* c, const std::string& key, uint32_t ntiles) {
+    if (c->heavy.pending) HIP_TRY(c, hipEventSynchronize(c->ev_heavy));
+    c->heavy.pending = false;
+    c->heavy.n = 0;
+    c->sched_key = key;
+    c->sched_ready = false;
+    c->sched_frame = 0;
+    c->motion.left = 0;
+    c->max_cost_serial = 0;
+    if (c->refinable) {   // a new shape refines from the upload's frontier
+        if (c->h_parts.size() != c->h_parts_base.size()) {
+            if (const int rc = join_split(c); rc != RTX_OK) return rc;
+            c->h_parts = c->h_parts_base;
+            HIP_TRY(c, hipMemcpyAsync(c->parts_dev, c->h_parts.data(), c->h_parts.size() * sizeof(int4),
+                                      hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            c->dev.n_parts = static_cast<uint32_t>(c->h_parts.size());
+        }
+        c->refine.reset_shape();
+    }
+    c->window.reset();
+    c->tuner.restart_default();   // tune again from the default
+    HIP_TRY(c, hipMemsetAsync(c->d_cost, 0, ntiles * 4, c->stream));
+    return RTX_OK;
+}
+
+// Adopt the heavy set the last measured frame selected, and step the tuner with that frame's timings.
+int adopt_heavy(rtx_ctx* c, bool motion) {
+    if (!c->heavy.pending) return RTX_OK;
+    if (motion) {   // no host wait: adopt only a measurement that has completed
+        const hipError_t q = hipEventQuery(c->ev_heavy);
+        (void)hipGetLastError();   // (a not-ready query is no error for the launches' checks)
+        if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(c, q);
+        if (q != hipSuccess) return RTX_OK;
+    } else {
+        HIP_TRY(c, hipEventSynchronize(c->ev_heavy));   // (one sync per measurement)
+    }
+    c->heavy.pending = false;
+    c->heavy.n = std::min<uint32_t>(c->h_heavy_n[0], kMaxHeavyTiles);
+    if (!c->concurrent) c->max_cost_serial = c->h_heavy_n[2];
+    c->heavy.cur ^= 1;
+    // nothing to balance while no tile is heavy at the default factor (the tuner only
+    // raises the factor from there when the split chain is the longer)
+    if (c->heavy.n == 0 && c->tuner.permille == kSplitPermille && c->heavy.permille[c->heavy.cur] == kSplitPermille)
+        c->tuner.done = true;
+    if (c->tuner.rec) {   // the measured frame's timings: complete (they precede ev_heavy)
+        c->tuner.rec = false;
+        float mm = 0.f, ch = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&mm, c->ev_tune[0], c->ev_tune[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ch, c->ev_tune[0], c->ev_tune[2]));
+        c->tuner.step(c->tuner.rec_permille, mm, ch);
+    }
+    return RTX_OK;
+}
+
+// Whether the frame renders its heavy tiles split: throughput mode and the in-flight one-piece rule.
+bool choose_split(rtx_ctx* c) {
+    // throughput mode: other contexts' frames in flight on this device (rtx_ctx::ev_frame; asked only
+    // where a tile can be split: the other contexts' event queries are not free in a GPU-bound loop)
+    const uint32_t others = (!c->throughput_off && c->tuner.on && c->split_ok && (c->heavy.n > 0 || !c->tuner.done))
+                                ? frames_concurrent(c) : 0u;
+    c->concurrent = others > 0;
+    // in flight: one piece while the heaviest tile is short next to the split frame (kInflightCritPermille)
+    c->frame_onepiece = c->concurrent && c->heavy.n > 0 && inflight_onepiece(c, others + 1);
+    return c->split_mode != 0 && c->split_ok && c->sched_enabled && c->heavy.n > 0 && !c->frame_onepiece;
+}
+
+// The frontier refinement: a completed measurement's round, then whether this frame measures its parts.
+int arm_refinement(rtx_ctx* c, FrameArgs& F, bool split, bool motion) {
+    rtxh::Refinement& R = c->refine;
+    if (R.state == 1)
+        if (const int rc = refine_round(c); rc != RTX_OK) return rc;
+    if (R.quiet) --R.quiet;
+    if (split && R.state == 0 && !motion && c->renders_since_upload >= kRefineQuiet && R.quiet == 0 &&
+        (R.wait == 0 || --R.wait == 0)) {
+        constexpr size_t kWords = 2ull * kMaxParts * kPartShards;
+        if (!c->d_part_max) {
+            if (const int rc = c->d_part_max.grow(c, kWords); rc != RTX_OK) return rc;
+            c->h_part_max.resize(kWords);
+        }
+        HIP_TRY(c, hipMemsetAsync(c->d_part_max, 0, kWords * sizeof(uint32_t), c->stream));
+        F.part_max = c->d_part_max;
+        R.rec = true;
+    }
+    return RTX_OK;
+}
+
+// light-major (FrameArgs::lm_*): a launch small enough that its slowest tiles, not its work, set
+// its time (a few tiles per resident wave slot: a stripe share of a frame), with shadows and 2+
+// lights; the deep-stack variants render one piece
+int choose_light_major(rtx_ctx* c, FrameArgs& F) {
+    const uint32_t nl = c->dev.n_lights, ntiles = F.n_tiles;
+    c->frame_lm = F.shadows && nl >= 2 && nl <= kMaxLmLights && !c->deep_stack && !c->hbm_stack &&
+                  (c->lm_mode == 2 || (c->lm_mode == 1 && ntiles <= c->lm_tiles));
+    if (!c->frame_lm) return RTX_OK;
+    if (ntiles > c->d_lm_rec.cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (const int rc = c->d_lm_rec.grow(c, ntiles, 64 * 2 * sizeof(float4)); rc != RTX_OK) return rc;
+    }
+    if (static_cast<size_t>(ntiles) * nl > c->d_lm_mask.cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (const int rc = c->d_lm_mask.grow(c, static_cast<size_t>(ntiles) * nl); rc != RTX_OK) return rc;
+    }
+    F.lm_lights = nl;
+    F.lm_rec = c->d_lm_rec;
+    F.lm_mask = c->d_lm_mask;
+    return RTX_OK;
+}
+
+// Measure tile costs on the first frame of a shape and then every kSchedPeriod frames;
+// the frames in between reuse the last order and pay nothing for scheduling.
+// while the split threshold is being tuned (a scene with split tiles), every other frame is measured
+void choose_measure(rtx_ctx* c, FrameArgs& F, bool motion) {
+    const bool tuning = c->tuner.on && !c->tuner.done && c->heavy.n > 0 && c->split_mode == 1 && c->split_ok && !motion &&
+                        !c->concurrent;
+    const bool measure = c->sched_enabled && !c->heavy.pending &&
+                         (!c->sched_ready || motion || c->sched_frame % (tuning ? 2u : c->sched_period) == 0);
+    ++c->sched_frame;
+    F.order = (c->sched_enabled && c->sched_ready) ? (c->xcd_order ? c->d_order_xcd : c->d_order).get() : nullptr;
+    F.cost = measure ? c->d_cost.get() : nullptr;
+    F.part_cost = (measure && motion) ? 1u : 0u;
+}
+
+}  // namespace
+
+int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p, bool want_rgb, FrameArgs& F,
+            dim3& grid) {
+    if (const int rc = check_params(c, cams, n_views, p); rc != RTX_OK) return rc;
+    // Supersampling (rtx_set_supersample): the launch renders the k*width x k*height sample frame `sp`
+    // (the reference's frame of that size; stripes stay output rows, k*stripe_rows sample rows: whole
+    // wave-tile rows) and resolves it into the width x height frame buffer.
+    const uint32_t ss = c->ss_log2;
     rtx_render_params sp = *p;
     sp.width <<= ss; sp.height <<= ss; sp.stripe_rows <<= ss;
     const size_t npx = static_cast<size_t>(p->width) * p->height * static_cast<size_t>(n_views);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->join_pending &&
-        !(n_views == c->join_views && c->scene_gen == c->join_gen && c->sb_cur == c->join_sb && ss == c->join_ss &&
-          std::memcmp(p, &c->join_p, sizeof *p) == 0 &&
-          std::memcmp(cams, c->join_cams, sizeof(rtx_camera) * static_cast<size_t>(n_views)) == 0)) {
-        const int rc = join_split(c);
-        if (rc != RTX_OK) return rc;
-    }
-    c->join_p = *p;   // this frame's identity, for the next frame's test above
-    std::memcpy(c->join_cams, cams, sizeof(rtx_camera) * static_cast<size_t>(n_views));
-    c->join_views = n_views;
-    c->join_gen = c->scene_gen;
-    c->join_sb = c->sb_cur;
-    c->join_ss = ss;
-    if (npx > c->px_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (const int rc = device_grow(c, c->d_px, c->px_cap, npx); rc != RTX_OK) return rc;
-    }
-    if (want_rgb && npx > c->rgb_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (const int rc = device_grow(c, c->d_rgb, c->rgb_cap, npx, 12); rc != RTX_OK) return rc;
-    }
+    if (c->join.pending && !c->join.same_frame(*p, cams, n_views, c->scene_gen, c->sb_cur, ss))
+        if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    c->join.note(*p, cams, n_views, c->scene_gen, c->sb_cur, ss);   // this frame's identity, for the next frame's test
+    if (const int rc = frame_buffers(c, npx, want_rgb); rc != RTX_OK) return rc;
     frame_shape(c, cams, n_views, p, sp, ss, F, grid);
     F.out_px = c->d_px;
-    F.out_rgb = want_rgb ? c->d_rgb : nullptr;
+    F.out_rgb = want_rgb ? c->d_rgb.get() : nullptr;
     F.counters = c->d_counters;
-    const uint32_t ntiles = F.n_tiles;
-    // Cost-ordered dispatch (see the kernel): keep one order/cost pair per launch shape.
-    if (ntiles > c->sched_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_order);
-        (void)hipFree(c->d_order_xcd);
-        c->d_order_xcd = nullptr;
-        (void)hipFree(c->d_cost);
-        for (int k = 0; k < 2; ++k) { (void)hipFree(c->d_heavy_flag[k]); c->d_heavy_flag[k] = nullptr; }
-        (void)hipFree(c->d_saved_cost);
-        c->d_saved_cost = nullptr;
-        (void)hipFree(c->d_hist);
-        (void)hipFree(c->d_csum);
-        c->d_hist = nullptr;
-        c->d_csum = nullptr;
-        c->d_order = nullptr;
-        c->d_cost = nullptr;
-        c->sched_cap = 0;
-        HIP_TRY(c, hipMalloc(&c->d_order, ntiles * 4));
-        if (c->xcd_order) HIP_TRY(c, hipMalloc(&c->d_order_xcd, ntiles * 4));
-        HIP_TRY(c, hipMalloc(&c->d_cost, ntiles * 4));
-        for (int k = 0; k < 2; ++k) HIP_TRY(c, hipMalloc(&c->d_heavy_flag[k], ntiles * 4));
-        HIP_TRY(c, hipMalloc(&c->d_saved_cost, ntiles * 4));
-        const size_t nch = (ntiles + kSchedChunk - 1) / kSchedChunk;
-        HIP_TRY(c, hipMalloc(&c->d_hist, nch * kCostBuckets * 4));
-        HIP_TRY(c, hipMalloc(&c->d_csum, nch * 8));
-        c->sched_cap = ntiles;
-        c->sched_key.clear();
-    }
-    std::string key = std::to_string(sp.width) + "x" + std::to_string(sp.height) + "v" + std::to_string(n_views) +
-                      "s" + std::to_string(sp.stripe_rows) + "/" + std::to_string(p->stripe_first) + "/" +
-                      std::to_string(p->stripe_step) + "g" + c->scene_sig + "m" +
-                      std::to_string(p->lighting_mode) + std::to_string(p->shadows_enabled) + "k" + std::to_string(ss);
+    if (const int rc = sched_buffers(c, F.n_tiles); rc != RTX_OK) return rc;
+    const std::string key = std::to_string(sp.width) + "x" + std::to_string(sp.height) + "v" + std::to_string(n_views) +
+                            "s" + std::to_string(sp.stripe_rows) + "/" + std::to_string(p->stripe_first) + "/" +
+                            std::to_string(p->stripe_step) + "g" + c->scene_sig + "m" +
+                            std::to_string(p->lighting_mode) + std::to_string(p->shadows_enabled) + "k" + std::to_string(ss);
     // Motion mode: a camera differs from the previous frame's (any field), so the tile costs go
     // stale quickly.  For kMotionFrames frames from then on, every frame is measured whose previous
     // measurement has completed (adopted without waiting), and split tiles are costed by their
     // split waves (FrameArgs::part_cost).  Otherwise: one measurement every sched_period frames,
     // adopted at the next frame (one host wait per measurement).
-    bool moved = c->prev_views != n_views;
-    for (int v = 0; !moved && v < n_views; ++v) {
-        const ViewCam &a = F.cam[v], &b = c->prev_cam[v];
-        moved = std::memcmp(a.origin, b.origin, 12) || std::memcmp(a.right, b.right, 12) ||
-                std::memcmp(a.up, b.up, 12) || std::memcmp(a.forward, b.forward, 12) || a.fov != b.fov;
-    }
-    std::memcpy(c->prev_cam, F.cam, sizeof(ViewCam) * static_cast<size_t>(n_views));
-    c->prev_views = n_views;
-    // animated geometry (rtx_ctx::upload_motion), where a stale schedule costs: a scene with split
+    // Animated geometry (Motion::upload_motion) counts where a stale schedule costs: a scene with split
     // tiles (W4_Optional's F6 loop: GPU wait 0.51 -> 0.43 ms).  Without them the per-frame
     // measurement is the larger cost (W4_Bunny's loop 7-10 % slower, W4_Reference's serial 11 %).
-    moved = moved || (c->upload_motion && c->heavy_n > 0);
-    c->upload_motion = false;
-    if (key != c->sched_key) {   // new shape or scene: identity order, fresh costs, no split
-        if (c->heavy_pending) HIP_TRY(c, hipEventSynchronize(c->ev_heavy));
-        c->heavy_pending = false;
-        c->heavy_n = 0;
-        c->sched_key = key;
-        c->sched_ready = false;
-        c->sched_frame = 0;
-        c->motion_left = 0;
-        c->max_cost_serial = 0;
-        if (c->refinable) {   // a new shape refines from the upload's frontier
-            if (c->h_parts.size() != c->h_parts_base.size()) {
-                if (const int rc = join_split(c); rc != RTX_OK) return rc;
-                c->h_parts = c->h_parts_base;
-                HIP_TRY(c, hipMemcpyAsync(c->parts_dev, c->h_parts.data(), c->h_parts.size() * sizeof(int4),
-                                          hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                c->dev.n_parts = static_cast<uint32_t>(c->h_parts.size());
-            }
-            c->refine_round = 0;
-            c->refine_state = 0;
-            c->refine_wait = 0;
-            c->refine_prev_max = 0;
-            c->refine_rec = false;
-            c->refine_quiet = kRefineQuiet;
-        }
-        c->win_state = 0;
-        c->win_frames = 0;
-        c->win_interval_ms = 0.f;
-        if (c->tune_on) {   // a new shape: tune again from the default
-            c->split_permille = kSplitPermille;
-            c->tune_done = false;
-            c->tune_steps = 0;
-            c->tune_dir = 0;
-            c->tune_step = 1.15f;
-            c->tune_best_span = 0.f;
-            c->tune_best_permille = 0;
-        }
-        c->tune_rec = false;
-        HIP_TRY(c, hipMemsetAsync(c->d_cost, 0, ntiles * 4, c->stream));
-    } else if (moved && !c->motion_off) {
-        c->motion_left = kMotionFrames;
+    const bool moved = c->motion.moved(cams, n_views) || (c->motion.upload_motion && c->heavy.n > 0);
+    c->motion.upload_motion = false;
+    if (key != c->sched_key) {
+        if (const int rc = new_shape(c, key, F.n_tiles); rc != RTX_OK) return rc;
+    } else if (moved && !c->motion.off) {
+        c->motion.left = kMotionFrames;
     }
-    const bool motion = c->motion_left > 0;
-    if (motion) --c->motion_left;
+    const bool motion = c->motion.left > 0;
+    if (motion) --c->motion.left;
     c->frame_motion = motion;
-    if (c->heavy_pending) {
-        bool ready = true;
-        if (motion) {   // no host wait: adopt only a measurement that has completed
-            const hipError_t q = hipEventQuery(c->ev_heavy);
-            (void)hipGetLastError();   // (a not-ready query is no error for the launches' checks)
-            if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(c, q);
-            ready = q == hipSuccess;
-        } else {
-            // adopt the heavy set the last measured frame selected (one sync per measurement)
-            HIP_TRY(c, hipEventSynchronize(c->ev_heavy));
-        }
-        if (ready) {
-            c->heavy_pending = false;
-            c->heavy_n = std::min<uint32_t>(c->h_heavy_n[0], kMaxHeavyTiles);
-            if (!c->concurrent) c->max_cost_serial = c->h_heavy_n[2];
-            c->heavy_cur ^= 1;
-            // nothing to balance while no tile is heavy at the default factor (the tuner only
-            // raises the factor from there when the split chain is the longer)
-            if (c->heavy_n == 0 && c->split_permille == kSplitPermille && c->set_permille[c->heavy_cur] == kSplitPermille)
-                c->tune_done = true;
-            if (c->tune_rec) {   // the measured frame's timings: complete (they precede ev_heavy)
-                c->tune_rec = false;
-                float mm = 0.f, ch = 0.f;
-                HIP_TRY(c, hipEventElapsedTime(&mm, c->ev_tune[0], c->ev_tune[1]));
-                HIP_TRY(c, hipEventElapsedTime(&ch, c->ev_tune[0], c->ev_tune[2]));
-                c->tune_main_ms = mm;
-                c->tune_chain_ms = ch;
-                split_tune(c, mm, ch);
-            }
-        }
-    }
-    // throughput mode: other contexts' frames in flight on this device (rtx_ctx::ev_frame; asked only
-    // where a tile can be split: the other contexts' event queries are not free in a GPU-bound loop)
-    const uint32_t others = (!c->throughput_off && c->tune_on && c->split_ok && (c->heavy_n > 0 || !c->tune_done))
-                                ? frames_concurrent(c) : 0u;
-    c->concurrent = others > 0;
-    // in flight: one piece while the heaviest tile is short next to the split frame (kInflightCritPermille)
-    c->frame_onepiece = c->concurrent && c->heavy_n > 0 && inflight_onepiece(c, others + 1);
-    const bool split = c->split_mode != 0 && c->split_ok && c->sched_enabled && c->heavy_n > 0 && !c->frame_onepiece;
-    F.heavy_flag = split ? c->d_heavy_flag[c->heavy_cur] : nullptr;
+    if (const int rc = adopt_heavy(c, motion); rc != RTX_OK) return rc;
+    const bool split = choose_split(c);
+    F.heavy_flag = split ? c->d_heavy_flag[c->heavy.cur].get() : nullptr;
     F.part_max = nullptr;
-    if (c->refine_state == 1) {
-        const int rc = refine_round(c);
-        if (rc != RTX_OK) return rc;
-    }
-    if (c->refine_quiet) --c->refine_quiet;
-    if (split && c->refine_state == 0 && !motion && c->renders_since_upload >= kRefineQuiet && c->refine_quiet == 0 &&
-        (c->refine_wait == 0 || --c->refine_wait == 0)) {
-        if (!c->d_part_max) {
-            HIP_TRY(c, hipMalloc(&c->d_part_max, 2ull * kMaxParts * kPartShards * sizeof(uint32_t)));
-            c->h_part_max.resize(2ull * kMaxParts * kPartShards);
-        }
-        HIP_TRY(c, hipMemsetAsync(c->d_part_max, 0, 2ull * kMaxParts * kPartShards * sizeof(uint32_t), c->stream));
-        F.part_max = c->d_part_max;
-        c->refine_rec = true;
-    }
-    F.heavy_list = c->d_heavy_list[c->heavy_cur];
-    F.heavy_n = split ? c->heavy_n : 0u;
+    if (const int rc = arm_refinement(c, F, split, motion); rc != RTX_OK) return rc;
+    F.heavy_list = c->d_heavy_list[c->heavy.cur];
+    F.heavy_n = split ? c->heavy.n : 0u;
     F.hit_key = c->d_hit_key;
     F.occ_bits = c->d_occ;
-    // light-major (FrameArgs::lm_*): a launch small enough that its slowest tiles, not its work, set
-    // its time (a few tiles per resident wave slot: a stripe share of a frame), with shadows and 2+
-    // lights; the deep-stack variants render one piece
-    const uint32_t nl = c->dev.n_lights;
-    c->frame_lm = F.shadows && nl >= 2 && nl <= kMaxLmLights && !c->deep_stack && !c->hbm_stack &&
-                  (c->lm_mode == 2 || (c->lm_mode == 1 && ntiles <= c->lm_tiles));
-    if (c->frame_lm) {
-        if (ntiles > c->lm_rec_tiles) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (const int rc = device_grow(c, c->d_lm_rec, c->lm_rec_tiles, ntiles, 64 * 2 * sizeof(float4)); rc != RTX_OK)
-                return rc;
-        }
-        if (static_cast<size_t>(ntiles) * nl > c->lm_mask_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (const int rc = device_grow(c, c->d_lm_mask, c->lm_mask_cap, static_cast<size_t>(ntiles) * nl); rc != RTX_OK)
-                return rc;
-        }
-        F.lm_lights = nl;
-        F.lm_rec = c->d_lm_rec;
-        F.lm_mask = c->d_lm_mask;
-    }
-    // Measure tile costs on the first frame of a shape and then every kSchedPeriod frames;
-    // the frames in between reuse the last order and pay nothing for scheduling.
-    // while the split threshold is being tuned (a scene with split tiles), every other frame is measured
-    const bool tuning = c->tune_on && !c->tune_done && c->heavy_n > 0 && c->split_mode == 1 && c->split_ok && !motion &&
-                        !c->concurrent;
-    const bool measure = c->sched_enabled && !c->heavy_pending &&
-                         (!c->sched_ready || motion || c->sched_frame % (tuning ? 2u : c->sched_period) == 0);
-    ++c->sched_frame;
-    F.order = (c->sched_enabled && c->sched_ready) ? (c->xcd_order ? c->d_order_xcd : c->d_order) : nullptr;
-    F.cost = measure ? c->d_cost : nullptr;
-    F.part_cost = (measure && motion) ? 1u : 0u;
+    if (const int rc = choose_light_major(c, F); rc != RTX_OK) return rc;
+    choose_measure(c, F, motion);
     return RTX_OK;
 }
 
@@ -340,15 +338,10 @@ int ensure_hbm_stacks(rtx_ctx* c, uint32_t groups) {
     constexpr size_t kEntryBytes = sizeof(uint4) + sizeof(unsigned long long);
     if (need * kEntryBytes > (size_t(64) << 30))
         return fail(c, RTX_E_UNSUPPORTED, "DFS stacks of a " + std::to_string(c->max_depth) + "-level BVH for this frame exceed 64 GB");
-    if (need > c->hstk_entries) {
-        (void)hipFree(c->d_hstk);
-        (void)hipFree(c->d_hstkT);
-        c->d_hstk = nullptr;
-        c->d_hstkT = nullptr;
-        c->hstk_entries = 0;
-        HIP_TRY(c, hipMalloc(&c->d_hstk, need * sizeof(uint4)));
-        HIP_TRY(c, hipMalloc(&c->d_hstkT, need * sizeof(unsigned long long)));
-        c->hstk_entries = need;
+    if (need > c->d_hstkT.cap) {   // (the one grown last: both hold `need` or this runs again)
+        c->d_hstkT.free();
+        if (const int rc = c->d_hstk.grow(c, need); rc != RTX_OK) return rc;
+        if (const int rc = c->d_hstkT.grow(c, need); rc != RTX_OK) return rc;
     }
     c->dev.hstk = c->d_hstk;
     c->dev.hstkT = c->d_hstkT;
@@ -356,82 +349,43 @@ int ensure_hbm_stacks(rtx_ctx* c, uint32_t groups) {
     return RTX_OK;
 }
 
-// count: 1 = the reference's traversal counted (the instrumented kernel), 2 = the culled walk's
-// executed tests (its counting variant, rtx_count_work_culled; the plain one without records)
-int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
-    if (grid.x == 0 || grid.y == 0) return RTX_OK;
-    // (prepare joined already unless this frame repeats the last one's parameters and cameras)
-    const bool inflight_join = c->concurrent && (!c->defer_inflight || c->win_state == 2 || c->win_state == 3);
-    if (c->join_pending && (count || F.cost || F.part_max || F.lm_lights || inflight_join || c->hbm_stack ||
-                            c->deep_stack || F.heavy_flag != c->join_heavy || F.heavy_n != c->join_heavy_n)) {
-        const int rc = join_split(c);
-        if (rc != RTX_OK) return rc;
-    }
-    if (c->hbm_stack) {
-        const int rc = ensure_hbm_stacks(c, grid.x);
-        if (rc != RTX_OK) return rc;
-    }
-    if (count) {
-        FrameArgs G = F;   // the instrumented variant neither reads nor feeds the schedule
-        G.order = nullptr;
-        G.cost = nullptr;
-        G.heavy_flag = nullptr;
-        if (count == 2 && c->dev.cull_stride && !c->hbm_stack && !c->deep_stack) {
-            const int rc = cull_views(c, F);   // the views' camera records, as a frame would
-            if (rc != RTX_OK) return rc;
-            launch_render_one(true, false, false, true, grid, c->stream, c->dev, G);
-        } else if (c->hbm_stack)
-            launch_render_one(true, true, true, false, grid, c->stream, c->dev, G);
-        else if (c->deep_stack)
-            launch_render_one(true, true, false, false, grid, c->stream, c->dev, G);
-        else
-            launch_render_one(true, false, false, false, grid, c->stream, c->dev, G);
+namespace {
+
+// ---- launch's steps -----------------------------------------------------------------------------
+// The heavy tiles, one BVH frontier part per workgroup (see the kernel), on a high-priority stream
+// forked from the frame stream: they share no pixels with the main kernel, so the two run side by
+// side and the join closes the frame.
+int launch_chain(rtx_ctx* c, const FrameArgs& F, int v) {
+    const uint32_t nh = (c->heavy.n + kWavesPerBlock - 1) / kWavesPerBlock, np = c->dev.n_parts;   // heavy wave tiles per workgroup
+    hipStream_t s2 = c->split_stream;
+    // the tuner's timings: static cameras only (a moving one changes the frame under the measurement)
+    const bool timed = F.cost && c->tuner.on && !c->tuner.done && c->split_mode == 1 && !c->frame_motion && !c->concurrent;
+    if (timed) HIP_TRY(c, hipEventRecord(c->ev_tune[0], c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(s2, c->ev_fork, 0));
+    if (!RTX_ABL_CHAIN) {
+        launch_render_phase(1, v, dim3(nh, np, 1), s2, c->dev, F);
         HIP_TRY(c, hipGetLastError());
-        return RTX_OK;
-    }
-    ++c->renders_since_upload;
-    if (c->dev.cull_stride) {   // the views' camera-anchor cull records, when a camera moved
-        const int rc = cull_views(c, F);
-        if (rc != RTX_OK) return rc;
-    }
-    // the first specialised variant whose facts the scene and frame satisfy (kSpecVariants;
-    // RTX_NO_SPEC=1 forces the generic kernel); the split launches take it too
-    const int facts = c->scene_spec | ((F.mode == RTX_MODE_COMBINED && F.shadows) ? kSpecCombShadows : 0);
-    const int v = (c->no_spec || c->deep_stack) ? -1 : spec_variant(facts);
-    c->last_facts = facts;
-    c->last_variant = v;
-    if (F.heavy_flag) {
-        // The heavy tiles, one BVH frontier part per workgroup (see the kernel), on a
-        // high-priority stream forked from the frame stream: they share no pixels with the
-        // main kernel, so the two run side by side and the join closes the frame.
-        const uint32_t nh = (c->heavy_n + kWavesPerBlock - 1) / kWavesPerBlock, np = c->dev.n_parts;   // heavy wave tiles per workgroup
-        hipStream_t s2 = c->split_stream;
-        // split_tune: static cameras only (a moving one changes the frame under the measurement)
-        const bool timed = F.cost && c->tune_on && !c->tune_done && c->split_mode == 1 && !c->frame_motion && !c->concurrent;
-        if (timed) HIP_TRY(c, hipEventRecord(c->ev_tune[0], c->stream));
-        HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(s2, c->ev_fork, 0));
-        if (!RTX_ABL_CHAIN) {
-            launch_render_phase(1, v, dim3(nh, np, 1), s2, c->dev, F);
-            HIP_TRY(c, hipGetLastError());
-            if (F.shadows && c->dev.n_lights) {
-                launch_render_phase(2, v, dim3(nh, np, c->dev.n_lights), s2, c->dev, F);
-                HIP_TRY(c, hipGetLastError());
-            }
-            launch_render_phase(3, v, dim3(nh, 1, 1), s2, c->dev, F);
+        if (F.shadows && c->dev.n_lights) {
+            launch_render_phase(2, v, dim3(nh, np, c->dev.n_lights), s2, c->dev, F);
             HIP_TRY(c, hipGetLastError());
         }
-        if (timed) {   // (before ev_join: the frame's completion then implies this event's)
-            HIP_TRY(c, hipEventRecord(c->ev_tune[2], s2));
-            c->tune_rec = true;
-            c->tune_rec_permille = c->set_permille[c->heavy_cur];
-        }
-        HIP_TRY(c, hipEventRecord(c->ev_join, s2));
+        launch_render_phase(3, v, dim3(nh, 1, 1), s2, c->dev, F);
+        HIP_TRY(c, hipGetLastError());
     }
-    if (c->hbm_stack)   // (the deep variants walk without the cull)
-        launch_render_one(false, true, true, false, grid, c->stream, c->dev, F);
-    else if (c->deep_stack)
-        launch_render_one(false, true, false, false, grid, c->stream, c->dev, F);
+    if (timed) {   // (before ev_join: the frame's completion then implies this event's)
+        HIP_TRY(c, hipEventRecord(c->ev_tune[2], s2));
+        c->tuner.rec = true;
+        c->tuner.rec_permille = c->heavy.permille[c->heavy.cur];
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_join, s2));
+    return RTX_OK;
+}
+
+// The frame's own launch on the frame stream: one kernel, or the light-major three.
+int launch_main(rtx_ctx* c, const FrameArgs& F, dim3 grid, int v) {
+    if (c->deep_stack)   // (the deep variants walk without the cull; hbm_stack is a deep stack too)
+        launch_render_one(false, true, c->hbm_stack, false, grid, c->stream, c->dev, F);
     else if (F.lm_lights) {   // light-major: hit records, then the (tile, light) waves
         launch_render_phase(4, v, grid, c->stream, c->dev, F);
         HIP_TRY(c, hipGetLastError());
@@ -443,30 +397,35 @@ int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
     } else if (!(RTX_ABL_MAIN && F.heavy_flag && !F.cost))
         launch_render_phase(0, v, grid, c->stream, c->dev, F);
     HIP_TRY(c, hipGetLastError());
-    if (F.heavy_flag && c->tune_rec && F.cost) HIP_TRY(c, hipEventRecord(c->ev_tune[1], c->stream));
-    if (F.heavy_flag) {
-        // a plain repeat of the frame defers the join to the next frame or reader (rtx_ctx::join_pending);
-        // a measured, tuned, refined or in-flight one joins now
-        if (F.cost || F.part_max || inflight_join || c->join_off || c->tune_rec || c->refine_rec) {
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        } else {
-            c->join_pending = true;
-            c->join_heavy = F.heavy_flag;
-            c->join_heavy_n = F.heavy_n;
-        }
-    }
-    if (F.cost) {   // the next frames' order and heavy set (rtx_sched.hip)
-        if (const int rc = sched_update(c, F); rc != RTX_OK) return rc;
-    }
+    return RTX_OK;
+}
+
+// The instrumented variants (count: 1 = the reference's traversal counted, 2 = the culled walk's
+// executed tests, rtx_count_work_culled; the plain one without records).
+int launch_counting(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
+    FrameArgs G = F;   // the instrumented variant neither reads nor feeds the schedule
+    G.order = nullptr;
+    G.cost = nullptr;
+    G.heavy_flag = nullptr;
+    const bool culled = count == 2 && c->dev.cull_stride && !c->deep_stack;   // (hbm_stack is a deep stack too)
+    if (culled)   // the views' camera records, as a frame would
+        if (const int rc = cull_views(c, F); rc != RTX_OK) return rc;
+    launch_render_one(true, c->deep_stack, c->hbm_stack, culled, grid, c->stream, c->dev, G);
+    HIP_TRY(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// The events at the frame's end: the in-flight window's, the refinement's, and the frame's own.
+int end_frame(rtx_ctx* c) {
     // the frame's end, for other contexts' throughput mode (prepare).  Only a context whose tiles can
     // be split records it: one that has nothing to split (no frontier, or no heavy tile at a converged
     // factor: W4_Bunny) skips the event and the registry's lock on every frame.
-    const bool tracked = c->split_ok && c->split_mode != 0 && !(c->heavy_n == 0 && c->tune_done);
-    if (c->win_rec >= 0) HIP_TRY(c, hipEventRecord(c->ev_win[c->win_rec], c->stream));
-    if (c->refine_rec) {   // the measured frame's end (its chain joined): its part statistics are complete
+    const bool tracked = c->split_ok && c->split_mode != 0 && !(c->heavy.n == 0 && c->tuner.done);
+    if (c->window.rec >= 0) HIP_TRY(c, hipEventRecord(c->ev_win[c->window.rec], c->stream));
+    if (c->refine.rec) {   // the measured frame's end (its chain joined): its part statistics are complete
         HIP_TRY(c, hipEventRecord(c->ev_refine, c->stream));
-        c->refine_rec = false;
-        c->refine_state = 1;
+        c->refine.rec = false;
+        c->refine.state = 1;
     }
     if (tracked) {
         HIP_TRY(c, hipEventRecord(c->ev_frame, c->stream));
@@ -479,6 +438,48 @@ int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
         c->in_registry = false;
     }
     return RTX_OK;
+}
+
+}  // namespace
+
+// count: 0 a frame, 1 / 2 the instrumented kernels (launch_counting)
+int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
+    if (grid.x == 0 || grid.y == 0) return RTX_OK;
+    // (prepare joined already unless this frame repeats the last one's parameters and cameras)
+    const bool inflight_join = c->concurrent && (!c->defer_inflight || c->window.state == 2 || c->window.state == 3);
+    if (c->join.pending && (count || F.cost || F.part_max || F.lm_lights || inflight_join || c->hbm_stack ||
+                            c->deep_stack || F.heavy_flag != c->join.heavy || F.heavy_n != c->join.heavy_n))
+        if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    if (c->hbm_stack)
+        if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
+    if (count) return launch_counting(c, F, grid, count);
+    ++c->renders_since_upload;
+    if (c->dev.cull_stride)   // the views' camera-anchor cull records, when a camera moved
+        if (const int rc = cull_views(c, F); rc != RTX_OK) return rc;
+    // the first specialised variant whose facts the scene and frame satisfy (kSpecVariants;
+    // RTX_NO_SPEC=1 forces the generic kernel); the split launches take it too
+    const int facts = c->scene_spec | ((F.mode == RTX_MODE_COMBINED && F.shadows) ? kSpecCombShadows : 0);
+    const int v = (c->no_spec || c->deep_stack) ? -1 : spec_variant(facts);
+    c->last_facts = facts;
+    c->last_variant = v;
+    if (F.heavy_flag)
+        if (const int rc = launch_chain(c, F, v); rc != RTX_OK) return rc;
+    if (const int rc = launch_main(c, F, grid, v); rc != RTX_OK) return rc;
+    if (F.heavy_flag && c->tuner.rec && F.cost) HIP_TRY(c, hipEventRecord(c->ev_tune[1], c->stream));
+    if (F.heavy_flag) {
+        // a plain repeat of the frame defers the join to the next frame or reader (rtx_ctx::join);
+        // a measured, tuned, refined or in-flight one joins now
+        if (F.cost || F.part_max || inflight_join || c->join.off || c->tuner.rec || c->refine.rec) {
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+        } else {
+            c->join.pending = true;
+            c->join.heavy = F.heavy_flag;
+            c->join.heavy_n = F.heavy_n;
+        }
+    }
+    if (F.cost)   // the next frames' order and heavy set (rtx_sched.hip)
+        if (const int rc = sched_update(c, F); rc != RTX_OK) return rc;
+    return end_frame(c);
 }
 
 void remember(rtx_ctx* c, const rtx_render_params* p, int n_views, bool rgb) {
@@ -536,8 +537,8 @@ int queue_owned_copy(rtx_ctx* c, uint32_t* out_px, float* out_rgb) {
     if (out_rgb && !c->last_rgb) return fail(c, RTX_E_STATE, "last render did not produce colours");
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = join_split(c); rc != RTX_OK) return rc;
-    const CopyPlane planes[2] = {{reinterpret_cast<char*>(out_px), reinterpret_cast<const char*>(c->d_px), 4},
-                                 {reinterpret_cast<char*>(out_rgb), reinterpret_cast<const char*>(c->d_rgb), 12}};
+    const CopyPlane planes[2] = {{reinterpret_cast<char*>(out_px), reinterpret_cast<const char*>(c->d_px.get()), 4},
+                                 {reinterpret_cast<char*>(out_rgb), reinterpret_cast<const char*>(c->d_rgb.get()), 12}};
     return queue_rows(c, c->last, c->last_views, planes, 2);
 }
 

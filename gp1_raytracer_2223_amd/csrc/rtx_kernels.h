@@ -35,17 +35,13 @@ constexpr uint32_t kCullWorthReuse = 16;  // animated uploads per cull worth est
 constexpr int kPartsPerMesh = 64;      // target frontier size per mesh BVH (with the exact cull, Synthetic100k
                                        // 1080p: 64 parts 1.00 ms, 128 1.12, 256 1.46; before it 128 beat 64 by 6 %)
 constexpr int kMaxParts = 1024;        // all meshes together
-// Frontier refinement (rtx_ctx::refine_*): a static scene's split frame is measured per part (its
-// longest closest-hit and shadow waves), and the parts whose waves are within kRefineTopPermille /
+// Frontier refinement (rtx_ctx::refine; the kRefine* constants not here are rtx_policy.h's): a static
+// scene's split frame is measured per part (its longest closest-hit and shadow waves), and the parts whose waves are within kRefineTopPermille /
 // 1000 of the longest are cut into their two children (at most kRefineSplits per round, kRefineRounds
 // rounds, kRefineQuiet frames after an upload): the chain's critical path is its longest part waves
 // (profiles/r06/floor_hist_chain.jsonl), and cutting the few heaviest parts shortens it
 // (profiles/r06/part_refine.txt: Synthetic100k share of 8 0.607 -> 0.441-0.473 ms).
 constexpr int kPartShards = 16;
-constexpr uint32_t kRefineRounds = 3;
-constexpr uint32_t kRefineSplits = 8;
-constexpr uint32_t kRefineTopPermille = 600;
-constexpr uint32_t kRefineQuiet = 32;
 // ... and only while the longest part waves (closest hit + shadow) exceed kRefineMinUs: shorter ones
 // are not the chain's cost (its launches are), and more parts only add waves (Bunny + 8 lights)
 constexpr uint32_t kRefineMinUs = 100;
@@ -54,27 +50,9 @@ constexpr uint32_t kRefineMinUs = 100;
 // and its frames in flight lost throughput to the extra part waves (0.51 -> 0.56 ms per frame)
 constexpr uint32_t kRefineOverMainPermille = 1500;
 constexpr int kMaxHeavyTiles = 8192;   // heavy wave tiles per frame (hit-key buffer: 64 px each)
-// split factor floor while other contexts' frames are in flight (rtx_ctx::ev_frame)
+// split factor floor while other contexts' frames are in flight (rtx_ctx::ev_frame; the in-flight
+// one-piece choice and the default factor kSplitPermille are rtx_policy.h's)
 constexpr uint32_t kThroughputPermille = 2600;
-// In flight (rtx_ctx::concurrent) a split frame's extra work (the chain's repeated path walks, its
-// launches) can cost more than its shorter critical path saves, since the other contexts' frames fill
-// the GPU beside a long tile (2 frames in flight, profiles/r06/inflight_split_ab.txt: Bunny + 8 lights
-// 4K share of 8 0.067 split / 0.059 ms one piece, W4_Optional share of 8 0.110 / 0.088, Synthetic100k
-// share of 8 0.405 / 0.622).  Two frames in flight hide a tile as long as about two frames' time: a
-// frame in flight renders one piece when its heaviest tile's one-piece cost (measured serialized) is
-// below kInflightCritPermille / 1000 x the split frame's serialized span (the tuner's best, main
-// kernel or chain), which holds for the first two and not for Synthetic100k (profiles/r06/
-// inflight_crit_ab.txt).  RTX_INFLIGHT_CRIT=f sets the factor (0: split as serialized frames do).
-constexpr uint32_t kInflightCritPermille = 1600;
-// ... or when split frames in flight do not overlap: k frames in flight at once, their interval on a
-// context's stream at least k x the serialized span / kInflightOverlapMin (timed over kInflightWindow
-// frames after kInflightWindowSkip; W4_Optional's shares: the chain's work fills the GPU)
-constexpr float kInflightOverlapMin = 1.15f;
-constexpr uint32_t kInflightWindow = 32;
-constexpr uint32_t kInflightWindowSkip = 16;
-// 1.5 (v14 sweep, tools/split_sweep.sh): Synthetic100k 4.38 -> 3.51 ms, W4_Optional within
-// noise of 2.0; below 1.25 the split overhead outgrows the tail it removes
-constexpr int kSplitPermille = 1500;
 constexpr int kMaxSplitLights = 32;    // occlusion bits per pixel
 // A tile is split only if its cost is also at least kSplitMinUs (in the cost unit, 16 shader cycles at
 // 2.4 GHz): a launch with fewer tiles than wave slots (a stripe share) starts every tile at once, and
@@ -230,7 +208,7 @@ struct FrameArgs {
     uint32_t n_tiles;             // wave tiles in the launch (all views)
     const uint32_t* __restrict__ order;   // dispatch permutation of the tiles (null = identity)
     uint32_t* __restrict__ cost;          // per-tile cost of this frame (null = not measured)
-    // camera in motion (a measured frame of rtx_ctx::motion_left): the split launches add their
+    // camera in motion (a measured frame of rtx_ctx::motion): the split launches add their
     // waves' durations to their tile's cost, which then replaces the tile's saved one-piece cost
     uint32_t part_cost;
     uint32_t* __restrict__ out_px;   // view v at out_px + v * width * height
@@ -244,7 +222,7 @@ struct FrameArgs {
     uint32_t heavy_n;                           // entries of heavy_list in use
     unsigned long long* __restrict__ hit_key;   // per heavy pixel: min {t bits, triangle}
     uint32_t* __restrict__ occ_bits;            // per heavy pixel: bit l = mesh occludes light l
-    // split launches of a frame the frontier refinement measures (rtx_ctx::refine_*; else null): per
+    // split launches of a frame the frontier refinement measures (rtx_ctx::refine; else null): per
     // (phase 1/2, part, shard) the longest wave, 16-cycle units (atomicMax; shard = wave % kPartShards)
     uint32_t* __restrict__ part_max;
     // Light-major frame (opt-in): PHASE 4 writes each pixel's hit record, PHASE 5 runs

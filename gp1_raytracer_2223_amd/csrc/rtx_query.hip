@@ -77,14 +77,16 @@ QueryArgs trace_args(const rtx_ray* d_rays, uint32_t n, uint32_t mask, const rtx
     return Q;
 }
 
-// The staging buffer for n rays (grown on demand: the queries queued so far are waited for first).
-int stage(rtx_ctx* c, const rtx_ray* rays, uint32_t n) {
+// The staging buffer for n rays (grown on demand: the queries queued so far are waited for first) ...
+int stage_room(rtx_ctx* c, uint32_t n) {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (n > c->query_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const size_t cap = (static_cast<size_t>(n) + 63u) / 64u * 64u;
-        if (const int rc = device_grow(c, c->d_query, c->query_cap, cap, kPerRay); rc != RTX_OK) return rc;
-    }
+    if (n <= c->d_query.cap) return RTX_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return c->d_query.grow(c, (static_cast<size_t>(n) + 63u) / 64u * 64u, kPerRay);
+}
+// ... and the rays in it.
+int stage(rtx_ctx* c, const rtx_ray* rays, uint32_t n) {
+    if (const int rc = stage_room(c, n); rc != RTX_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_query, rays, static_cast<size_t>(n) * sizeof(rtx_ray), hipMemcpyHostToDevice,
                               c->stream));
     return RTX_OK;
@@ -119,14 +121,8 @@ extern "C" int rtx_occluded_device(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n
 extern "C" int rtx_time_ray_queries(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n, int what, uint32_t mask,
                                     const rtx_aov_planes* d_out, uint8_t* d_occ, int iters, float* mean_ms) {
     if (!c || !d_rays || !mean_ms || iters <= 0 || n == 0 || what < 0 || what > 2) return RTX_E_INVALID;
-    if (what == 2) {   // the staging buffer's ray section as the copy's target
-        HIP_TRY(c, hipSetDevice(c->device));
-        if (n > c->query_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            const size_t cap = (static_cast<size_t>(n) + 63u) / 64u * 64u;
-            if (const int rc = device_grow(c, c->d_query, c->query_cap, cap, kPerRay); rc != RTX_OK) return rc;
-        }
-    }
+    if (what == 2)   // the staging buffer's ray section as the copy's target
+        if (const int rc = stage_room(c, n); rc != RTX_OK) return rc;
     const auto once = [&]() -> int {
         if (what == 0) return rtx_trace_rays_device(c, d_rays, n, mask, d_out);
         if (what == 1) return rtx_occluded_device(c, d_rays, n, d_occ);
@@ -152,13 +148,13 @@ extern "C" int rtx_trace_rays(rtx_ctx* c, const rtx_ray* rays, uint32_t n, uint3
     if (n == 0) return RTX_OK;
     if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
     if (const int rc = stage(c, rays, n); rc != RTX_OK) return rc;
-    const size_t cap = c->query_cap;
+    const size_t cap = c->d_query.cap;
     rtx_aov_planes d{};
     if (out->depth) d.depth = reinterpret_cast<float*>(c->d_query + kOffDepth * cap);
     if (out->normal) d.normal = reinterpret_cast<float*>(c->d_query + kOffNormal * cap);
     if (out->material) d.material = reinterpret_cast<uint32_t*>(c->d_query + kOffMaterial * cap);
     if (out->primitive) d.primitive = reinterpret_cast<uint32_t*>(c->d_query + kOffPrimitive * cap);
-    if (const int rc = rtx_trace_rays_device(c, reinterpret_cast<const rtx_ray*>(c->d_query), n, mask, &d); rc != RTX_OK)
+    if (const int rc = rtx_trace_rays_device(c, reinterpret_cast<const rtx_ray*>(c->d_query.get()), n, mask, &d); rc != RTX_OK)
         return rc;
     const size_t N = n;
     if (out->depth) HIP_TRY(c, hipMemcpyAsync(out->depth, d.depth, N * 4u, hipMemcpyDeviceToHost, c->stream));
@@ -175,8 +171,8 @@ extern "C" int rtx_occluded(rtx_ctx* c, const rtx_ray* rays, uint32_t n, uint8_t
     if (n == 0) return RTX_OK;
     if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
     if (const int rc = stage(c, rays, n); rc != RTX_OK) return rc;
-    uint8_t* d_occ = reinterpret_cast<uint8_t*>(c->d_query + kOffOcc * c->query_cap);
-    if (const int rc = rtx_occluded_device(c, reinterpret_cast<const rtx_ray*>(c->d_query), n, d_occ); rc != RTX_OK)
+    uint8_t* d_occ = reinterpret_cast<uint8_t*>(c->d_query + kOffOcc * c->d_query.cap);
+    if (const int rc = rtx_occluded_device(c, reinterpret_cast<const rtx_ray*>(c->d_query.get()), n, d_occ); rc != RTX_OK)
         return rc;
     HIP_TRY(c, hipMemcpyAsync(out, d_occ, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

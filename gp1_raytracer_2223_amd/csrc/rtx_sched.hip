@@ -270,11 +270,11 @@ namespace rtxh {
 int sched_update(rtx_ctx* c, const FrameArgs& F) {
     const uint32_t slots = (c->split_mode == 0 || !c->split_ok) ? 0u
                            : (c->split_mode == 2 ? 0xffffffffu : c->split_slots);
-    const int stage = c->heavy_cur ^ 1;
+    const int stage = c->heavy.cur ^ 1;
     // (throughput mode: at least kThroughputPermille, see rtx_ctx::ev_frame)
-    const uint32_t permille = c->concurrent ? std::max<uint32_t>(c->split_permille, kThroughputPermille)
-                                            : c->split_permille;
-    c->set_permille[stage] = permille;
+    const uint32_t permille = c->concurrent ? std::max<uint32_t>(c->tuner.permille, kThroughputPermille)
+                                            : c->tuner.permille;
+    c->heavy.permille[stage] = permille;
     const uint32_t nch = (F.n_tiles + kSchedChunk - 1) / kSchedChunk;
     hipLaunchKernelGGL(rtx_sched_count, dim3(nch), dim3(kReorderThreads), 0, c->stream, F.cost, F.n_tiles,
                        F.heavy_flag, c->d_saved_cost, c->d_hist, c->d_csum, nch, F.part_cost, c->d_heavy_n + 1);
@@ -294,7 +294,7 @@ int sched_update(rtx_ctx* c, const FrameArgs& F) {
     }
     HIP_TRY(c, hipMemcpyAsync(c->h_heavy_n, c->d_heavy_n, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_heavy, c->stream));
-    c->heavy_pending = true;
+    c->heavy.pending = true;
     c->sched_ready = true;
     return RTX_OK;
 }

@@ -191,7 +191,7 @@ extern "C" int rtx_upload_scene(rtx_ctx* c, const rtx_scene* s) {
     if (c) {   // the upload pattern the cull decision reads (see rtx_ctx::cull_animated)
         c->short_uploads = (c->has_scene && c->renders_since_upload <= 1) ? c->short_uploads + 1 : 0;
         c->renders_since_upload = 0;
-        c->upload_motion = c->short_uploads >= 1;
+        c->motion.upload_motion = c->short_uploads >= 1;
         if (const int rc = join_split(c); rc != RTX_OK) return rc;   // (the last chain reads the current image)
     }
     return upload_scene(c, s, nullptr);
@@ -500,22 +500,13 @@ int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay) {
         HIP_TRY(c, hipEventSynchronize(B.done));
         B.pending = false;
     }
-    if (total > B.cap) {
-        (void)hipFree(B.d);
-        if (B.h) (void)hipHostFree(B.h);
-        B.d = nullptr;
-        B.h = nullptr;
-        B.cap = 0;
-        HIP_TRY(c, hipMalloc(&B.d, total));
-        HIP_TRY(c, hipHostMalloc(&B.h, total));
-        B.cap = total;
-    }
+    if (total > B.cap) HIP_TRY(c, B.grow(total));
     // cull records: one copy of the node slots per anchor (kMaxViews cameras, then the lights)
     const size_t cull_stride = align256(nodes.size() * 16);
     const size_t cull_bytes = cull_on ? (kMaxViews + static_cast<size_t>(s->n_lights)) * cull_stride : 0;
     if (cull_on && (cull_stride >= (1ull << 32) || 2 * tri.size() >= (1ull << 32))) cull_on = false;
-    if (cull_on && cull_bytes > B.cull_cap) {
-        if (const int rc = device_grow(c, B.cull, B.cull_cap, cull_bytes, 1); rc != RTX_OK) return rc;
+    if (cull_on && cull_bytes > B.cull.cap) {
+        if (const int rc = B.cull.grow(c, cull_bytes, 1); rc != RTX_OK) return rc;
     }
     // Large node arrays send copy 0 only and the device writes copies 1..7 (rtx_octant_expand):
     // 1/8 of the node bytes over PCIe and of the host's staging writes (an upload per animated
@@ -623,14 +614,11 @@ int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay) {
         c->last_variant = -1;
     }
     c->split_ok = split_ok && !parts.empty() && !c->deep_stack;
-    c->refinable = refinable && c->split_ok && !c->refine_off;
+    c->refinable = refinable && c->split_ok && !c->refine.off;
     c->h_parts.assign(parts.begin(), parts.begin() + static_cast<std::ptrdiff_t>(n_parts_real));
     c->h_parts_base = c->h_parts;
     c->parts_dev = reinterpret_cast<int4*>(base + secs[8].off);
-    c->refine_round = 0;
-    c->refine_state = c->refinable ? 0 : 2;
-    c->refine_wait = 0;
-    c->refine_prev_max = 0;
+    c->refine.reset_upload(c->refinable);
     c->has_scene = true;
     ++c->scene_gen;
     c->scene_sig = std::to_string(d.n_spheres) + "/" + std::to_string(d.n_planes) + "/" + std::to_string(d.n_meshes) +

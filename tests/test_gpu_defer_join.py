@@ -1,4 +1,4 @@
-"""Deferred join of the split chain (rtx_ctx::join_pending): a frame that repeats the last
+"""Deferred join of the split chain (rtx_ctx::join): a frame that repeats the last
 one (parameters, cameras, scene image, heavy set) starts its main kernel beside the last frame's split
 chain (they write disjoint tiles); anything else joins first.  A sequence that mixes repeats with
 every kind of change — lighting mode, camera, a new scene, stripes — must read back, after each

@@ -1,4 +1,4 @@
-"""Frontier refinement (rtx_ctx::refine_*): after kRefineQuiet frames of a static scene
+"""Frontier refinement (rtx_ctx::refine): after kRefineQuiet frames of a static scene
 the split frame is measured per BVH frontier part and the heaviest parts are cut into their children.
 Parts still partition the triangles, so every frame before, during and after the rounds is the
 reference's: compared with a context that never refines (RTX_REFINE=0)."""
