@@ -39,12 +39,7 @@ struct rtx_anim {
     size_t total = 0, tri_off = 0, node_off = 0, part_off = 0, mesh_off = 0;
     uint32_t oct_bytes = 0;
     DevScene dev{};                       // pointers relative to the image base
-    bool split_ok = false;
-    int spec = 0;
-    float room_p0[5] = {};   // rtx_ctx::room_p0 of the registration upload
-    bool room_fact = false;  // ... and its room skip fact (lights and planes do not animate)
-    float room_M = 0.f;
-    std::string sig;
+    SceneFacts facts;                     // of the registration upload (lights and planes do not animate)
     hipEvent_t ev = nullptr;              // the last update
     // RTX_ANIM_OWN_STREAM=1: the updates run on the anim's own stream (high priority;
     // RTX_ANIM_STREAM_PRIO=normal: default priority) beside the previous frame's render, the
@@ -141,15 +136,12 @@ extern "C" int rtx_anim_create(rtx_anim** out, rtx_ctx* c, const rtx_scene* s, c
         for (uint32_t k = 0; k < 3 * q.n_positions; ++k)
             if (q.positions[k] != q.positions[k]) return afail(nullptr, RTX_E_UNSUPPORTED, "NaN position");
     }
-    UploadLayout lay;
-    lay.reserve.assign(s->n_meshes, 0);
-    for (uint32_t i = 0; i < n; ++i) lay.reserve[ids[i]] = 1;
-    lay.tri0.assign(s->n_meshes, 0); lay.root.assign(s->n_meshes, 0);
-    lay.part0.assign(s->n_meshes, 0); lay.part_cap.assign(s->n_meshes, 0);
-    lay.depth.assign(s->n_meshes, 0);
-    int rc = upload_scene(c, s, &lay);
+    std::vector<uint8_t> reserve(s->n_meshes, 0);
+    for (uint32_t i = 0; i < n; ++i) reserve[ids[i]] = 1;
+    PackedScene P;
+    int rc = upload_scene(c, s, reserve, P);
     if (rc != RTX_OK) return afail(nullptr, rc, std::string("upload: ") + c->err);
-    if (c->deep_stack) return afail(nullptr, RTX_E_UNSUPPORTED, "scene needs the deep-stack kernel");
+    if (c->facts.deep_stack) return afail(nullptr, RTX_E_UNSUPPORTED, "scene needs the deep-stack kernel");
 
     rtx_anim* a = new (std::nothrow) rtx_anim;
     if (!a) return RTX_E_NOMEM;
@@ -184,9 +176,10 @@ extern "C" int rtx_anim_create(rtx_anim** out, rtx_ctx* c, const rtx_scene* s, c
         ANIM_CREATE_TRY(hipStreamCreateWithPriority(&a->stream, hipStreamNonBlocking,
                                                     pr && std::string(pr) == "normal" ? lo_prio : hi_prio));
     }
-    a->total = lay.total;
-    a->tri_off = lay.tri_off; a->node_off = lay.node_off; a->part_off = lay.part_off; a->mesh_off = lay.mesh_off;
-    a->oct_bytes = lay.oct_bytes;
+    a->total = P.total;
+    a->tri_off = P.sec[kSecTris].off; a->node_off = P.sec[kSecNodes].off;
+    a->part_off = P.sec[kSecParts].off; a->mesh_off = P.sec[kSecMeshes].off;
+    a->oct_bytes = P.oct_bytes;
     ANIM_CREATE_TRY(anim_alloc(a, &a->d_template, a->total));
     // anim_alloc's clears run on the null stream, which the context's non-blocking stream
     // does not wait for: finish them before the template copy is queued
@@ -196,14 +189,9 @@ extern "C" int rtx_anim_create(rtx_anim** out, rtx_ctx* c, const rtx_scene* s, c
     a->dev = rebase(c->dev, base, nullptr);
     // every animated triangle keeps |e1| |e2| within a rounding of its registration value
     // (a rotation): FAST Moller-Trumbore only with a factor-2 margin below its 2^56 bound
-    a->dev.tri_fast = lay.max_ee <= 0x1p55 ? 1u : 0u;
+    a->dev.tri_fast = P.max_ee <= 0x1p55 ? 1u : 0u;
     a->reg_fast = a->dev.tri_fast != 0;
-    a->split_ok = c->split_ok;
-    a->spec = c->scene_spec;
-    std::memcpy(a->room_p0, c->room_p0, sizeof a->room_p0);
-    a->room_fact = c->room_fact;
-    a->room_M = c->room_M;
-    a->sig = c->scene_sig;
+    a->facts = c->facts;   // (deep_stack and hbm_stack false: refused above)
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t id = static_cast<uint32_t>(ids[i]);
         const rtx_mesh& m = s->meshes[id];
@@ -254,10 +242,10 @@ extern "C" int rtx_anim_create(rtx_anim** out, rtx_ctx* c, const rtx_scene* s, c
         ANIM_CREATE_TRY(hipMemcpy(d.ref, m.nodes, sizeof(rtx_bvh_node) * m.n_nodes, hipMemcpyHostToDevice));
         d.mat_bits = m.material;
         d.mesh = id;
-        d.tri0 = lay.tri0[id];
-        d.root = lay.root[id];
-        d.part0 = lay.part0[id];
-        d.part_cap = c->split_ok ? lay.part_cap[id] : 0u;
+        d.tri0 = P.mesh_layout[id].tri0;
+        d.root = P.mesh_layout[id].root;
+        d.part0 = P.mesh_layout[id].part0;
+        d.part_cap = a->facts.split_ok ? P.mesh_layout[id].part_cap : 0u;
         a->mesh.push_back(d);
     }
     ANIM_CREATE_TRY(anim_alloc(a, &a->d_mesh, n));
@@ -281,15 +269,10 @@ extern "C" int rtx_anim_update(rtx_anim* a, rtx_ctx* c, const float* transforms)
     if (c->device != a->device) return afail(a, RTX_E_INVALID, "context on another device");
     ANIM_TRY(a, hipSetDevice(a->device));
     if (join_split(c) != RTX_OK) return afail(a, RTX_E_DEVICE, "joining the last split chain");
-    // the context's next scene image (as rtx_upload_scene picks it)
-    const int k = c->sb_cur < 0 ? 0 : (c->sb_cur ^ 1);
+    int k = 0;
+    if (const int rc = next_image(c, a->total, k); rc != RTX_OK) return afail(a, rc, c->err);
     rtx_ctx::SceneBuf& B = c->sb[k];
-    if (B.pending) {
-        ANIM_TRY(a, hipEventSynchronize(B.done));
-        B.pending = false;
-    }
-    if (a->total > B.cap) ANIM_TRY(a, B.grow(a->total));
-    // (image B's earlier renders on this context have completed: B.done above)
+    // (image B's earlier renders on this context have completed: next_image waited for them)
     hipStream_t s = a->stream ? a->stream : c->stream;
     if (a->built) ANIM_TRY(a, hipStreamWaitEvent(s, a->ev, 0));
     ANIM_TRY(a, hipMemcpyAsync(B.d, a->d_template, a->total, hipMemcpyDeviceToDevice, s));
@@ -321,14 +304,8 @@ extern "C" int rtx_anim_update(rtx_anim* a, rtx_ctx* c, const float* transforms)
     if (s != c->stream) ANIM_TRY(a, hipStreamWaitEvent(c->stream, a->ev, 0));   // the next render reads image B
     a->built = true;
     a->cur ^= 1u;
-    // the context now renders from image k (the bookkeeping of rtx_upload_scene)
-    if (c->sb_cur >= 0) {
-        rtx_ctx::SceneBuf& O = c->sb[c->sb_cur];
-        HIP_TRY(c, hipEventRecord(O.done, c->stream));
-        O.pending = true;
-    }
-    c->sb_cur = k;
-    c->scene_bytes = a->total;
+    // the context now renders from image k
+    if (const int rc = adopt_image(c, k, a->total); rc != RTX_OK) return rc;
     c->dev = rebase(a->dev, nullptr, B.d);
     // FAST Moller-Trumbore needs |e1| |e2| <= 2^56 for every triangle (DevScene::tri_fast).  The
     // caller's transform is arbitrary (a scale can grow the edges), so bound the rebuilt edges
@@ -346,16 +323,9 @@ extern "C" int rtx_anim_update(rtx_anim* a, rtx_ctx* c, const float* transforms)
         fast = e * e <= 0x1p55;   // false for NaN / inf too
     }
     c->dev.tri_fast = fast ? 1u : 0u;
-    c->deep_stack = false;
-    c->hbm_stack = false;
-    c->split_ok = a->split_ok;
-    c->scene_spec = a->spec;
-    std::memcpy(c->room_p0, a->room_p0, sizeof c->room_p0);
-    c->room_fact = a->room_fact;
-    c->room_M = a->room_M;
+    c->facts = a->facts;
     c->has_scene = true;
     ++c->scene_gen;
-    c->scene_sig = a->sig;
     return RTX_OK;
 }
 

@@ -64,10 +64,10 @@ int aov_prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rende
 int aov_launch(rtx_ctx* c, const FrameArgs& F, dim3 grid) {
     if (grid.x == 0) return RTX_OK;
     if (const int rc = join_split(c); rc != RTX_OK) return rc;
-    if (c->hbm_stack) {
+    if (c->facts.hbm_stack) {
         if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
         launch_hit_pass(true, true, false, grid, c->stream, c->dev, F);
-    } else if (c->deep_stack) {
+    } else if (c->facts.deep_stack) {
         launch_hit_pass(true, false, false, grid, c->stream, c->dev, F);
     } else {
         if (c->dev.cull_stride) {   // the views' camera-anchor cull records, as a frame would

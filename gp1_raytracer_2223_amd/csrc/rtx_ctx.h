@@ -3,8 +3,9 @@
 // and pure transitions are rtx_policy.h's structs, one per policy; rtx_policy.hip makes their HIP
 // calls: the split tuner, the throughput / in-flight choice, the frontier refinement and the
 // deferred join of the split chain), the context's device buffers (DevBuf), the upload
-// (rtx_upload.hip), the cull records (rtx_cull_records.hip), the tile schedule (rtx_sched.hip) and
-// the frame (rtx_frame.hip).  The render kernel's launches are rtx_launch.h's.  Internal to librtx_hip.so.
+// (rtx_upload.hip, committing what the HIP-free rtx_pack.h packs), the cull records
+// (rtx_cull_records.hip), the tile schedule (rtx_sched.hip) and the frame (rtx_frame.hip).  The render
+// kernel's launches are rtx_launch.h's.  Internal to librtx_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 #include "rtx_diag.h"
 #include "rtx_cull.h"
 #include "rtx_kernels.h"
+#include "rtx_pack.h"
 #include "rtx_policy.h"
 
 using namespace rtxd;
@@ -94,7 +96,7 @@ struct rtx_ctx {
     SceneBuf sb[2];
     int sb_cur = -1;
     size_t scene_bytes = 0;
-    std::string scene_sig;   // topology of the uploaded scene (keeps the tile schedule across re-uploads)
+    rtxh::SceneFacts facts;  // of the uploaded scene (rtx_pack.h)
     DevScene dev{};
     bool has_scene = false;
     // frame buffer in HBM
@@ -168,19 +170,9 @@ struct rtx_ctx {
     hipEvent_t ev_refine = nullptr;
     DevBuf<uint32_t> d_part_max{bufs};
     std::vector<uint32_t> h_part_max;
-    bool split_ok = false;           // the uploaded scene admits split rendering
-    bool deep_stack = false;         // the uploaded scene needs rtx_render_kernel<..., DEEP = true>
-    bool hbm_stack = false;          // ... with its stacks in HBM (HSTK = true): kStackDepthDeep or more levels
-    uint32_t max_depth = 0;          // deepest BVH level of the uploaded scene
     DevBuf<uint4> d_hstk{bufs};      // the HBM stacks (and the instrumented variant's masks), grown on demand
     DevBuf<unsigned long long> d_hstkT{bufs};
-    int scene_spec = 0;              // kSpec* facts of the uploaded scene (kernel specialisation)
-    float room_p0[5] = {};           // kSpecRoomPlanes: plane k's origin on axis kRoomAxes[k]
-    // room skip (rtx_upload.hip, room_skip): every light strictly inside the room, and the bound on the
-    // shadow origins' plane distances; RTX_ROOM_SKIP=0: off (the fact is then reported false)
-    bool room_fact = false;
-    float room_M = 0.f;
-    bool room_skip_off = false;
+    bool room_skip_off = false;      // RTX_ROOM_SKIP=0 (SceneFacts::room_fact)
     bool no_spec = false;            // RTX_NO_SPEC=1: always the generic kernel (tests)
     int last_facts = 0;              // rtx_spec_info: the facts and the kSpecVariants index (-1: the
     int last_variant = -1;           // generic kernel) of the last frame launched
@@ -270,23 +262,14 @@ inline int fail(rtx_ctx* c, int code, const std::string& msg) {
 uint32_t frames_concurrent(rtx_ctx* c);
 void frames_note(rtx_ctx* c);
 void frames_forget(rtx_ctx* c);
-// Layout of an upload whose meshes may reserve rebuild-sized regions (rtx_anim_*): a mesh
-// with reserve[i] set owns 2T node slots from its root (the most a rebuild can number) and
-// exactly `target` frontier entries (unused ones are {-1, ...}), so a device rebuild can
-// rewrite it in place without moving anything else.
-struct UploadLayout {
-    std::vector<uint8_t> reserve;                            // in, per mesh
-    std::vector<uint32_t> tri0, root, part0, part_cap;       // out, per mesh
-    std::vector<int> depth;
-    double max_ee = 0.0;
-    size_t total = 0;
-    uint32_t oct_bytes = 0;
-    size_t tri_off = 0, node_off = 0, part_off = 0, mesh_off = 0;   // section offsets in the image
-};
-
-// Upload a scene into the context's next image (rtx_upload.hip; rtx_upload_scene, and the device
-// Update's registration with `lay`).
-int upload_scene(rtx_ctx* c, const rtx_scene* s, UploadLayout* lay);
+// rtx_upload.hip.  Pack a scene (rtx_pack.h) and commit it to the context's next image; `reserve`
+// (per mesh, or empty) and `P`, the packed scene, serve the device Update's registration.
+int upload_scene(rtx_ctx* c, const rtx_scene* s, const std::vector<uint8_t>& reserve, PackedScene& P);
+// The image a new scene of `total` bytes goes into: the one no queued frame reads, once the frames of
+// two uploads ago are done with it, grown to hold it.  And its adoption once the copies are queued:
+// every frame queued so far reads the previous image.
+int next_image(rtx_ctx* c, size_t total, int& k);
+int adopt_image(rtx_ctx* c, int k, size_t total);
 
 // rtx_cull_records.hip: at upload, the light anchors (tmax bound T[l]) of the image's cull records;
 // before a frame, the record launches its views still need; and the device's octant copies 1..7 of

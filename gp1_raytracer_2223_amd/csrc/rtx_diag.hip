@@ -129,8 +129,8 @@ extern "C" int rtx_spec_info(rtx_ctx* c, uint32_t* facts, int32_t* last_variant)
 
 extern "C" int rtx_room_info(rtx_ctx* c, uint32_t* fact, float* room_M) {
     if (!c) return RTX_E_INVALID;
-    if (fact) *fact = c->room_fact ? 1u : 0u;
-    if (room_M) *room_M = c->room_M;
+    if (fact) *fact = c->facts.room_fact ? 1u : 0u;
+    if (room_M) *room_M = c->facts.room_M;
     return RTX_OK;
 }
 
@@ -187,9 +187,9 @@ extern "C" int rtx_split_info(rtx_ctx* c, uint32_t* heavy_tiles, uint32_t* parts
         HIP_TRY(c, hipEventSynchronize(c->ev_heavy));
     }
     const uint32_t n = c->heavy.pending ? std::min<uint32_t>(c->h_heavy_n[0], kMaxHeavyTiles) : c->heavy.n;
-    const bool on = c->split_mode != 0 && c->split_ok && c->sched_enabled;
+    const bool on = c->split_mode != 0 && c->facts.split_ok && c->sched_enabled;
     if (heavy_tiles) *heavy_tiles = on ? n : 0u;
-    if (parts) *parts = c->split_ok ? c->dev.n_parts : 0u;
+    if (parts) *parts = c->facts.split_ok ? c->dev.n_parts : 0u;
     return RTX_OK;
 }
 

@@ -53,10 +53,10 @@ void frame_shape(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rend
             const double bt = 4.0 * R + 1.0;
             F.cam[v].cull_bt = std::isfinite(bt) && bt < 0x1p60 ? static_cast<float>(bt) : 0.f;   // 0: no pruning
         }
-        if (c->scene_spec & kSpecRoomPlanes) {   // the room planes' camera numerators (ViewCam)
+        if (c->facts.spec & kSpecRoomPlanes) {   // the room planes' camera numerators (ViewCam)
             bool ok = true;
             for (int k = 0; k < 5; ++k) {
-                const float a = c->room_p0[k] - cams[v].origin[kRoomAxes[k]];
+                const float a = c->facts.room_p0[k] - cams[v].origin[kRoomAxes[k]];
                 const float aa = std::fabs(a);
                 F.cam[v].room_a[k] = a;
                 ok = ok && (a == 0.f || (aa >= 0x1p-60f && aa <= 0x1p60f));
@@ -208,12 +208,12 @@ int adopt_heavy(rtx_ctx* c, bool motion) {
 bool choose_split(rtx_ctx* c) {
     // throughput mode: other contexts' frames in flight on this device (rtx_ctx::ev_frame; asked only
     // where a tile can be split: the other contexts' event queries are not free in a GPU-bound loop)
-    const uint32_t others = (!c->throughput_off && c->tuner.on && c->split_ok && (c->heavy.n > 0 || !c->tuner.done))
+    const uint32_t others = (!c->throughput_off && c->tuner.on && c->facts.split_ok && (c->heavy.n > 0 || !c->tuner.done))
                                 ? frames_concurrent(c) : 0u;
     c->concurrent = others > 0;
     // in flight: one piece while the heaviest tile is short next to the split frame (kInflightCritPermille)
     c->frame_onepiece = c->concurrent && c->heavy.n > 0 && inflight_onepiece(c, others + 1);
-    return c->split_mode != 0 && c->split_ok && c->sched_enabled && c->heavy.n > 0 && !c->frame_onepiece;
+    return c->split_mode != 0 && c->facts.split_ok && c->sched_enabled && c->heavy.n > 0 && !c->frame_onepiece;
 }
 
 // The frontier refinement: a completed measurement's round, then whether this frame measures its parts.
@@ -241,7 +241,7 @@ int arm_refinement(rtx_ctx* c, FrameArgs& F, bool split, bool motion) {
 // lights; the deep-stack variants render one piece
 int choose_light_major(rtx_ctx* c, FrameArgs& F) {
     const uint32_t nl = c->dev.n_lights, ntiles = F.n_tiles;
-    c->frame_lm = F.shadows && nl >= 2 && nl <= kMaxLmLights && !c->deep_stack && !c->hbm_stack &&
+    c->frame_lm = F.shadows && nl >= 2 && nl <= kMaxLmLights && !c->facts.deep_stack && !c->facts.hbm_stack &&
                   (c->lm_mode == 2 || (c->lm_mode == 1 && ntiles <= c->lm_tiles));
     if (!c->frame_lm) return RTX_OK;
     if (ntiles > c->d_lm_rec.cap) {
@@ -262,7 +262,7 @@ int choose_light_major(rtx_ctx* c, FrameArgs& F) {
 // the frames in between reuse the last order and pay nothing for scheduling.
 // while the split threshold is being tuned (a scene with split tiles), every other frame is measured
 void choose_measure(rtx_ctx* c, FrameArgs& F, bool motion) {
-    const bool tuning = c->tuner.on && !c->tuner.done && c->heavy.n > 0 && c->split_mode == 1 && c->split_ok && !motion &&
+    const bool tuning = c->tuner.on && !c->tuner.done && c->heavy.n > 0 && c->split_mode == 1 && c->facts.split_ok && !motion &&
                         !c->concurrent;
     const bool measure = c->sched_enabled && !c->heavy.pending &&
                          (!c->sched_ready || motion || c->sched_frame % (tuning ? 2u : c->sched_period) == 0);
@@ -296,7 +296,7 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
     if (const int rc = sched_buffers(c, F.n_tiles); rc != RTX_OK) return rc;
     const std::string key = std::to_string(sp.width) + "x" + std::to_string(sp.height) + "v" + std::to_string(n_views) +
                             "s" + std::to_string(sp.stripe_rows) + "/" + std::to_string(p->stripe_first) + "/" +
-                            std::to_string(p->stripe_step) + "g" + c->scene_sig + "m" +
+                            std::to_string(p->stripe_step) + "g" + c->facts.sig + "m" +
                             std::to_string(p->lighting_mode) + std::to_string(p->shadows_enabled) + "k" + std::to_string(ss);
     // Motion mode: a camera differs from the previous frame's (any field), so the tile costs go
     // stale quickly.  For kMotionFrames frames from then on, every frame is measured whose previous
@@ -333,11 +333,11 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
 // The HBM stacks of the HSTK variant: max_depth + 1 entries for each wave of a launch of
 // `groups` workgroups (sized per launch: a wave's index in it selects its stack).
 int ensure_hbm_stacks(rtx_ctx* c, uint32_t groups) {
-    const size_t depth = static_cast<size_t>(c->max_depth) + 1u;
+    const size_t depth = static_cast<size_t>(c->facts.max_depth) + 1u;
     const size_t need = static_cast<size_t>(groups) * kWavesPerBlock * depth;
     constexpr size_t kEntryBytes = sizeof(uint4) + sizeof(unsigned long long);
     if (need * kEntryBytes > (size_t(64) << 30))
-        return fail(c, RTX_E_UNSUPPORTED, "DFS stacks of a " + std::to_string(c->max_depth) + "-level BVH for this frame exceed 64 GB");
+        return fail(c, RTX_E_UNSUPPORTED, "DFS stacks of a " + std::to_string(c->facts.max_depth) + "-level BVH for this frame exceed 64 GB");
     if (need > c->d_hstkT.cap) {   // (the one grown last: both hold `need` or this runs again)
         c->d_hstkT.free();
         if (const int rc = c->d_hstk.grow(c, need); rc != RTX_OK) return rc;
@@ -384,8 +384,8 @@ int launch_chain(rtx_ctx* c, const FrameArgs& F, int v) {
 
 // The frame's own launch on the frame stream: one kernel, or the light-major three.
 int launch_main(rtx_ctx* c, const FrameArgs& F, dim3 grid, int v) {
-    if (c->deep_stack)   // (the deep variants walk without the cull; hbm_stack is a deep stack too)
-        launch_render_one(false, true, c->hbm_stack, false, grid, c->stream, c->dev, F);
+    if (c->facts.deep_stack)   // (the deep variants walk without the cull; hbm_stack is a deep stack too)
+        launch_render_one(false, true, c->facts.hbm_stack, false, grid, c->stream, c->dev, F);
     else if (F.lm_lights) {   // light-major: hit records, then the (tile, light) waves
         launch_render_phase(4, v, grid, c->stream, c->dev, F);
         HIP_TRY(c, hipGetLastError());
@@ -407,10 +407,10 @@ int launch_counting(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
     G.order = nullptr;
     G.cost = nullptr;
     G.heavy_flag = nullptr;
-    const bool culled = count == 2 && c->dev.cull_stride && !c->deep_stack;   // (hbm_stack is a deep stack too)
+    const bool culled = count == 2 && c->dev.cull_stride && !c->facts.deep_stack;   // (hbm_stack is a deep stack too)
     if (culled)   // the views' camera records, as a frame would
         if (const int rc = cull_views(c, F); rc != RTX_OK) return rc;
-    launch_render_one(true, c->deep_stack, c->hbm_stack, culled, grid, c->stream, c->dev, G);
+    launch_render_one(true, c->facts.deep_stack, c->facts.hbm_stack, culled, grid, c->stream, c->dev, G);
     HIP_TRY(c, hipGetLastError());
     return RTX_OK;
 }
@@ -420,7 +420,7 @@ int end_frame(rtx_ctx* c) {
     // the frame's end, for other contexts' throughput mode (prepare).  Only a context whose tiles can
     // be split records it: one that has nothing to split (no frontier, or no heavy tile at a converged
     // factor: W4_Bunny) skips the event and the registry's lock on every frame.
-    const bool tracked = c->split_ok && c->split_mode != 0 && !(c->heavy.n == 0 && c->tuner.done);
+    const bool tracked = c->facts.split_ok && c->split_mode != 0 && !(c->heavy.n == 0 && c->tuner.done);
     if (c->window.rec >= 0) HIP_TRY(c, hipEventRecord(c->ev_win[c->window.rec], c->stream));
     if (c->refine.rec) {   // the measured frame's end (its chain joined): its part statistics are complete
         HIP_TRY(c, hipEventRecord(c->ev_refine, c->stream));
@@ -447,10 +447,10 @@ int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
     if (grid.x == 0 || grid.y == 0) return RTX_OK;
     // (prepare joined already unless this frame repeats the last one's parameters and cameras)
     const bool inflight_join = c->concurrent && (!c->defer_inflight || c->window.state == 2 || c->window.state == 3);
-    if (c->join.pending && (count || F.cost || F.part_max || F.lm_lights || inflight_join || c->hbm_stack ||
-                            c->deep_stack || F.heavy_flag != c->join.heavy || F.heavy_n != c->join.heavy_n))
+    if (c->join.pending && (count || F.cost || F.part_max || F.lm_lights || inflight_join || c->facts.hbm_stack ||
+                            c->facts.deep_stack || F.heavy_flag != c->join.heavy || F.heavy_n != c->join.heavy_n))
         if (const int rc = join_split(c); rc != RTX_OK) return rc;
-    if (c->hbm_stack)
+    if (c->facts.hbm_stack)
         if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
     if (count) return launch_counting(c, F, grid, count);
     ++c->renders_since_upload;
@@ -458,8 +458,8 @@ int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count) {
         if (const int rc = cull_views(c, F); rc != RTX_OK) return rc;
     // the first specialised variant whose facts the scene and frame satisfy (kSpecVariants;
     // RTX_NO_SPEC=1 forces the generic kernel); the split launches take it too
-    const int facts = c->scene_spec | ((F.mode == RTX_MODE_COMBINED && F.shadows) ? kSpecCombShadows : 0);
-    const int v = (c->no_spec || c->deep_stack) ? -1 : spec_variant(facts);
+    const int facts = c->facts.spec | ((F.mode == RTX_MODE_COMBINED && F.shadows) ? kSpecCombShadows : 0);
+    const int v = (c->no_spec || c->facts.deep_stack) ? -1 : spec_variant(facts);
     c->last_facts = facts;
     c->last_variant = v;
     if (F.heavy_flag)

@@ -39,8 +39,8 @@ int query_launch(rtx_ctx* c, bool any, QueryArgs Q) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = join_split(c); rc != RTX_OK) return rc;
     uint32_t chunk = kQueryChunkRays;
-    if (c->hbm_stack) {
-        const size_t per_wave = (static_cast<size_t>(c->max_depth) + 1u) * (sizeof(uint4) + sizeof(unsigned long long));
+    if (c->facts.hbm_stack) {
+        const size_t per_wave = (static_cast<size_t>(c->facts.max_depth) + 1u) * (sizeof(uint4) + sizeof(unsigned long long));
         const size_t waves = std::max<size_t>(kQueryStackBytes / per_wave, static_cast<size_t>(kWavesPerBlock));
         chunk = static_cast<uint32_t>(std::min<size_t>(chunk, waves / kWavesPerBlock * kWavesPerBlock * 64u));
     }
@@ -49,11 +49,11 @@ int query_launch(rtx_ctx* c, bool any, QueryArgs Q) {
         const uint32_t n = std::min(chunk, total - first);
         const uint32_t waves = (n + 63u) / 64u;
         const dim3 grid((waves + kWavesPerBlock - 1u) / kWavesPerBlock);
-        if (c->hbm_stack) {
+        if (c->facts.hbm_stack) {
             if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
         }
         Q.n = n;
-        launch_query(any, c->deep_stack || c->hbm_stack, c->hbm_stack, grid, c->stream, c->dev, Q);
+        launch_query(any, c->facts.deep_stack || c->facts.hbm_stack, c->facts.hbm_stack, grid, c->stream, c->dev, Q);
         HIP_TRY(c, hipGetLastError());
         Q.rays += static_cast<size_t>(n) * 8u;
         if (Q.depth) Q.depth += n;

@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(kScanThreads) rtx_sched_xcd(const uint32_t* __
 namespace rtxh {
 
 int sched_update(rtx_ctx* c, const FrameArgs& F) {
-    const uint32_t slots = (c->split_mode == 0 || !c->split_ok) ? 0u
+    const uint32_t slots = (c->split_mode == 0 || !c->facts.split_ok) ? 0u
                            : (c->split_mode == 2 ? 0xffffffffu : c->split_slots);
     const int stage = c->heavy.cur ^ 1;
     // (throughput mode: at least kThroughputPermille, see rtx_ctx::ev_frame)

@@ -3,7 +3,7 @@ reference tree).
 
 The render kernel runs no shadow-ray room-plane test in a wave whose shadow origins all satisfy the
 lane condition below while the uploaded scene has the host fact (csrc/rtx_hip.hip room_clear,
-csrc/rtx_upload.hip room_skip).  That is only allowed where HitTest_Plane (Utils.h:82-98) on the
+csrc/rtx_pack.cpp room_skip).  That is only allowed where HitTest_Plane (Utils.h:82-98) on the
 reference's shadow ray (Renderer.cpp:128-140: l = L - o, tmax = l.Normalize(), tmin = 1e-4) fails
 for every room plane.  Both are restated here and driven with the catalogue room and adversarial
 origins and lights: no case that satisfies the condition may be a plane hit.
