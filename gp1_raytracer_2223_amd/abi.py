@@ -182,7 +182,8 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_render_aov_async", "rtx_render_aov", "rtx_download_aov", "rtx_gather_aov_async",
                "rtx_device_aov_buffers", "rtx_group_render_aov", "rtx_time_aov_frames",
                "rtx_trace_rays", "rtx_occluded", "rtx_trace_rays_device", "rtx_occluded_device",
-               "rtx_time_ray_queries", "rtx_room_info", "rtx_schedule_xcd_order"]
+               "rtx_time_ray_queries", "rtx_room_info", "rtx_schedule_xcd_order",
+               "rtx_shade_rays", "rtx_shade_rays_device", "rtx_time_shade_rays"]
 
 
 def load_hip() -> C.CDLL:
@@ -327,6 +328,15 @@ def load_hip() -> C.CDLL:
             lib.rtx_time_ray_queries.argtypes = [VP, VP, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(AovPlanes), VP,
                                                  C.c_int, C.POINTER(C.c_float)]
             lib.rtx_time_ray_queries.restype = C.c_int
+        if hasattr(lib, "rtx_shade_rays"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_shade_rays.argtypes = [VP, C.POINTER(Ray), C.c_uint32, C.POINTER(RenderParams),
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+            lib.rtx_shade_rays.restype = C.c_int
+            lib.rtx_shade_rays_device.argtypes = [VP, VP, C.c_uint32, C.POINTER(RenderParams), VP, VP]
+            lib.rtx_shade_rays_device.restype = C.c_int
+            lib.rtx_time_shade_rays.argtypes = [VP, VP, C.c_uint32, C.POINTER(RenderParams), VP, VP, C.c_int,
+                                                C.POINTER(C.c_float)]
+            lib.rtx_time_shade_rays.restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]
             lib.rtx_scene_image.restype = C.c_int

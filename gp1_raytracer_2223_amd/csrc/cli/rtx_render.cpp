@@ -4,7 +4,7 @@
 //
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
-//              [--device-update] [--ss K] [--aov PREFIX]
+//              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE]
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -17,6 +17,9 @@
 // the hit pass of the frame it rendered (rtx_render_aov) and writes its planes as raw little-endian
 // files: PREFIX_depth.f32, PREFIX_normal.f32 (3 floats per pixel), PREFIX_material.u32 and
 // PREFIX_primitive.u32 (kind << 30 | index), row-major width x height.
+// --rays FILE (single frames only: not with --benchmark, --sequence, --aov or --ss above 1) shades the
+// image from the caller's rays instead of the camera's (rtx_shade_rays): FILE is raw little-endian
+// float32, width x height rays of eight floats {origin, direction, tmin, tmax}, row-major.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -312,11 +315,11 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
                              "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
-                             "[--aov prefix]\n",
+                             "[--aov prefix] [--rays file]\n",
                      argv[0]);
         return 2;
     }
-    std::string scene = argv[1], out = "RayTracing_Buffer.bmp", assets, aov;
+    std::string scene = argv[1], out = "RayTracing_Buffer.bmp", assets, aov, rays_file;
     int W = 640, H = 480, mode = 3, frames = 1, bench = 0, inflight = 2, ss = 1;
     std::vector<float> seq;
     float t = -1.f;
@@ -347,6 +350,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else if (a == "--aov" && i + 1 < argc) aov = argv[++i];
+        else if (a == "--rays" && i + 1 < argc) rays_file = argv[++i];
         else if (a == "--assets" && i + 1 < argc) assets = argv[++i];
         else if (a == "--benchmark") bench = (i + 1 < argc && std::atoi(argv[i + 1]) > 0) ? std::atoi(argv[++i]) : 10;
         else if (pos == 0) { W = std::atoi(argv[i]); ++pos; }
@@ -355,6 +359,26 @@ int main(int argc, char** argv) {
     if (!aov.empty() && (bench || !seq.empty())) {
         std::fprintf(stderr, "--aov writes the planes of a single frame: not with --benchmark or --sequence\n");
         return 2;
+    }
+    std::vector<rtx_ray> rays;
+    if (!rays_file.empty()) {   // checked and read here: a bad use ends the program before any device work
+        if (bench || !seq.empty() || !aov.empty() || ss > 1) {
+            std::fprintf(stderr, "--rays shades a single frame: not with --benchmark, --sequence, --aov or --ss above 1\n");
+            return 2;
+        }
+        if (W <= 0 || H <= 0) {
+            std::fprintf(stderr, "--rays: bad image size\n");
+            return 2;
+        }
+        rays.resize(static_cast<size_t>(W) * static_cast<size_t>(H));
+        FILE* f = std::fopen(rays_file.c_str(), "rb");
+        const bool ok = f && std::fread(rays.data(), sizeof(rtx_ray), rays.size(), f) == rays.size() && std::fgetc(f) == EOF;
+        if (f) std::fclose(f);
+        if (!ok) {
+            std::fprintf(stderr, "--rays %s: expected %d x %d rays of 8 float32 (%zu bytes)\n", rays_file.c_str(), W, H,
+                         rays.size() * sizeof(rtx_ray));
+            return 2;
+        }
     }
     char err[512] = {0};
     rtx_host_scene* hs = nullptr;
@@ -398,6 +422,8 @@ int main(int argc, char** argv) {
             const std::vector<rtx_host_scene*> more = more_scenes();
             rc = run_benchmark(r, hs, bench, inflight, device_update, nullptr, "", more, static_cast<uint32_t>(ss));
             for (rtx_host_scene* h : more) rtx_host_scene_destroy(h);
+        } else if (!rays.empty()) {   // the image from the caller's rays, through the same BMP writer
+            r.Pixels() = r.ShadeRays(hs, rays, true).pixels;
         } else {
             r.Render(hs, true);
             auto t0 = Clock::now();

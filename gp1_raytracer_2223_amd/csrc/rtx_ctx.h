@@ -238,8 +238,9 @@ struct rtx_ctx {
     rtx_render_params aov_last{};
     int aov_last_views = 1;
     uint32_t aov_last_mask = 0;   // 0: no pass yet
-    // Ray queries (rtx_trace_rays, rtx_occluded: rtx_query.hip): the host variants' staging buffer in
-    // HBM, the rays and then every result array of one call; its cap = the rays it holds
+    // Ray queries and shaded rays (rtx_trace_rays, rtx_occluded, rtx_shade_rays: rtx_query.hip): the host
+    // variants' staging buffer in HBM, the rays and then every result array of one call; its cap = the
+    // rays it holds
     DevBuf<char> d_query{bufs};
 };
 

@@ -1816,6 +1816,242 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
     }
 }
 
+// ====================================================================== shaded rays
+// Renderer::RenderPixel from GetClosestHit on (Renderer.cpp:116-181) for caller-supplied rays
+// (rtx_shade_rays*, rtx.h): the ray is the caller's eight floats as rtx_query_kernel reads them, in its
+// layout (ray i = lane i & 63 of wave i / 64, tail lanes inactive and storing nothing), and viewDirection
+// is the ray's direction as given, so Material::Shade receives -direction whatever its length.
+// Closest hit is the query kernel's closest-hit body with its per-wave choice of walk; the hit record
+// is render_tile's (hit.origin = o + d * t included); the light loop is render_tile's generic one
+// (SPEC 0, shade<0>, no counters), and its shadow ray Ray{originOffset, l, 1e-4, |l|} runs the query
+// kernel's any-hit body with `hitmask` as the active mask: the shadow ray's own `slow` bits, origin,
+// |d_k| <= 1, |o_k| <= 2^40 and tmax decide the walk and the plane loop per wave, as for a query
+// (a caller's ray can put a hit point anywhere, so none of these is known beforehand).
+// The renderer's own shortcuts stay off: no exact cull (no anchor), no camera numerators, no room
+// planes or room skip, no LDS numerator cache, no atomicMin key, no split phases.  The loops are
+// restated, not shared with render_tile or rtx_query_kernel, for the reason given there.
+// Occupancy target: the generic kernel's (65 VGPRs, 7 waves per SIMD).  Asked for 8 waves the default
+// kernel fits 64 VGPRs without scratch and measured 2-3 % slower on W4_Bunny and W3 at 1080p
+// (profiles/shade/ab_waves8.txt), and the HBM-stack one spilled.
+template <bool DEEP, bool HSTK>
+__global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_WAVES_PER_EU)
+    rtx_shade_kernel(const DevScene S, const ShadeArgs Q) {
+    constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
+    __shared__ uint4 stkE[kBlockThreads / 64][kDepth];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t widx = blockIdx.x * kWavesPerBlock + wave;
+    if (widx * 64u >= Q.n) return;
+    uint4* stk = stkE[wave];
+    if constexpr (HSTK) stk = S.hstk + static_cast<size_t>(widx) * S.hstk_depth;
+    const uint32_t i = widx * 64u + lane;
+    const bool valid = i < Q.n;
+    // the lane's ray: 32 bytes with vector loads (a tail lane keeps a harmless one; it is in no mask)
+    QRay q = {{0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 0.f}};
+    if (valid) q = *reinterpret_cast<const QRay*>(Q.rays + static_cast<size_t>(i) * 8u);
+    unsigned long long slow;
+    const Ray r = make_ray(q.v[0], q.v[1], q.v[2], q.v[3], q.v[4], q.v[5], q.v[6], q.v[7], slow);
+    const unsigned long long active = ballot(valid);
+    slow |= ballot(!finite3(r.ox, r.oy, r.oz));
+    const bool slab_fast = (active & slow) == 0;
+    const bool tri_dom = fmaxf(fmaxf(fabsf(r.dx), fabsf(r.dy)), fabsf(r.dz)) <= 1.f &&
+                         fmaxf(fmaxf(fabsf(r.ox), fabsf(r.oy)), fabsf(r.oz)) <= 0x1p40f;
+    const bool fast = slab_fast && S.tri_fast && (active & ~ballot(tri_dom)) == 0;
+    const int oct = (fast && S.oct_bytes) ? batch_octant(r, active) : -1;
+    Counts cnt;   // (never counted: the walks' COUNT is off)
+
+    // ---- Scene::GetClosestHit (Scene.cpp:29-66), as rtx_query_kernel<false, ...>
+    float best_t = FLT_MAX, sc_t = FLT_MAX;
+    uint32_t best_kind = 0, best_idx = 0;   // kind: 0 none, 1 sphere, 2 plane, 3 triangle; idx: BYTE offset
+    for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
+        const float4 s = ldcb16(S.spheres, opaque(k));
+        const SphereProj p = sphere_perp(s, r);
+        const unsigned long long near = ballot(!(s.w < p.perp)) & active;
+        if (!near) continue;
+        const float t = sphere_t(s, p);
+        const bool h = ((near >> lane) & 1ull) & !(t < r.tmin) & !(t > r.tmax);
+        sc_t = h ? t : sc_t;
+        const bool b = h & (t < best_t);
+        best_t = b ? t : best_t;
+        best_kind = b ? 1u : best_kind;
+        best_idx = b ? k : best_idx;
+    }
+    for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+        float4 p0, p1;
+        ldcb32(S.planes, opaque(k), p0, p1);
+        const float t = plane_num(p0, p1, r) / plane_den(p1, r);
+        const bool h = valid & (t >= r.tmin) & (t < r.tmax);
+        sc_t = h ? t : sc_t;
+        const bool b = h & (t < best_t);
+        best_t = b ? t : best_t;
+        best_kind = b ? 2u : best_kind;
+        best_idx = b ? k : best_idx;
+    }
+    for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
+        const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
+        uint32_t sc_tri = 0;
+        unsigned long long unused = 0;
+        if (oct >= 0)
+            mesh_traverse<false, kSlabOct, false>(S, M, r, oct, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
+        else if (fast)
+            mesh_traverse<false, kSlabFast, false>(S, M, r, 0, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
+        else if (slab_fast)
+            mesh_traverse<false, kSlabFast, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
+                                                                       sc_tri, unused, cnt);
+        else
+            mesh_traverse<false, kSlabExact, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
+                                                                        sc_tri, unused, cnt);
+        if (sc_t < best_t) { best_t = sc_t; best_kind = 3; best_idx = sc_tri; }
+    }
+
+    // ---- hit record (rebuilt from t: ray.origin + t * ray.direction, Utils.h:62-64), as render_tile
+    const bool did = best_kind != 0;
+    float hx = 0.f, hy = 0.f, hz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+    uint32_t mat = 0;
+    if (did) {
+        hx = r.ox + r.dx * best_t; hy = r.oy + r.dy * best_t; hz = r.oz + r.dz * best_t;
+        if (best_kind == 1) {
+            const float4 s = ldcb16(S.spheres, best_idx);
+            nx = hx - s.x; ny = hy - s.y; nz = hz - s.z;
+            const float m = sqrtf(nx * nx + ny * ny + nz * nz);   // closestHit.normal.Normalize()
+            div3_exact(nx, ny, nz, m);   // nx /= m; ny /= m; nz /= m
+            mat = ldc(S.sphere_mat, best_idx >> 4);
+        } else if (best_kind == 2) {
+            float4 p0, p1;
+            ldcb32(S.planes, best_idx, p0, p1);
+            nx = p1.x; ny = p1.y; nz = p1.z;
+            mat = __float_as_uint(p0.w);
+        } else {
+            Tri T;
+            ldcb64(S.tris, best_idx, T.a, T.b, T.c, T.d);   // best_idx: byte offset
+            nx = T.a.w; ny = T.b.w; nz = T.c.w;
+            mat = __float_as_uint(T.d.x);
+        }
+    }
+
+    // ---- the reference's light loop (Renderer.cpp:128-176), as render_tile's generic one
+    float shadowFactor = 1.f;
+    float fr = 0.f, fg = 0.f, fb = 0.f;
+    const unsigned long long hitmask = ballot(did);
+    const int mode = Q.mode;
+    if (hitmask) {
+        // originOffset = hit.origin + hit.normal * 0.0001f (Renderer.cpp:126)
+        const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
+        const float vx = -r.dx, vy = -r.dy, vz = -r.dz;
+        for (uint32_t li = 0; li < S.n_lights; ++li) {
+            float4 L0, L1;
+            ldcb32(S.lights, opaque(li * 32u), L0, L1);
+            const int ltype = __float_as_int(L0.w);
+            const bool known = (ltype == RTX_LIGHT_POINT || ltype == RTX_LIGHT_DIRECTIONAL);
+            float lx = known ? L0.x - oox : 0.f, ly = known ? L0.y - ooy : 0.f, lz = known ? L0.z - ooz : 0.f;
+            const float mag = sqrtf(lx * lx + ly * ly + lz * lz);
+            div3_exact(lx, ly, lz, mag);
+            bool occ = false;
+            if (Q.shadows) {
+                // Scene::DoesHit (Scene.cpp:68-96) on Ray{originOffset, l, 1e-4, |l|}, as
+                // rtx_query_kernel<true, ...> with `hitmask` for `active`; `live` = lanes still without
+                // an occluder
+                unsigned long long sslow;
+                const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, 0.0001f, mag, sslow);
+                sslow |= ballot(!finite3(sr.ox, sr.oy, sr.oz));
+                const bool s_slab_fast = (hitmask & sslow) == 0;
+                const bool s_tri_dom = fmaxf(fmaxf(fabsf(sr.dx), fabsf(sr.dy)), fabsf(sr.dz)) <= 1.f &&
+                                       fmaxf(fmaxf(fabsf(sr.ox), fabsf(sr.oy)), fabsf(sr.oz)) <= 0x1p40f;
+                const bool sfast = s_slab_fast && S.tri_fast && (hitmask & ~ballot(s_tri_dom)) == 0;
+                const int soct = (sfast && S.oct_bytes) ? batch_octant(sr, hitmask) : -1;
+                unsigned long long live = hitmask;
+                for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
+                    const float4 s = ldcb16(S.spheres, opaque(k));
+                    const SphereProj p = sphere_perp(s, sr);
+                    const unsigned long long near = ballot(!(s.w < p.perp)) & live;
+                    if (!near) continue;
+                    const float t = sphere_t(s, p);
+                    live &= ~(near & ballot(!(t < sr.tmin)) & ballot(!(t > sr.tmax)));
+                }
+                // (tmin = 1e-4 > 0: plane_cand's domain is a finite tmax = |l| in every hit lane)
+                const bool pl_dom = (hitmask & ~ballot(sr.tmin > 0.f && fabsf(sr.tmax) < INFINITY)) == 0;
+                if (pl_dom) {
+                    for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+                        float4 p0, p1;
+                        ldcb32(S.planes, opaque(k), p0, p1);
+                        const float num = plane_num(p0, p1, sr), den = plane_den(p1, sr);
+                        const unsigned long long cand = plane_cand(num, den, sr.tmax) & live;
+                        if (!cand) continue;   // also taken once no lane is live
+                        const float t = num / den;
+                        live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax) & cand);
+                    }
+                } else {
+                    for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+                        float4 p0, p1;
+                        ldcb32(S.planes, opaque(k), p0, p1);
+                        const float t = plane_num(p0, p1, sr) / plane_den(p1, sr);
+                        live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax));
+                    }
+                }
+                for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
+                    if (!live) break;
+                    float st = 0.f;
+                    uint32_t stri = 0;
+                    const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
+                    if (soct >= 0)
+                        mesh_traverse<true, kSlabOct, false>(S, M, sr, soct, live, lane, stk, nullptr, st, stri, live, cnt);
+                    else if (sfast)
+                        mesh_traverse<true, kSlabFast, false>(S, M, sr, 0, live, lane, stk, nullptr, st, stri, live, cnt);
+                    else if (s_slab_fast)
+                        mesh_traverse<true, kSlabFast, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
+                                                                                  st, stri, live, cnt);
+                    else
+                        mesh_traverse<true, kSlabExact, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
+                                                                                   st, stri, live, cnt);
+                }
+                occ = did & !((live >> lane) & 1ull);
+            }
+            if (!did) continue;
+            if (occ) {
+                shadowFactor *= 0.95f;
+                continue;
+            }
+            if (mode == RTX_MODE_COMBINED || mode == RTX_MODE_RADIANCE) {
+                // LightUtils::GetRadiance (Utils.h:355-369) at hit.origin
+                float s = 0.f;
+                bool any = true;
+                if (ltype == RTX_LIGHT_POINT) {
+                    const float ex = L0.x - hx, ey = L0.y - hy, ez = L0.z - hz;
+                    s = L1.w / (ex * ex + ey * ey + ez * ez);
+                } else if (ltype == RTX_LIGHT_DIRECTIONAL) {
+                    s = L1.w;
+                } else {
+                    any = false;
+                }
+                const float rr = any ? L1.x * s : 0.f, rg = any ? L1.y * s : 0.f, rb = any ? L1.z * s : 0.f;
+                if (mode == RTX_MODE_RADIANCE) {
+                    fr += rr; fg += rg; fb += rb;
+                } else {
+                    const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
+                    const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
+                    fr += (rr * oa) * br.r; fg += (rg * oa) * br.g; fb += (rb * oa) * br.b;
+                }
+            } else if (mode == RTX_MODE_OBSERVED_AREA) {
+                const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
+                fr += oa; fg += oa; fb += oa;
+            } else if (mode == RTX_MODE_BRDF) {
+                const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
+                fr += br.r; fg += br.g; fb += br.b;
+            }
+        }
+        if (did) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
+    }
+    // ColorRGB::MaxToOne (ColorRGB.h:12-17)
+    const float mv = smax(fr, smax(fg, fb));
+    if (mv > 1.f) { fr /= mv; fg /= mv; fb /= mv; }
+    if (valid) {
+        const size_t o = i;
+        if (Q.out_px) Q.out_px[o] = (q8(fr) << Q.rshift) | (q8(fg) << Q.gshift) | (q8(fb) << Q.bshift) | Q.amask;
+        if (Q.out_rgb) {
+            Q.out_rgb[3 * o] = fr; Q.out_rgb[3 * o + 1] = fg; Q.out_rgb[3 * o + 2] = fb;
+        }
+    }
+}
+
 // ====================================================================== launches
 namespace {
 
@@ -1912,6 +2148,12 @@ static void launch_query_t(bool deep, bool hstk, dim3 grid, hipStream_t s, const
 void launch_query(bool any, bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene& d, const QueryArgs& Q) {
     if (any) launch_query_t<true>(deep, hstk, grid, s, d, Q);
     else launch_query_t<false>(deep, hstk, grid, s, d, Q);
+}
+
+void launch_shade(bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene& d, const ShadeArgs& Q) {
+    if (hstk) hipLaunchKernelGGL((rtx_shade_kernel<true, true>), grid, dim3(kBlockThreads), 0, s, d, Q);
+    else if (deep) hipLaunchKernelGGL((rtx_shade_kernel<true, false>), grid, dim3(kBlockThreads), 0, s, d, Q);
+    else hipLaunchKernelGGL((rtx_shade_kernel<false, false>), grid, dim3(kBlockThreads), 0, s, d, Q);
 }
 
 }  // namespace rtxh

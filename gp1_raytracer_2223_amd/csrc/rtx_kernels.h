@@ -1,6 +1,6 @@
 // rtx_kernels.h — device layout of the uploaded scene and the per-frame launch record.
 // Shared by the kernels (rtx_hip.hip, rtx_cull_records.hip, rtx_sched.hip) and the host units
-// that fill them in (rtx_upload.hip, rtx_frame.hip, rtx_aov.hip, rtx_query.hip).
+// that fill them in (rtx_upload.hip, rtx_frame.hip, rtx_aov.hip, rtx_query.hip, rtx_shade.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -263,6 +263,18 @@ struct QueryArgs {
     uint32_t* __restrict__ material;
     uint32_t* __restrict__ primitive;
     uint8_t* __restrict__ occ;
+};
+
+// Shaded rays (rtx_shade_rays*): one launch of rtx_shade_kernel over `n` caller-supplied
+// rays in the queries' layout.  Ray i's pixel goes to out_px[i] and its colour to out_rgb[3i .. 3i + 2];
+// either pointer may be null (not asked for), not both.  Cut into launches as the queries are.
+struct ShadeArgs {
+    const float* __restrict__ rays;
+    uint32_t n;
+    int32_t mode, shadows;
+    uint32_t rshift, gshift, bshift, amask;
+    uint32_t* __restrict__ out_px;
+    float* __restrict__ out_rgb;
 };
 
 // Light-major frames (opt-in: RTX_LIGHT_MAJOR=1 always, =auto while a launch has at most kLmSlotsPercent /

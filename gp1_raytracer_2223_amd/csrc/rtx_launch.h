@@ -25,5 +25,7 @@ void launch_hit_pass(bool deep, bool hstk, bool cull, dim3 grid, hipStream_t s, 
 // one, or the deep one in HBM; grid.x = the launch's waves, ceil(Q.n / 64) / kWavesPerBlock.
 void launch_query(bool any, bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
                   const rtxd::QueryArgs& Q);
+// Shaded rays (rtx_shade_kernel): the same three stacks and grid.
+void launch_shade(bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d, const rtxd::ShadeArgs& Q);
 
 }  // namespace rtxh

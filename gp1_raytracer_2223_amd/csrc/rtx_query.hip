@@ -1,5 +1,6 @@
 // rtx_query.hip — ray queries behind the C-ABI: rtx_trace_rays*, rtx_occluded* (rtx_query_kernel,
-// rtx_hip.hip): their checks, the host variants' staging buffer and the launches.
+// rtx_hip.hip) and rtx_shade_rays* (rtx_shade_kernel): their checks, the host variants' staging buffer
+// and the launches.
 #include <algorithm>
 
 #include "rtx_ctx.h"
@@ -9,8 +10,10 @@ using namespace rtxh;
 
 namespace {
 
-// the staging buffer's sections for `cap` rays: the rays, the four planes, the occlusion bytes
+// the staging buffer's sections for `cap` rays: the rays, the four planes, the occlusion bytes; a shade
+// call's pixels and colours take the depth and the normal sections (the same sizes per ray)
 constexpr size_t kOffDepth = 32, kOffNormal = 36, kOffMaterial = 48, kOffPrimitive = 52, kOffOcc = 56, kPerRay = 57;
+constexpr size_t kOffPixels = kOffDepth, kOffRgb = kOffNormal;
 
 int query_check(rtx_ctx* c, const void* rays, uint32_t n, const void* out) {
     if (!c) return RTX_E_INVALID;
@@ -31,6 +34,17 @@ int mask_check(rtx_ctx* c, uint32_t mask, const rtx_aov_planes* out) {
     return RTX_OK;
 }
 
+// The rays of one launch: kQueryChunkRays, and with HBM stacks what keeps them below kQueryStackBytes.
+uint32_t launch_rays(const rtx_ctx* c) {
+    uint32_t chunk = kQueryChunkRays;
+    if (c->facts.hbm_stack) {
+        const size_t per_wave = (static_cast<size_t>(c->facts.max_depth) + 1u) * (sizeof(uint4) + sizeof(unsigned long long));
+        const size_t waves = std::max<size_t>(kQueryStackBytes / per_wave, static_cast<size_t>(kWavesPerBlock));
+        chunk = static_cast<uint32_t>(std::min<size_t>(chunk, waves / kWavesPerBlock * kWavesPerBlock * 64u));
+    }
+    return chunk;
+}
+
 // Queue the launches of one query on the context stream, behind the last frame's split chain like the
 // hit pass; nothing of the frames' state is read or written.  A large n is cut into launches of at most
 // kQueryChunkRays rays, and with HBM stacks into launches whose stacks stay below kQueryStackBytes.
@@ -38,12 +52,7 @@ int query_launch(rtx_ctx* c, bool any, QueryArgs Q) {
     if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = join_split(c); rc != RTX_OK) return rc;
-    uint32_t chunk = kQueryChunkRays;
-    if (c->facts.hbm_stack) {
-        const size_t per_wave = (static_cast<size_t>(c->facts.max_depth) + 1u) * (sizeof(uint4) + sizeof(unsigned long long));
-        const size_t waves = std::max<size_t>(kQueryStackBytes / per_wave, static_cast<size_t>(kWavesPerBlock));
-        chunk = static_cast<uint32_t>(std::min<size_t>(chunk, waves / kWavesPerBlock * kWavesPerBlock * 64u));
-    }
+    const uint32_t chunk = launch_rays(c);
     const uint32_t total = Q.n;
     for (uint32_t first = 0; first < total; first += chunk) {
         const uint32_t n = std::min(chunk, total - first);
@@ -62,6 +71,42 @@ int query_launch(rtx_ctx* c, bool any, QueryArgs Q) {
         if (Q.primitive) Q.primitive += n;
         if (Q.occ) Q.occ += n;
     }
+    return RTX_OK;
+}
+
+// The same for a shade call (rtx_shade_kernel): the two output pointers advance by n and 3n.
+int shade_launch(rtx_ctx* c, ShadeArgs Q) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    const uint32_t chunk = launch_rays(c);
+    const uint32_t total = Q.n;
+    for (uint32_t first = 0; first < total; first += chunk) {
+        const uint32_t n = std::min(chunk, total - first);
+        const uint32_t waves = (n + 63u) / 64u;
+        const dim3 grid((waves + kWavesPerBlock - 1u) / kWavesPerBlock);
+        if (c->facts.hbm_stack) {
+            if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
+        }
+        Q.n = n;
+        launch_shade(c->facts.deep_stack || c->facts.hbm_stack, c->facts.hbm_stack, grid, c->stream, c->dev, Q);
+        HIP_TRY(c, hipGetLastError());
+        Q.rays += static_cast<size_t>(n) * 8u;
+        if (Q.out_px) Q.out_px += n;
+        if (Q.out_rgb) Q.out_rgb += static_cast<size_t>(n) * 3u;
+    }
+    return RTX_OK;
+}
+
+// A shade call's checks, in the order of the error table (rtx.h); the lighting mode and the pixel
+// format as rtx_render checks them.
+int shade_check(rtx_ctx* c, const void* rays, uint32_t n, const rtx_render_params* p, const void* px, const void* rgb) {
+    if (!c) return RTX_E_INVALID;
+    if (!p) return fail(c, RTX_E_INVALID, "a shade call needs render parameters");
+    if (n > 0 && !rays) return fail(c, RTX_E_INVALID, "a shade call needs rays");
+    if (n > 0 && !px && !rgb) return fail(c, RTX_E_INVALID, "a shade call needs an output: pixels, rgb or both");
+    if (p->lighting_mode < 0 || p->lighting_mode >= RTX_MODE_COUNT) return fail(c, RTX_E_INVALID, "bad lighting mode");
+    if (p->format.rshift > 24 || p->format.gshift > 24 || p->format.bshift > 24)
+        return fail(c, RTX_E_INVALID, "bad pixel format");
     return RTX_OK;
 }
 
@@ -176,5 +221,55 @@ extern "C" int rtx_occluded(rtx_ctx* c, const rtx_ray* rays, uint32_t n, uint8_t
         return rc;
     HIP_TRY(c, hipMemcpyAsync(out, d_occ, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+extern "C" int rtx_shade_rays_device(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n, const rtx_render_params* p,
+                                     uint32_t* d_pixels, float* d_rgb) {
+    if (const int rc = shade_check(c, d_rays, n, p, d_pixels, d_rgb); rc != RTX_OK) return rc;
+    if (n == 0) return RTX_OK;
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    ShadeArgs Q{};
+    Q.rays = reinterpret_cast<const float*>(d_rays);
+    Q.n = n;
+    Q.mode = p->lighting_mode;
+    Q.shadows = p->shadows_enabled ? 1 : 0;
+    Q.rshift = p->format.rshift; Q.gshift = p->format.gshift; Q.bshift = p->format.bshift; Q.amask = p->format.amask;
+    Q.out_px = d_pixels;
+    Q.out_rgb = d_rgb;
+    return shade_launch(c, Q);
+}
+
+extern "C" int rtx_shade_rays(rtx_ctx* c, const rtx_ray* rays, uint32_t n, const rtx_render_params* p, uint32_t* out_pixels,
+                              float* out_rgb) {
+    if (const int rc = shade_check(c, rays, n, p, out_pixels, out_rgb); rc != RTX_OK) return rc;
+    if (n == 0) return RTX_OK;
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    if (const int rc = stage(c, rays, n); rc != RTX_OK) return rc;
+    const size_t cap = c->d_query.cap, N = n;
+    uint32_t* d_px = out_pixels ? reinterpret_cast<uint32_t*>(c->d_query + kOffPixels * cap) : nullptr;
+    float* d_rgb = out_rgb ? reinterpret_cast<float*>(c->d_query + kOffRgb * cap) : nullptr;
+    if (const int rc = rtx_shade_rays_device(c, reinterpret_cast<const rtx_ray*>(c->d_query.get()), n, p, d_px, d_rgb);
+        rc != RTX_OK)
+        return rc;
+    if (out_pixels) HIP_TRY(c, hipMemcpyAsync(out_pixels, d_px, N * 4u, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb) HIP_TRY(c, hipMemcpyAsync(out_rgb, d_rgb, N * 12u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+extern "C" int rtx_time_shade_rays(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n, const rtx_render_params* p,
+                                   uint32_t* d_pixels, float* d_rgb, int iters, float* mean_ms) {
+    if (!c || !d_rays || !p || !mean_ms || iters <= 0 || n == 0) return RTX_E_INVALID;
+    // (checks, a pending chain's join: outside the timing)
+    if (const int rc = rtx_shade_rays_device(c, d_rays, n, p, d_pixels, d_rgb); rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i)
+        if (const int rc = rtx_shade_rays_device(c, d_rays, n, p, d_pixels, d_rgb); rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
     return RTX_OK;
 }

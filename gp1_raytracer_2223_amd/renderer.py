@@ -199,6 +199,34 @@ class DeviceContext:
         abi.check(self.lib.rtx_occluded_device(self.h, C.c_void_p(int(d_rays)), int(n), C.c_void_p(int(d_out))),
                   "rtx_occluded_device", self.h)
 
+    def shade_rays(self, rays, params: abi.RenderParams):
+        """Renderer::RenderPixel from GetClosestHit on for caller-supplied rays (rtx_shade_rays), blocking:
+        (pixels uint32[n], rgb float32[3n]), element i = ray i's.  `params` supplies the lighting mode,
+        shadows and pixel format; its frame size is ignored.  Nothing about a ray is interpreted and Shade
+        receives -direction as given (include/rtx.h)."""
+        a = self._rays(rays)
+        n = a.shape[0]
+        px, rgb = np.zeros(n, np.uint32), np.zeros(3 * n, np.float32)
+        abi.check(self.lib.rtx_shade_rays(self.h, a.ctypes.data_as(C.POINTER(abi.Ray)), n, C.byref(params),
+                                          px.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          rgb.ctypes.data_as(C.POINTER(C.c_float))), "rtx_shade_rays", self.h)
+        return px, rgb
+
+    def shade_rays_device(self, d_rays: int, n: int, params: abi.RenderParams, d_pixels: int = 0, d_rgb: int = 0) -> None:
+        """rtx_shade_rays_device: device addresses (0 = that output is not asked for); queued, complete
+        after synchronize()."""
+        abi.check(self.lib.rtx_shade_rays_device(self.h, C.c_void_p(int(d_rays)), int(n), C.byref(params),
+                                                 C.c_void_p(int(d_pixels) or None), C.c_void_p(int(d_rgb) or None)),
+                  "rtx_shade_rays_device", self.h)
+
+    def time_shade_rays(self, d_rays: int, n: int, params: abi.RenderParams, d_pixels: int, d_rgb: int,
+                        iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_shade_rays(self.h, C.c_void_p(int(d_rays)), int(n), C.byref(params),
+                                               C.c_void_p(int(d_pixels) or None), C.c_void_p(int(d_rgb) or None),
+                                               int(iters), C.byref(ms)), "rtx_time_shade_rays", self.h)
+        return ms.value
+
     def time_aov_frames(self, cam, params, mask: int, iters: int) -> float:
         ms = C.c_float()
         abi.check(self.lib.rtx_time_aov_frames(self.h, C.byref(cam), C.byref(params), int(mask), int(iters),
@@ -454,6 +482,12 @@ class Renderer:
         """Scene::DoesHit on the caller's (n, 8) rays against `scene`: uint8[n]."""
         self._view(scene, upload)
         return self.ctx.occluded(rays)
+
+    def ShadeRays(self, scene: HostScene, rays, upload: bool = True):
+        """RenderPixel from GetClosestHit on for the caller's (n, 8) rays against `scene`, with the
+        renderer's current lighting mode, shadows and pixel format: (pixels uint32[n], rgb float32[3n])."""
+        self._view(scene, upload)
+        return self.ctx.shade_rays(rays, self.params())
 
     def Render(self, scene: HostScene, upload: bool = True, want_rgb: bool = False) -> np.ndarray:
         """Renderer::Render (Renderer.cpp:34-98): blocking; fills self.buffer."""

@@ -30,7 +30,7 @@
  * and the scheduler's / exact cull's internals are in rtx_diag.h; the environment knobs the library
  * reads are listed in INTEGRATION.md (none of them changes a pixel).  In csrc/ the entry points
  * live by topic: rtx_context.hip, rtx_upload.hip, rtx_frame.hip, rtx_aov.hip (the hit pass),
- * rtx_query.hip (ray queries), rtx_group.cpp and rtx_anim_host.hip; the render kernel is rtx_hip.hip.
+ * rtx_query.hip (ray queries and shaded rays), rtx_group.cpp and rtx_anim_host.hip; the render kernel is rtx_hip.hip.
  */
 #ifndef RTX_H_
 #define RTX_H_
@@ -326,6 +326,46 @@ int rtx_occluded(rtx_ctx* ctx, const rtx_ray* rays, uint32_t n, uint8_t* out);
  * call and keeps every buffer alive until then. */
 int rtx_trace_rays_device(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, uint32_t mask, const rtx_aov_planes* d_out);
 int rtx_occluded_device(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, uint8_t* d_out);
+
+/* ---- shaded rays: the reference's pixel for caller-supplied rays ---------------------
+ * Everything of Renderer::RenderPixel after the primary ray (Renderer.cpp:116-181), for rays the caller
+ * makes: a fisheye, orthographic or panoramic camera, a lens with depth of field, a jittered or foveated
+ * sample pattern, a mirror bounce built from the hit pass's normal, a probe at a surface point.
+ *
+ * For ray i the result is RenderPixel's with two changes: viewRay is the dae::Ray built from the eight
+ * floats exactly as rtx_trace_rays builds it (nothing normalised or validated, tmin / tmax as given), and
+ * viewDirection is that ray's direction as given, so Material::Shade receives -direction whatever its
+ * length.  From there it is the reference statement for statement: GetClosestHit; originOffset =
+ * hit.origin + hit.normal * 0.0001f; per light in scene order GetDirectionToLight, Normalize and, with
+ * shadows on, DoesHit(Ray{originOffset, l, 0.0001f, |l|}) then shadowFactor *= 0.95f; the lighting mode's
+ * term; finalColor *= shadowFactor; MaxToOne; the 8-bit quantisation and SDL_MapRGB with params->format.
+ * A miss, and any ray of a scene without lights, is black.
+ *
+ * `params` supplies lighting_mode, shadows_enabled and format; width, height and the stripe fields are
+ * ignored.  out_pixels[i] is ray i's pixel word, out_rgb[3i .. 3i + 2] its colour before quantisation;
+ * either may be NULL (not asked for, never touched), not both.
+ *
+ * Tolerance: every output word is the reference's (a NaN float may be any NaN) wherever the reference
+ * calls no powf: the modes ObservedArea and Radiance on every scene, and every mode on scenes without
+ * Phong or Cook-Torrance materials.  In Combined and BRDF on scenes with such materials the bound is the
+ * frames' (1e-4 per colour channel, 1 LSB per 8-bit channel), claimed for rays with a unit-length
+ * direction; for other directions the output is defined by the text above without a stated bound.
+ *
+ * Errors (the context keeps working after each): NULL ctx, NULL rays with n > 0, NULL params, both
+ * outputs NULL with n > 0, a lighting mode or pixel format rtx_render would reject: RTX_E_INVALID; no
+ * scene uploaded: RTX_E_STATE.  n == 0 returns RTX_OK and launches nothing.
+ *
+ * Queuing, ordering and isolation are the ray queries' (above): behind a pending split chain, ordered
+ * with the frames, passes, uploads and device Updates on the context, nothing of the frame buffer, the
+ * hit-pass planes, the last-frame and last-pass records or the frame schedule is read or written, and a
+ * supersample factor does not matter.  Rays are dispatched in the caller's order, 64 to a wave.
+ * rtx_shade_rays takes host pointers, stages through the queries' buffer and returns when the outputs
+ * are filled; rtx_shade_rays_device takes DEVICE pointers, is queued and returns at once (complete after
+ * rtx_synchronize).  To get the hit record as well, call rtx_trace_rays on the same rays. */
+int rtx_shade_rays(rtx_ctx* ctx, const rtx_ray* rays, uint32_t n, const rtx_render_params* params,
+                   uint32_t* out_pixels, float* out_rgb);
+int rtx_shade_rays_device(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, const rtx_render_params* params,
+                          uint32_t* d_pixels, float* d_rgb);
 
 /* ---- one frame over several GPUs from one process ------------------
  * The reference's Renderer::Render covers the frame with parallel_for

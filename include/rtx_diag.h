@@ -33,6 +33,10 @@ int rtx_time_aov_frames(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_pa
  * bytes) into the context's staging buffer. */
 int rtx_time_ray_queries(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, int what, uint32_t mask,
                          const rtx_aov_planes* d_out, uint8_t* d_occ, int iters, float* mean_ms);
+/* The same for rtx_shade_rays_device(d_rays, n, params, d_pixels, d_rgb): `iters` back-to-back calls, the
+ * mean device time of one in ms. */
+int rtx_time_shade_rays(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, const rtx_render_params* params,
+                        uint32_t* d_pixels, float* d_rgb, int iters, float* mean_ms);
 /* Bytes of HBM the uploaded scene image occupies. */
 int rtx_scene_bytes(const rtx_ctx* ctx, uint64_t* bytes);
 /* Diagnostics: copy the context's current scene image (DESIGN.md §2 layout) after its queued

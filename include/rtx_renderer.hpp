@@ -116,7 +116,31 @@ public:
         return Occluded(rays);
     }
 
-    void CycleLightingMode() {                                                     // Renderer.cpp:189-193
+    // Shaded rays (rtx_shade_rays; not in the reference's Renderer): RenderPixel from GetClosestHit on
+    // for the caller's rays, with the renderer's current lighting mode, shadows and pixel format
+    // (Params()).  Element i of `pixels` and elements 3i .. 3i + 2 of `rgb` are ray i's.
+    struct ShadedRays {
+        std::vector<uint32_t> pixels;
+        std::vector<float> rgb;
+    };
+    ShadedRays ShadeRays(const std::vector<rtx_ray>& rays) {
+        const rtx_render_params p = Params();
+        ShadedRays out;
+        out.pixels.resize(rays.size());
+        out.rgb.resize(3 * rays.size());
+        Check(rtx_shade_rays(m_Ctx, rays.data(), static_cast<uint32_t>(rays.size()), &p, out.pixels.data(), out.rgb.data()),
+              "rtx_shade_rays");
+        return out;
+    }
+    ShadedRays ShadeRays(rtx_host_scene* scene, const std::vector<rtx_ray>& rays, bool upload = true) {
+        rtx_scene s;
+        rtx_camera cam;
+        Check(rtx_host_scene_view(scene, &s, &cam), "rtx_host_scene_view");
+        if (upload) Upload(s);
+        return ShadeRays(rays);
+    }
+
+    void CycleLightingMode() {                                                    // Renderer.cpp:189-193
         m_CurrentLightingMode = static_cast<LightingMode>((static_cast<int>(m_CurrentLightingMode) + 1) %
                                                           static_cast<int>(LightingMode::Count));
     }
