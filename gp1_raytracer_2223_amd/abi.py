@@ -183,7 +183,8 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_device_aov_buffers", "rtx_group_render_aov", "rtx_time_aov_frames",
                "rtx_trace_rays", "rtx_occluded", "rtx_trace_rays_device", "rtx_occluded_device",
                "rtx_time_ray_queries", "rtx_room_info", "rtx_schedule_xcd_order",
-               "rtx_shade_rays", "rtx_shade_rays_device", "rtx_time_shade_rays"]
+               "rtx_shade_rays", "rtx_shade_rays_device", "rtx_time_shade_rays",
+               "rtx_render_adaptive_async", "rtx_render_adaptive", "rtx_adaptive_refined", "rtx_time_adaptive_frames"]
 
 
 def load_hip() -> C.CDLL:
@@ -337,6 +338,18 @@ def load_hip() -> C.CDLL:
             lib.rtx_time_shade_rays.argtypes = [VP, VP, C.c_uint32, C.POINTER(RenderParams), VP, VP, C.c_int,
                                                 C.POINTER(C.c_float)]
             lib.rtx_time_shade_rays.restype = C.c_int
+        if hasattr(lib, "rtx_render_adaptive"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_render_adaptive_async.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_int,
+                                                      C.c_uint32, C.c_uint32]
+            lib.rtx_render_adaptive_async.restype = C.c_int
+            lib.rtx_render_adaptive.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+            lib.rtx_render_adaptive.restype = C.c_int
+            lib.rtx_adaptive_refined.argtypes = [VP, C.POINTER(C.c_uint32)]
+            lib.rtx_adaptive_refined.restype = C.c_int
+            lib.rtx_time_adaptive_frames.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
+                                                     C.c_uint32, C.c_int, C.POINTER(C.c_float)]
+            lib.rtx_time_adaptive_frames.restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]
             lib.rtx_scene_image.restype = C.c_int

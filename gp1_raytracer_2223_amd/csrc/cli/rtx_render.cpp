@@ -4,7 +4,7 @@
 //
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
-//              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE]
+//              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T]
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -20,6 +20,9 @@
 // --rays FILE (single frames only: not with --benchmark, --sequence, --aov or --ss above 1) shades the
 // image from the caller's rays instead of the camera's (rtx_shade_rays): FILE is raw little-endian
 // float32, width x height rays of eight floats {origin, direction, tmin, tmax}, row-major.
+// --adaptive K,T (single frames only: not with --benchmark, --sequence, --aov, --rays or --ss above 1) renders
+// the frame with adaptive supersampling (rtx_render_adaptive): K x K samples (K = 2, 4 or 8) for the pixels
+// that differ from a 4-neighbour by more than T (0..255) in an 8-bit channel, and prints how many that was.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -315,12 +318,13 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
                              "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
-                             "[--aov prefix] [--rays file]\n",
+                             "[--aov prefix] [--rays file] [--adaptive K,T]\n",
                      argv[0]);
         return 2;
     }
     std::string scene = argv[1], out = "RayTracing_Buffer.bmp", assets, aov, rays_file;
     int W = 640, H = 480, mode = 3, frames = 1, bench = 0, inflight = 2, ss = 1;
+    int ad_k = 0, ad_t = 0;   // --adaptive K,T (0: not asked for)
     std::vector<float> seq;
     float t = -1.f;
     bool shadows = true, device_update = false;
@@ -348,6 +352,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (a == "--adaptive") {   // checked here: a bad pair ends the program before any device work
+            char tail = 0;
+            const int got = i + 1 < argc ? std::sscanf(argv[++i], "%d,%d%c", &ad_k, &ad_t, &tail) : 0;
+            if (got != 2 || (ad_k != 2 && ad_k != 4 && ad_k != 8) || ad_t < 0 || ad_t > 255) {
+                std::fprintf(stderr, "--adaptive K,T: the factor K must be 2, 4 or 8 and the threshold T 0..255\n");
+                return 2;
+            }
+        }
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else if (a == "--aov" && i + 1 < argc) aov = argv[++i];
         else if (a == "--rays" && i + 1 < argc) rays_file = argv[++i];
@@ -358,6 +370,10 @@ int main(int argc, char** argv) {
     }
     if (!aov.empty() && (bench || !seq.empty())) {
         std::fprintf(stderr, "--aov writes the planes of a single frame: not with --benchmark or --sequence\n");
+        return 2;
+    }
+    if (ad_k && (bench || !seq.empty() || !aov.empty() || !rays_file.empty() || ss > 1)) {
+        std::fprintf(stderr, "--adaptive renders a single frame: not with --benchmark, --sequence, --aov, --rays or --ss above 1\n");
         return 2;
     }
     std::vector<rtx_ray> rays;
@@ -424,6 +440,9 @@ int main(int argc, char** argv) {
             for (rtx_host_scene* h : more) rtx_host_scene_destroy(h);
         } else if (!rays.empty()) {   // the image from the caller's rays, through the same BMP writer
             r.Pixels() = r.ShadeRays(hs, rays, true).pixels;
+        } else if (ad_k) {   // the adaptive frame, through the same BMP writer
+            r.RenderAdaptive(hs, static_cast<uint32_t>(ad_k), static_cast<uint32_t>(ad_t), true);
+            std::printf("refined %u of %d pixels\n", r.AdaptiveRefined(), W * H);
         } else {
             r.Render(hs, true);
             auto t0 = Clock::now();

@@ -130,6 +130,13 @@ extern "C" int rtx_create(rtx_ctx** out, int device_id) {
     c->split_slots = static_cast<uint32_t>(cus > 0 ? cus : 1) * 28u;
     if (!std::getenv("RTX_LIGHT_MAJOR_TILES")) c->lm_tiles = c->split_slots * kLmSlotsPercent / 100u;
     c->lm_waves = static_cast<uint32_t>(cus > 0 ? cus : 1) * 32u;
+    // the adaptive refinement's persistent waves: every wave slot at its kernel's occupancy, the shade
+    // kernel's (RTX_ADAPTIVE_WAVES caps it: tests force the stride loop with a few waves)
+    c->adapt_waves = c->split_slots;
+    if (const char* e = std::getenv("RTX_ADAPTIVE_WAVES")) {
+        const unsigned long v = std::strtoul(e, nullptr, 10);
+        if (v >= 1 && v < c->adapt_waves) c->adapt_waves = static_cast<uint32_t>(v);
+    }
     *out = c;
     return RTX_OK;
 }

@@ -242,6 +242,14 @@ struct rtx_ctx {
     // variants' staging buffer in HBM, the rays and then every result array of one call; its cap = the
     // rays it holds
     DevBuf<char> d_query{bufs};
+    // Adaptive supersampling (rtx_render_adaptive*: rtx_adaptive.hip): the list of the pixels to refine
+    // (width * height entries, grown on demand) and its length on the device, which an adaptive frame
+    // never reads on the host; adapt_waves = the refinement's persistent waves (every wave slot at the
+    // render kernel's occupancy, RTX_ADAPTIVE_WAVES caps it), adapt_valid = an adaptive frame was queued
+    DevBuf<uint32_t> d_adapt_list{bufs};
+    DevBuf<uint32_t> d_adapt_count{bufs};
+    uint32_t adapt_waves = 0;
+    bool adapt_valid = false;
 };
 
 namespace rtxh {
@@ -290,6 +298,8 @@ void frame_shape(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rend
                  const rtx_render_params& sp, uint32_t ss, FrameArgs& F, dim3& grid);
 int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p, bool want_rgb, FrameArgs& F,
             dim3& grid);
+// prepare's first step: what rtx_render* rejects of a frame's arguments, before anything is queued
+int check_params(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p);
 int ensure_hbm_stacks(rtx_ctx* c, uint32_t groups);
 int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count);
 void remember(rtx_ctx* c, const rtx_render_params* p, int n_views, bool rgb);

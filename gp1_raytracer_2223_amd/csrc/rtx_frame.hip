@@ -91,9 +91,8 @@ void frame_shape(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rend
     grid = dim3(nblocks, 1, 1);
 }
 
-namespace {
-
 // ---- prepare's steps, in its order --------------------------------------------------------------
+// (the first one is an adaptive frame's too, rtx_adaptive.hip)
 int check_params(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p) {
     if (!c || !cams || !p) return RTX_E_INVALID;
     if (n_views < 1 || n_views > kMaxViews) return fail(c, RTX_E_INVALID, "n_views must be 1..8");
@@ -113,6 +112,8 @@ int check_params(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rend
                                           std::to_string(1u << ss) + ", the sample frame exceeds 65536 per side");
     return RTX_OK;
 }
+
+namespace {
 
 // The frame buffer (and the colour plane when asked for) of npx pixels.
 int frame_buffers(rtx_ctx* c, size_t npx, bool want_rgb) {

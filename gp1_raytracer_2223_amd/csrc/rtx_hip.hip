@@ -2052,6 +2052,287 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
     }
 }
 
+// ====================================================================== adaptive supersampling
+// The refinement of rtx_render_adaptive* (rtx.h): for each pixel rtx_classify_kernel listed
+// (AdaptiveArgs::list, y << 16 | x; their number in AdaptiveArgs::count, read from the device), the k x k
+// samples of rtx_set_supersample's contract rendered and resolved into the frame buffer; no other pixel is
+// written.
+// Lanes: a wave holds 64 / k^2 listed pixels; lane bits 0 .. n-1 are sx, the next n bits sy (n = log2 k),
+// the rest the pixel's slot, so a pixel's lanes are valid together.  Tail lanes carry the shade kernel's
+// harmless ray and are in no mask.
+// The lane's ray is render_tile's primary ray of sample (k x + sx, k y + sy) of the k W x k H frame,
+// statement for statement; from there on the body is rtx_shade_kernel's (the generic walks chosen per
+// wave, SPEC 0, no exact cull, no room planes), restated like it and for its reason.
+// The resolve is the butterfly ss_add_xor3<1>, <2>, <4>, <8>, <16>, <32> cut after 2 n levels: with this
+// layout the first n levels are the contract's adjacent-pair tree over sx and the next n the tree over
+// sy.  <4> (row_half_mirror) equals lane ^ 4 only once a quad's four lanes hold one value: it is level 3
+// of k = 4 and k = 8, after <1> and <2>, and k = 2 ends before it.  The loop is wave-uniform, so all 64
+// lanes execute every level.
+// Grid: persistent waves, wave w takes items w, w + NW, ... (an item = one wave's pixels); the host sizes
+// NW from the device's wave slots, never from W * H * k^2.  HSTK: one stack per wave of the grid.
+template <bool DEEP, bool HSTK>
+__global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_WAVES_PER_EU)
+    rtx_adaptive_kernel(const DevScene S, const AdaptiveArgs A) {
+    constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
+    __shared__ uint4 stkE[kBlockThreads / 64][kDepth];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t widx = blockIdx.x * kWavesPerBlock + wave;
+    uint4* stk = stkE[wave];
+    if constexpr (HSTK) stk = S.hstk + static_cast<size_t>(widx) * S.hstk_depth;
+    const uint32_t n = A.ss_log2, km = (1u << n) - 1u;
+    const uint32_t ppw_log2 = 6u - 2u * n;   // a wave's pixels: 16, 4, 1
+    const uint32_t count = ldc(A.count, 0);
+    const uint32_t items = (count + (1u << ppw_log2) - 1u) >> ppw_log2;
+    const uint32_t nw = gridDim.x * kWavesPerBlock;
+    for (uint32_t it = uni(widx); it < items; it += nw) {
+        // (from an opaque copy of the lane index: recomputed per item, not kept across the loop)
+        uint32_t l1 = lane;
+        asm volatile("" : "+v"(l1));
+        const uint32_t sx = l1 & km, sy = (l1 >> n) & km, slot = l1 >> (2u * n);
+        const uint32_t i = (it << ppw_log2) + slot;
+        const bool valid = i < count;
+        uint32_t xy = 0;
+        if (valid) xy = A.list[i];
+        const int px = static_cast<int>(((xy & 0xffffu) << n) | sx);
+        const int py = static_cast<int>(((xy >> 16) << n) | sy);
+
+        // ---- primary ray (Renderer.cpp:104-114), as render_tile makes it for the sample frame
+        const int W = static_cast<int>(A.width), H = static_cast<int>(A.height);
+        const float fW = static_cast<float>(W), fH = static_cast<float>(H);
+        const float cx = (2.f * div_rn(px + 0.5f, fW, A.inv_width) - 1) * A.aspect * A.fov;
+        const float cy = (1.f - div_rn(2.f * (py + 0.5f), fH, A.inv_height)) * A.fov;
+        float dx = A.right[0] * cx + A.up[0] * cy + A.forward[0] * 1.f;
+        float dy = A.right[1] * cx + A.up[1] * cy + A.forward[1] * 1.f;
+        float dz = A.right[2] * cx + A.up[2] * cy + A.forward[2] * 1.f;
+        const float dm = sqrtf(dx * dx + dy * dy + dz * dz);
+        div3_exact(dx, dy, dz, dm);   // dx /= dm; ... (Vector3::Normalize)
+        unsigned long long slow;
+        // (a tail lane keeps the shade kernel's harmless ray; it is in no mask)
+        const Ray r = make_ray(valid ? A.origin[0] : 0.f, valid ? A.origin[1] : 0.f, valid ? A.origin[2] : 0.f,
+                               valid ? dx : 1.f, valid ? dy : 1.f, valid ? dz : 1.f, valid ? 0.0001f : 1.f,
+                               valid ? FLT_MAX : 0.f, slow);
+        const unsigned long long active = ballot(valid);
+        slow |= ballot(!finite3(r.ox, r.oy, r.oz));
+        const bool slab_fast = (active & slow) == 0;
+        const bool tri_dom = fmaxf(fmaxf(fabsf(r.dx), fabsf(r.dy)), fabsf(r.dz)) <= 1.f &&
+                             fmaxf(fmaxf(fabsf(r.ox), fabsf(r.oy)), fabsf(r.oz)) <= 0x1p40f;
+        const bool fast = slab_fast && S.tri_fast && (active & ~ballot(tri_dom)) == 0;
+        const int oct = (fast && S.oct_bytes) ? batch_octant(r, active) : -1;
+        Counts cnt;   // (never counted: the walks' COUNT is off)
+
+        // ---- Scene::GetClosestHit (Scene.cpp:29-66), as rtx_shade_kernel
+        float best_t = FLT_MAX, sc_t = FLT_MAX;
+        uint32_t best_kind = 0, best_idx = 0;   // kind: 0 none, 1 sphere, 2 plane, 3 triangle; idx: BYTE offset
+        for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
+            const float4 s = ldcb16(S.spheres, opaque(k));
+            const SphereProj p = sphere_perp(s, r);
+            const unsigned long long near = ballot(!(s.w < p.perp)) & active;
+            if (!near) continue;
+            const float t = sphere_t(s, p);
+            const bool h = ((near >> lane) & 1ull) & !(t < r.tmin) & !(t > r.tmax);
+            sc_t = h ? t : sc_t;
+            const bool b = h & (t < best_t);
+            best_t = b ? t : best_t;
+            best_kind = b ? 1u : best_kind;
+            best_idx = b ? k : best_idx;
+        }
+        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+            float4 p0, p1;
+            ldcb32(S.planes, opaque(k), p0, p1);
+            const float t = plane_num(p0, p1, r) / plane_den(p1, r);
+            const bool h = valid & (t >= r.tmin) & (t < r.tmax);
+            sc_t = h ? t : sc_t;
+            const bool b = h & (t < best_t);
+            best_t = b ? t : best_t;
+            best_kind = b ? 2u : best_kind;
+            best_idx = b ? k : best_idx;
+        }
+        for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
+            const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
+            uint32_t sc_tri = 0;
+            unsigned long long unused = 0;
+            if (oct >= 0)
+                mesh_traverse<false, kSlabOct, false>(S, M, r, oct, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
+            else if (fast)
+                mesh_traverse<false, kSlabFast, false>(S, M, r, 0, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
+            else if (slab_fast)
+                mesh_traverse<false, kSlabFast, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
+                                                                           sc_tri, unused, cnt);
+            else
+                mesh_traverse<false, kSlabExact, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
+                                                                            sc_tri, unused, cnt);
+            if (sc_t < best_t) { best_t = sc_t; best_kind = 3; best_idx = sc_tri; }
+        }
+
+        // ---- hit record (rebuilt from t: ray.origin + t * ray.direction, Utils.h:62-64), as render_tile
+        const bool did = best_kind != 0;
+        float hx = 0.f, hy = 0.f, hz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+        uint32_t mat = 0;
+        if (did) {
+            hx = r.ox + r.dx * best_t; hy = r.oy + r.dy * best_t; hz = r.oz + r.dz * best_t;
+            if (best_kind == 1) {
+                const float4 s = ldcb16(S.spheres, best_idx);
+                nx = hx - s.x; ny = hy - s.y; nz = hz - s.z;
+                const float m = sqrtf(nx * nx + ny * ny + nz * nz);   // closestHit.normal.Normalize()
+                div3_exact(nx, ny, nz, m);   // nx /= m; ny /= m; nz /= m
+                mat = ldc(S.sphere_mat, best_idx >> 4);
+            } else if (best_kind == 2) {
+                float4 p0, p1;
+                ldcb32(S.planes, best_idx, p0, p1);
+                nx = p1.x; ny = p1.y; nz = p1.z;
+                mat = __float_as_uint(p0.w);
+            } else {
+                Tri T;
+                ldcb64(S.tris, best_idx, T.a, T.b, T.c, T.d);   // best_idx: byte offset
+                nx = T.a.w; ny = T.b.w; nz = T.c.w;
+                mat = __float_as_uint(T.d.x);
+            }
+        }
+
+        // ---- the reference's light loop (Renderer.cpp:128-176), as rtx_shade_kernel's
+        float shadowFactor = 1.f;
+        float fr = 0.f, fg = 0.f, fb = 0.f;
+        const unsigned long long hitmask = ballot(did);
+        const int mode = A.mode;
+        if (hitmask) {
+            // originOffset = hit.origin + hit.normal * 0.0001f (Renderer.cpp:126)
+            const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
+            const float vx = -r.dx, vy = -r.dy, vz = -r.dz;
+            for (uint32_t li = 0; li < S.n_lights; ++li) {
+                float4 L0, L1;
+                ldcb32(S.lights, opaque(li * 32u), L0, L1);
+                const int ltype = __float_as_int(L0.w);
+                const bool known = (ltype == RTX_LIGHT_POINT || ltype == RTX_LIGHT_DIRECTIONAL);
+                float lx = known ? L0.x - oox : 0.f, ly = known ? L0.y - ooy : 0.f, lz = known ? L0.z - ooz : 0.f;
+                const float mag = sqrtf(lx * lx + ly * ly + lz * lz);
+                div3_exact(lx, ly, lz, mag);
+                bool occ = false;
+                if (A.shadows) {
+                    // Scene::DoesHit (Scene.cpp:68-96) on Ray{originOffset, l, 1e-4, |l|} with `hitmask` for
+                    // `active`; `live` = lanes still without an occluder
+                    unsigned long long sslow;
+                    const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, 0.0001f, mag, sslow);
+                    sslow |= ballot(!finite3(sr.ox, sr.oy, sr.oz));
+                    const bool s_slab_fast = (hitmask & sslow) == 0;
+                    const bool s_tri_dom = fmaxf(fmaxf(fabsf(sr.dx), fabsf(sr.dy)), fabsf(sr.dz)) <= 1.f &&
+                                           fmaxf(fmaxf(fabsf(sr.ox), fabsf(sr.oy)), fabsf(sr.oz)) <= 0x1p40f;
+                    const bool sfast = s_slab_fast && S.tri_fast && (hitmask & ~ballot(s_tri_dom)) == 0;
+                    const int soct = (sfast && S.oct_bytes) ? batch_octant(sr, hitmask) : -1;
+                    unsigned long long live = hitmask;
+                    for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
+                        const float4 s = ldcb16(S.spheres, opaque(k));
+                        const SphereProj p = sphere_perp(s, sr);
+                        const unsigned long long near = ballot(!(s.w < p.perp)) & live;
+                        if (!near) continue;
+                        const float t = sphere_t(s, p);
+                        live &= ~(near & ballot(!(t < sr.tmin)) & ballot(!(t > sr.tmax)));
+                    }
+                    // (tmin = 1e-4 > 0: plane_cand's domain is a finite tmax = |l| in every hit lane)
+                    const bool pl_dom = (hitmask & ~ballot(sr.tmin > 0.f && fabsf(sr.tmax) < INFINITY)) == 0;
+                    if (pl_dom) {
+                        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+                            float4 p0, p1;
+                            ldcb32(S.planes, opaque(k), p0, p1);
+                            const float num = plane_num(p0, p1, sr), den = plane_den(p1, sr);
+                            const unsigned long long cand = plane_cand(num, den, sr.tmax) & live;
+                            if (!cand) continue;   // also taken once no lane is live
+                            const float t = num / den;
+                            live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax) & cand);
+                        }
+                    } else {
+                        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+                            float4 p0, p1;
+                            ldcb32(S.planes, opaque(k), p0, p1);
+                            const float t = plane_num(p0, p1, sr) / plane_den(p1, sr);
+                            live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax));
+                        }
+                    }
+                    for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
+                        if (!live) break;
+                        float st = 0.f;
+                        uint32_t stri = 0;
+                        const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
+                        if (soct >= 0)
+                            mesh_traverse<true, kSlabOct, false>(S, M, sr, soct, live, lane, stk, nullptr, st, stri, live, cnt);
+                        else if (sfast)
+                            mesh_traverse<true, kSlabFast, false>(S, M, sr, 0, live, lane, stk, nullptr, st, stri, live, cnt);
+                        else if (s_slab_fast)
+                            mesh_traverse<true, kSlabFast, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
+                                                                                      st, stri, live, cnt);
+                        else
+                            mesh_traverse<true, kSlabExact, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
+                                                                                       st, stri, live, cnt);
+                    }
+                    occ = did & !((live >> lane) & 1ull);
+                }
+                if (!did) continue;
+                if (occ) {
+                    shadowFactor *= 0.95f;
+                    continue;
+                }
+                if (mode == RTX_MODE_COMBINED || mode == RTX_MODE_RADIANCE) {
+                    // LightUtils::GetRadiance (Utils.h:355-369) at hit.origin
+                    float s = 0.f;
+                    bool any = true;
+                    if (ltype == RTX_LIGHT_POINT) {
+                        const float ex = L0.x - hx, ey = L0.y - hy, ez = L0.z - hz;
+                        s = L1.w / (ex * ex + ey * ey + ez * ez);
+                    } else if (ltype == RTX_LIGHT_DIRECTIONAL) {
+                        s = L1.w;
+                    } else {
+                        any = false;
+                    }
+                    const float rr = any ? L1.x * s : 0.f, rg = any ? L1.y * s : 0.f, rb = any ? L1.z * s : 0.f;
+                    if (mode == RTX_MODE_RADIANCE) {
+                        fr += rr; fg += rg; fb += rb;
+                    } else {
+                        const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
+                        const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
+                        fr += (rr * oa) * br.r; fg += (rg * oa) * br.g; fb += (rb * oa) * br.b;
+                    }
+                } else if (mode == RTX_MODE_OBSERVED_AREA) {
+                    const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
+                    fr += oa; fg += oa; fb += oa;
+                } else if (mode == RTX_MODE_BRDF) {
+                    const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
+                    fr += br.r; fg += br.g; fb += br.b;
+                }
+            }
+            if (did) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
+        }
+        // ColorRGB::MaxToOne (ColorRGB.h:12-17)
+        const float mv = smax(fr, smax(fg, fb));
+        if (mv > 1.f) { fr /= mv; fg /= mv; fb /= mv; }
+
+        // ---- the box filter: the sx tree, then the sy tree, times the exact 1 / (k * k)
+        ss_add_xor3<1>(fr, fg, fb);
+        ss_add_xor3<2>(fr, fg, fb);
+        if (n >= 2) {
+            ss_add_xor3<4>(fr, fg, fb);
+            ss_add_xor3<8>(fr, fg, fb);
+        }
+        if (n == 3) {
+            ss_add_xor3<16>(fr, fg, fb);
+            ss_add_xor3<32>(fr, fg, fb);
+        }
+        const float w = __uint_as_float((127u - 2u * n) << 23);   // 2^(-2 log2 k)
+        fr *= w; fg *= w; fb *= w;
+        // the pixel's sample 0 stores; its list entry is read again from an opaque copy of the lane index,
+        // so that neither it nor the sample coordinates stay in registers through the body above
+        uint32_t l2 = lane;
+        asm volatile("" : "+v"(l2));
+        const uint32_t i2 = (it << ppw_log2) + (l2 >> (2u * n));
+        if (i2 < count && (l2 & ((1u << (2u * n)) - 1u)) == 0) {
+            const uint32_t xy2 = A.list[i2];
+            const size_t o = static_cast<size_t>(xy2 >> 16) * A.out_width + (xy2 & 0xffffu);
+            A.out_px[o] = (q8(fr) << A.rshift) | (q8(fg) << A.gshift) | (q8(fb) << A.bshift) | A.amask;
+            if (A.out_rgb) {
+                A.out_rgb[3 * o] = fr; A.out_rgb[3 * o + 1] = fg; A.out_rgb[3 * o + 2] = fb;
+            }
+        }
+    }
+}
+
 // ====================================================================== launches
 namespace {
 
@@ -2154,6 +2435,12 @@ void launch_shade(bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene
     if (hstk) hipLaunchKernelGGL((rtx_shade_kernel<true, true>), grid, dim3(kBlockThreads), 0, s, d, Q);
     else if (deep) hipLaunchKernelGGL((rtx_shade_kernel<true, false>), grid, dim3(kBlockThreads), 0, s, d, Q);
     else hipLaunchKernelGGL((rtx_shade_kernel<false, false>), grid, dim3(kBlockThreads), 0, s, d, Q);
+}
+
+void launch_adaptive(bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene& d, const AdaptiveArgs& A) {
+    if (hstk) hipLaunchKernelGGL((rtx_adaptive_kernel<true, true>), grid, dim3(kBlockThreads), 0, s, d, A);
+    else if (deep) hipLaunchKernelGGL((rtx_adaptive_kernel<true, false>), grid, dim3(kBlockThreads), 0, s, d, A);
+    else hipLaunchKernelGGL((rtx_adaptive_kernel<false, false>), grid, dim3(kBlockThreads), 0, s, d, A);
 }
 
 }  // namespace rtxh

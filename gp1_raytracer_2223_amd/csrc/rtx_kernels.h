@@ -1,6 +1,6 @@
 // rtx_kernels.h — device layout of the uploaded scene and the per-frame launch record.
-// Shared by the kernels (rtx_hip.hip, rtx_cull_records.hip, rtx_sched.hip) and the host units
-// that fill them in (rtx_upload.hip, rtx_frame.hip, rtx_aov.hip, rtx_query.hip, rtx_shade.hip).
+// Shared by the kernels (rtx_hip.hip, rtx_cull_records.hip, rtx_sched.hip, rtx_adaptive.hip) and the host
+// units that fill them in (rtx_upload.hip, rtx_frame.hip, rtx_aov.hip, rtx_query.hip, rtx_adaptive.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -273,6 +273,40 @@ struct ShadeArgs {
     uint32_t n;
     int32_t mode, shadows;
     uint32_t rshift, gshift, bshift, amask;
+    uint32_t* __restrict__ out_px;
+    float* __restrict__ out_rgb;
+};
+
+// Adaptive supersampling (rtx_render_adaptive*): after the plain frame, rtx_classify_kernel
+// (rtx_adaptive.hip) lists the pixels of the contrast mask E, and rtx_adaptive_kernel (rtx_hip.hip) renders
+// and resolves k x k samples for the listed pixels only.
+// The classifier: one lane per pixel of the width x height uint32 plane `px`; a pixel is listed, as
+// y << 16 | x, when some in-frame 4-neighbour differs from it by more than `tau` in a channel read through
+// the shifts.  `count` (zeroed before the launch) ends as |E|; `list` holds width * height entries; the
+// list's order is whatever the waves' atomics made it.
+constexpr int kClassifyThreads = 256;
+struct ClassifyArgs {
+    const uint32_t* __restrict__ px;
+    uint32_t width, height;
+    uint32_t tau;
+    uint32_t rshift, gshift, bshift;
+    uint32_t* __restrict__ list;
+    uint32_t* __restrict__ count;
+};
+// The refinement: persistent waves over the list, 64 >> 2 ss_log2 pixels per wave and step.  aspect, inv_*,
+// width and height are the k*out_width x k*out_height sample frame's, as FrameArgs' of a supersampled
+// frame; out_px / out_rgb (null: the frame has no colour plane) are the out_width-pixel rows of the frame
+// buffer, of which only listed pixels are written.
+struct AdaptiveArgs {
+    float origin[3], right[3], up[3], forward[3], fov;
+    float aspect, inv_width, inv_height;
+    uint32_t width, height;
+    uint32_t out_width;
+    uint32_t ss_log2;   // 1..3
+    int32_t mode, shadows;
+    uint32_t rshift, gshift, bshift, amask;
+    const uint32_t* __restrict__ list;
+    const uint32_t* __restrict__ count;
     uint32_t* __restrict__ out_px;
     float* __restrict__ out_rgb;
 };

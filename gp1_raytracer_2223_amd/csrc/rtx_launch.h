@@ -27,5 +27,9 @@ void launch_query(bool any, bool deep, bool hstk, dim3 grid, hipStream_t s, cons
                   const rtxd::QueryArgs& Q);
 // Shaded rays (rtx_shade_kernel): the same three stacks and grid.
 void launch_shade(bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d, const rtxd::ShadeArgs& Q);
+// Adaptive refinement (rtx_adaptive_kernel): the same three stacks; grid.x * kWavesPerBlock persistent
+// waves stride over the listed pixels, whose number the kernel reads from the device.
+void launch_adaptive(bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
+                     const rtxd::AdaptiveArgs& A);
 
 }  // namespace rtxh

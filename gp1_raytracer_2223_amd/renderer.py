@@ -93,6 +93,36 @@ class DeviceContext:
         abi.check(rc, "rtx_render", self.h)
         return px, rgb
 
+    def render_adaptive(self, cam: abi.Camera, params: abi.RenderParams, k: int, threshold: int,
+                        want_rgb: bool = True):
+        """Adaptive supersampling (rtx_render_adaptive), blocking: the plain frame with k x k samples
+        (k = 2, 4, 8) for the pixels that differ from a 4-neighbour by more than `threshold` (0..255) in a
+        channel; (pixels, rgb) like render()."""
+        n = params.width * params.height
+        px = np.zeros(n, np.uint32)
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.lib.rtx_render_adaptive(self.h, C.byref(cam), C.byref(params), int(k), int(threshold),
+                                          px.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_render_adaptive", self.h)
+        return px, rgb
+
+    def render_adaptive_async(self, cam, params, k: int, threshold: int, want_rgb: bool = False) -> None:
+        abi.check(self.lib.rtx_render_adaptive_async(self.h, C.byref(cam), C.byref(params), int(want_rgb), int(k),
+                                                     int(threshold)), "rtx_render_adaptive_async", self.h)
+
+    def adaptive_refined(self) -> int:
+        """The pixels the last adaptive frame refined (rtx_adaptive_refined; waits for the stream)."""
+        n = C.c_uint32()
+        abi.check(self.lib.rtx_adaptive_refined(self.h, C.byref(n)), "rtx_adaptive_refined", self.h)
+        return n.value
+
+    def time_adaptive_frames(self, cam, params, k: int, threshold: int, iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_adaptive_frames(self.h, C.byref(cam), C.byref(params), int(k), int(threshold),
+                                                    int(iters), C.byref(ms)), "rtx_time_adaptive_frames", self.h)
+        return ms.value
+
     def render_async(self, cam, params, want_rgb=False):
         abi.check(self.lib.rtx_render_async(self.h, C.byref(cam), C.byref(params), int(want_rgb)),
                   "rtx_render_async", self.h)
@@ -434,7 +464,7 @@ class DeviceAnimation:
 
 class Renderer:
     def __init__(self, width: int, height: int, device: int = 0, stripe: tuple[int, int, int] | None = None,
-                 pixel_format=abi.XRGB8888, supersample: int = 1):
+                 pixel_format=abi.XRGB8888, supersample: int = 1, adaptive: tuple[int, int] | None = None):
         self.m_Width, self.m_Height = int(width), int(height)
         self.m_AspectRatio = self.m_Width / float(self.m_Height)
         self.m_CurrentLightingMode = LightingMode.Combined
@@ -445,7 +475,9 @@ class Renderer:
         if supersample != 1:
             self.ctx.set_supersample(supersample)
         self.supersample = int(supersample)
-        self._scene_ref = None    # weakref to the uploaded HostScene
+        # (k, threshold): Render takes k x k samples for the pixels that alias only (RenderAdaptive)
+        self.adaptive = (int(adaptive[0]), int(adaptive[1])) if adaptive is not None else None
+        self._scene_ref = None   # weakref to the uploaded HostScene
         self._scene_gen = -1      # its generation at upload
         self.buffer = np.zeros(self.m_Width * self.m_Height, np.uint32)
         self.rgb = None
@@ -490,7 +522,10 @@ class Renderer:
         return self.ctx.shade_rays(rays, self.params())
 
     def Render(self, scene: HostScene, upload: bool = True, want_rgb: bool = False) -> np.ndarray:
-        """Renderer::Render (Renderer.cpp:34-98): blocking; fills self.buffer."""
+        """Renderer::Render (Renderer.cpp:34-98): blocking; fills self.buffer.  A renderer made with
+        `adaptive=(k, threshold)` renders the adaptive frame (RenderAdaptive)."""
+        if self.adaptive is not None:
+            return self.RenderAdaptive(scene, *self.adaptive, upload=upload, want_rgb=want_rgb)
         s, cam = self._view(scene, upload)
         n = self.m_Width * self.m_Height
         rgb = np.zeros(3 * n, np.float32) if want_rgb else None
@@ -498,6 +533,21 @@ class Renderer:
                                      self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
                                      rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
         abi.check(rc, "rtx_render", self.ctx.h)
+        self.rgb = rgb
+        return self.buffer
+
+    def RenderAdaptive(self, scene: HostScene, k: int, threshold: int, upload: bool = True,
+                       want_rgb: bool = False) -> np.ndarray:
+        """Render with adaptive supersampling (rtx_render_adaptive; not in the reference's Renderer):
+        k x k samples for the pixels whose 8-bit colour differs from a 4-neighbour's by more than
+        `threshold` in a channel, the plain pixel elsewhere.  Blocking; fills self.buffer."""
+        _, cam = self._view(scene, upload)
+        n = self.m_Width * self.m_Height
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.ctx.lib.rtx_render_adaptive(self.ctx.h, C.byref(cam), C.byref(self.params()), int(k), int(threshold),
+                                              self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_render_adaptive", self.ctx.h)
         self.rgb = rgb
         return self.buffer
 

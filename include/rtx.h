@@ -30,7 +30,8 @@
  * and the scheduler's / exact cull's internals are in rtx_diag.h; the environment knobs the library
  * reads are listed in INTEGRATION.md (none of them changes a pixel).  In csrc/ the entry points
  * live by topic: rtx_context.hip, rtx_upload.hip, rtx_frame.hip, rtx_aov.hip (the hit pass),
- * rtx_query.hip (ray queries and shaded rays), rtx_group.cpp and rtx_anim_host.hip; the render kernel is rtx_hip.hip.
+ * rtx_query.hip (ray queries and shaded rays), rtx_adaptive.hip (adaptive supersampling), rtx_group.cpp and
+ * rtx_anim_host.hip; the render kernel is rtx_hip.hip.
  */
 #ifndef RTX_H_
 #define RTX_H_
@@ -214,6 +215,40 @@ int rtx_render_views_async(rtx_ctx* ctx, const rtx_camera* cams, int n_views,
  * k*height may not exceed 65536 (rtx_render* then returns RTX_E_INVALID).  Any other k returns
  * RTX_E_INVALID and leaves the factor as it was.  The work counters count the sample frame. */
 int rtx_set_supersample(rtx_ctx* ctx, uint32_t k);
+/* Adaptive supersampling: k x k samples for the pixels that alias only.  For a width x height frame, a
+ * factor k in {2, 4, 8} and a threshold tau in [0, 255]:
+ *   P  is the plain frame, what rtx_render gives with factor 1.
+ *   S  is the supersampled frame of factor k exactly as rtx_set_supersample defines it: sample
+ *      (k x + sx, k y + sy) is the reference's pixel of the k*width x k*height frame; per channel the
+ *      adjacent-pair tree over sx, then over sy, times 1/(k*k); then the 8-bit quantisation with
+ *      params->format.
+ *   Channel c of a pixel word is (word >> shift_c) & 255 with params->format.
+ *   E(x, y) holds iff some 4-neighbour (x +- 1, y) or (x, y +- 1) inside the frame has
+ *      |c(P(x, y)) - c(P(neighbour))| > tau for some channel c: integer only, symmetric (both pixels
+ *      of a pair are refined), and independent of the colour plane.
+ *   The adaptive frame is A = S where E holds, else P, in both planes.
+ * tau = 255 gives P; a tau that puts every pixel in E gives S.  The mask comes from the device's own P:
+ * the reference's P bit for bit wherever the reference calls no powf, the device's words elsewhere.
+ *
+ * rtx_render_adaptive_async queues the plain frame exactly as rtx_render_async does (it is a frame for
+ * the schedule and every policy), then, behind a pending split chain, the classification of the frame
+ * buffer and the refinement of the classified pixels, and returns; nothing waits on the host, and the
+ * number of refined pixels never leaves the device.  Afterwards the frame buffer holds A, and the
+ * last-frame record is the plain frame's: rtx_download, rtx_gather_async and rtx_device_buffers work
+ * unchanged.  The hit-pass planes and their record are not touched.  rtx_render_adaptive is the async
+ * call followed by rtx_download.  rtx_adaptive_refined waits for the context stream and gives |E| of
+ * the last adaptive frame.
+ * Errors (the context renders on after each): k not 2, 4 or 8, threshold > 255, anything rtx_render
+ * rejects, k*width or k*height above 65536: RTX_E_INVALID; no scene uploaded (for rtx_adaptive_refined:
+ * no adaptive frame yet): RTX_E_STATE; a supersample factor other than 1 on the context (the mode
+ * carries its own) and stripe_step > 1 (a stripe's neighbour rows belong to another context):
+ * RTX_E_UNSUPPORTED.  Views, rtx_group_* and stripes have no adaptive form. */
+int rtx_render_adaptive_async(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_params* params,
+                              int want_rgb, uint32_t k, uint32_t threshold);
+int rtx_render_adaptive(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_params* params,
+                        uint32_t k, uint32_t threshold, uint32_t* out_pixels, float* out_rgb);
+/* waits for the context stream; the number of refined pixels (|E|) of the last adaptive frame */
+int rtx_adaptive_refined(rtx_ctx* ctx, uint32_t* n_refined);
 int rtx_synchronize(rtx_ctx* ctx);
 /* Copy the context's frame buffer (rows owned by the last render) to host memory. */
 int rtx_download(rtx_ctx* ctx, uint32_t* out_pixels, float* out_rgb);

@@ -37,6 +37,11 @@ int rtx_time_ray_queries(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, int wh
  * mean device time of one in ms. */
 int rtx_time_shade_rays(rtx_ctx* ctx, const rtx_ray* d_rays, uint32_t n, const rtx_render_params* params,
                         uint32_t* d_pixels, float* d_rgb, int iters, float* mean_ms);
+/* The same for rtx_render_adaptive_async(cam, params, 0, k, threshold) (rtx.h): `iters` back-to-back
+ * adaptive frames (plain frame, classification, refinement; no colour plane, as rtx_time_frames), the
+ * mean device time of one in ms. */
+int rtx_time_adaptive_frames(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_params* params, uint32_t k,
+                             uint32_t threshold, int iters, float* mean_ms);
 /* Bytes of HBM the uploaded scene image occupies. */
 int rtx_scene_bytes(const rtx_ctx* ctx, uint64_t* bytes);
 /* Diagnostics: copy the context's current scene image (DESIGN.md §2 layout) after its queued

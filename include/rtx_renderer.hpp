@@ -49,6 +49,26 @@ public:
         Render(cam);
     }
 
+    // Render with adaptive supersampling (rtx_render_adaptive; not in the reference): k x k samples
+    // (k = 2, 4, 8) for the pixels whose 8-bit colour differs from a 4-neighbour's by more than `threshold`
+    // (0..255) in a channel, the plain pixel elsewhere.  AdaptiveRefined: how many pixels that was.
+    void RenderAdaptive(const rtx_camera& cam, uint32_t k, uint32_t threshold) {
+        const rtx_render_params p = Params();
+        Check(rtx_render_adaptive(m_Ctx, &cam, &p, k, threshold, m_Pixels.data(), nullptr), "rtx_render_adaptive");
+    }
+    void RenderAdaptive(rtx_host_scene* scene, uint32_t k, uint32_t threshold, bool upload = true) {
+        rtx_scene s;
+        rtx_camera cam;
+        Check(rtx_host_scene_view(scene, &s, &cam), "rtx_host_scene_view");
+        if (upload) Upload(s);
+        RenderAdaptive(cam, k, threshold);
+    }
+    uint32_t AdaptiveRefined() {
+        uint32_t n = 0;
+        Check(rtx_adaptive_refined(m_Ctx, &n), "rtx_adaptive_refined");
+        return n;
+    }
+
     // The hit pass of the frame Render would render (rtx_render_aov; not in the reference): what every
     // pixel's primary ray hit, the planes of `mask` filled and the others left empty (rtx.h gives the
     // values: depth, normal, material index, primitive kind << 30 | index).
