@@ -184,7 +184,8 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_trace_rays", "rtx_occluded", "rtx_trace_rays_device", "rtx_occluded_device",
                "rtx_time_ray_queries", "rtx_room_info", "rtx_schedule_xcd_order",
                "rtx_shade_rays", "rtx_shade_rays_device", "rtx_time_shade_rays",
-               "rtx_render_adaptive_async", "rtx_render_adaptive", "rtx_adaptive_refined", "rtx_time_adaptive_frames"]
+               "rtx_render_adaptive_async", "rtx_render_adaptive", "rtx_adaptive_refined", "rtx_time_adaptive_frames",
+               "rtx_shade_aov_async", "rtx_shade_aov", "rtx_time_shade_aov"]
 
 
 def load_hip() -> C.CDLL:
@@ -350,6 +351,13 @@ def load_hip() -> C.CDLL:
             lib.rtx_time_adaptive_frames.argtypes = [VP, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
                                                      C.c_uint32, C.c_int, C.POINTER(C.c_float)]
             lib.rtx_time_adaptive_frames.restype = C.c_int
+        if hasattr(lib, "rtx_shade_aov"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_shade_aov_async.argtypes = [VP, C.POINTER(RenderParams), C.c_int]
+            lib.rtx_shade_aov_async.restype = C.c_int
+            lib.rtx_shade_aov.argtypes = [VP, C.POINTER(RenderParams), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+            lib.rtx_shade_aov.restype = C.c_int
+            lib.rtx_time_shade_aov.argtypes = [VP, C.POINTER(RenderParams), C.c_int, C.c_int, C.POINTER(C.c_float)]
+            lib.rtx_time_shade_aov.restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]
             lib.rtx_scene_image.restype = C.c_int

@@ -4,7 +4,7 @@
 //
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
-//              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T]
+//              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T] [--deferred]
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -23,6 +23,9 @@
 // --adaptive K,T (single frames only: not with --benchmark, --sequence, --aov, --rays or --ss above 1) renders
 // the frame with adaptive supersampling (rtx_render_adaptive): K x K samples (K = 2, 4 or 8) for the pixels
 // that differ from a 4-neighbour by more than T (0..255) in an 8-bit channel, and prints how many that was.
+// --deferred (single frames only: not with --benchmark, --sequence, --rays, --adaptive or --ss above 1) makes the
+// image from one hit pass plus deferred shading (rtx_render_aov, rtx_shade_aov) instead of a frame: the same
+// BMP, and with --aov the same planes, from one primary traversal.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -318,7 +321,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
                              "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
-                             "[--aov prefix] [--rays file] [--adaptive K,T]\n",
+                             "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred]\n",
                      argv[0]);
         return 2;
     }
@@ -327,7 +330,7 @@ int main(int argc, char** argv) {
     int ad_k = 0, ad_t = 0;   // --adaptive K,T (0: not asked for)
     std::vector<float> seq;
     float t = -1.f;
-    bool shadows = true, device_update = false;
+    bool shadows = true, device_update = false, deferred = false;
     int pos = 0;
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i];
@@ -345,6 +348,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--inflight" && i + 1 < argc) inflight = std::max(1, std::min(8, std::atoi(argv[++i])));
         else if (a == "--device-update") device_update = true;
+        else if (a == "--deferred") deferred = true;
         else if (a == "--ss") {   // checked here: a bad factor ends the program before any device work
             ss = i + 1 < argc ? std::atoi(argv[++i]) : 0;
             if (ss != 1 && ss != 2 && ss != 4 && ss != 8) {
@@ -367,6 +371,11 @@ int main(int argc, char** argv) {
         else if (a == "--benchmark") bench = (i + 1 < argc && std::atoi(argv[i + 1]) > 0) ? std::atoi(argv[++i]) : 10;
         else if (pos == 0) { W = std::atoi(argv[i]); ++pos; }
         else if (pos == 1) { H = std::atoi(argv[i]); ++pos; }
+    }
+    if (deferred && (bench || !seq.empty() || !rays_file.empty() || ad_k || ss > 1)) {   // before any device work
+        std::fprintf(stderr, "--deferred shades a single frame's hit pass: not with --benchmark, --sequence, --rays, "
+                             "--adaptive or --ss above 1\n");
+        return 2;
     }
     if (!aov.empty() && (bench || !seq.empty())) {
         std::fprintf(stderr, "--aov writes the planes of a single frame: not with --benchmark or --sequence\n");
@@ -443,6 +452,18 @@ int main(int argc, char** argv) {
         } else if (ad_k) {   // the adaptive frame, through the same BMP writer
             r.RenderAdaptive(hs, static_cast<uint32_t>(ad_k), static_cast<uint32_t>(ad_t), true);
             std::printf("refined %u of %d pixels\n", r.AdaptiveRefined(), W * H);
+        } else if (deferred) {   // one hit pass, shaded from its planes; --aov writes the same pass
+            const rtx::Renderer::AovFrame f = r.RenderAov(hs, RTX_AOV_ALL, true);
+            r.ShadeAov();
+            if (!aov.empty()) {
+                if (!write_plane(aov + "_depth.f32", f.depth) || !write_plane(aov + "_normal.f32", f.normal) ||
+                    !write_plane(aov + "_material.u32", f.material) || !write_plane(aov + "_primitive.u32", f.primitive)) {
+                    std::fprintf(stderr, "cannot write %s_*\n", aov.c_str());
+                    rc = 1;
+                } else {
+                    std::printf("wrote %s_depth.f32 _normal.f32 _material.u32 _primitive.u32\n", aov.c_str());
+                }
+            }
         } else {
             r.Render(hs, true);
             auto t0 = Clock::now();

@@ -82,6 +82,16 @@ int aov_launch(rtx_ctx* c, const FrameArgs& F, dim3 grid) {
     return RTX_OK;
 }
 
+// The record of the pass just queued (rtx_ctx::aov_last*): its shape for the copies, and its cameras and
+// the scene's material count for deferred shading (rtx_deferred.hip).
+void aov_remember(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p, uint32_t mask) {
+    c->aov_last = *p;
+    c->aov_last_views = n_views;
+    c->aov_last_mask = mask;
+    for (int v = 0; v < n_views; ++v) c->aov_last_cams[v] = cams[v];
+    c->aov_last_materials = c->dev.n_materials;
+}
+
 // ... of the last hit pass (rtx_ctx::aov_last*)
 int queue_aov_copy(rtx_ctx* c, const rtx_aov_planes* out) {
     if (!c || !out) return RTX_E_INVALID;
@@ -110,9 +120,7 @@ extern "C" int rtx_render_aov_async(rtx_ctx* c, const rtx_camera* cams, int n_vi
     if (rc != RTX_OK) return rc;
     rc = aov_launch(c, F, grid);
     if (rc != RTX_OK) return rc;
-    c->aov_last = *p;
-    c->aov_last_views = n_views;
-    c->aov_last_mask = mask;
+    aov_remember(c, cams, n_views, p, mask);
     return RTX_OK;
 }
 
@@ -160,8 +168,6 @@ extern "C" int rtx_time_aov_frames(rtx_ctx* c, const rtx_camera* cam, const rtx_
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     *mean_ms = ms / static_cast<float>(iters);
-    c->aov_last = *p;
-    c->aov_last_views = 1;
-    c->aov_last_mask = mask;
+    aov_remember(c, cam, 1, p, mask);
     return RTX_OK;
 }

@@ -238,6 +238,10 @@ struct rtx_ctx {
     rtx_render_params aov_last{};
     int aov_last_views = 1;
     uint32_t aov_last_mask = 0;   // 0: no pass yet
+    // ... and, for deferred shading (rtx_shade_aov*, rtx_deferred.hip), the pass's cameras and the
+    // number of materials of the scene it traced (its material plane's indices lie below it)
+    rtx_camera aov_last_cams[kMaxViews] = {};
+    uint32_t aov_last_materials = 0;
     // Ray queries and shaded rays (rtx_trace_rays, rtx_occluded, rtx_shade_rays: rtx_query.hip): the host
     // variants' staging buffer in HBM, the rays and then every result array of one call; its cap = the
     // rays it holds
@@ -300,6 +304,13 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
             dim3& grid);
 // prepare's first step: what rtx_render* rejects of a frame's arguments, before anything is queued
 int check_params(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p);
+// The head of a launch shape's schedule key: the tile set (size, views, stripes), before the scene and mode
+std::string tiles_key(uint32_t width, uint32_t height, int n_views, uint32_t stripe_rows, uint32_t stripe_first,
+                      uint32_t stripe_step);
+// ... its buffer step: the frame buffer (and the colour plane when asked for) of npx pixels
+int frame_buffers(rtx_ctx* c, size_t npx, bool want_rgb);
+// The kSpecVariants index of the first variant the facts satisfy (-1: none, the generic kernel).
+int spec_variant(int facts);
 int ensure_hbm_stacks(rtx_ctx* c, uint32_t groups);
 int launch(rtx_ctx* c, const FrameArgs& F, dim3 grid, int count);
 void remember(rtx_ctx* c, const rtx_render_params* p, int n_views, bool rgb);

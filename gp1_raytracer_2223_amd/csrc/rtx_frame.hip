@@ -11,7 +11,7 @@
 
 using namespace rtxh;
 
-namespace {
+namespace rtxh {
 
 // Index into kSpecVariants of the first variant the facts satisfy, -1 for none: every kind the
 // scene references is compiled into the variant, and every other fact the variant assumes holds.
@@ -22,10 +22,6 @@ int spec_variant(int facts) {
     }
     return -1;
 }
-
-}  // namespace
-
-namespace rtxh {
 
 // The launch record of a frame of `n_views` cameras: the cameras (with their cull bounds and room-plane
 // numerators), the frame `sp` the kernel renders (the sample frame of a supersampled one, `p` otherwise),
@@ -91,6 +87,14 @@ void frame_shape(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rend
     grid = dim3(nblocks, 1, 1);
 }
 
+// The head of a launch shape's key (rtx_ctx::sched_key): the launches that share it have the same wave
+// tiles, so one's dispatch order is a permutation of the other's.
+std::string tiles_key(uint32_t width, uint32_t height, int n_views, uint32_t stripe_rows, uint32_t stripe_first,
+                      uint32_t stripe_step) {
+    return std::to_string(width) + "x" + std::to_string(height) + "v" + std::to_string(n_views) + "s" +
+           std::to_string(stripe_rows) + "/" + std::to_string(stripe_first) + "/" + std::to_string(stripe_step) + "g";
+}
+
 // ---- prepare's steps, in its order --------------------------------------------------------------
 // (the first one is an adaptive frame's too, rtx_adaptive.hip)
 int check_params(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_params* p) {
@@ -113,8 +117,6 @@ int check_params(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rend
     return RTX_OK;
 }
 
-namespace {
-
 // The frame buffer (and the colour plane when asked for) of npx pixels.
 int frame_buffers(rtx_ctx* c, size_t npx, bool want_rgb) {
     if (npx > c->d_px.cap) {
@@ -127,6 +129,8 @@ int frame_buffers(rtx_ctx* c, size_t npx, bool want_rgb) {
     }
     return RTX_OK;
 }
+
+namespace {
 
 // Cost-ordered dispatch (see the kernel): one order/cost pair per launch shape, for ntiles tiles.
 int sched_buffers(rtx_ctx* c, uint32_t ntiles) {
@@ -295,10 +299,9 @@ int prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_render_pa
     F.out_rgb = want_rgb ? c->d_rgb.get() : nullptr;
     F.counters = c->d_counters;
     if (const int rc = sched_buffers(c, F.n_tiles); rc != RTX_OK) return rc;
-    const std::string key = std::to_string(sp.width) + "x" + std::to_string(sp.height) + "v" + std::to_string(n_views) +
-                            "s" + std::to_string(sp.stripe_rows) + "/" + std::to_string(p->stripe_first) + "/" +
-                            std::to_string(p->stripe_step) + "g" + c->facts.sig + "m" +
-                            std::to_string(p->lighting_mode) + std::to_string(p->shadows_enabled) + "k" + std::to_string(ss);
+    const std::string key = tiles_key(sp.width, sp.height, n_views, sp.stripe_rows, p->stripe_first, p->stripe_step) +
+                            c->facts.sig + "m" + std::to_string(p->lighting_mode) + std::to_string(p->shadows_enabled) +
+                            "k" + std::to_string(ss);
     // Motion mode: a camera differs from the previous frame's (any field), so the tile costs go
     // stale quickly.  For kMotionFrames frames from then on, every frame is measured whose previous
     // measurement has completed (adopted without waiting), and split tiles are costed by their

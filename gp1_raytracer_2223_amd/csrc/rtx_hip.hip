@@ -891,6 +891,9 @@ __device__ __forceinline__ uint32_t q8(float c) {
 // The hit pass (rtx_render_aov*, FrameArgs::aov_*) is a launch of its own:
 //   PHASE 7  grid (tiles):                 PHASE 0 up to the hit record, whose t, normal, material and
 //                                          primitive it writes into the requested planes; no light loop
+// Deferred shading (rtx_shade_aov*) is the other half, also one launch:
+//   PHASE 8  grid (tiles):                 the hit record read from a stored hit pass's four planes (no
+//                                          closest-hit work), then PHASE 0 from originOffset on
 // Every phase recomputes the primary ray and the sphere/plane hits with the same code, so
 // all of them see bit-identical values.
 // DEEP: the variant for scenes whose BVH is kStackDepth or more levels deep (a DFS stack of
@@ -1050,8 +1053,8 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     float best_t = FLT_MAX, sc_t = FLT_MAX;
     // kind: 0 none, 1 sphere, 2 plane, 3 triangle; best_idx: the record's BYTE offset
     uint32_t best_kind = 0, best_idx = 0;
-    // (PHASE 5 reads the hit record PHASE 4 wrote: no closest-hit work)
-    for (uint32_t i = 0; i < ((PHASE == 5 || PHASE == 6) ? 0u : n_sph * 16u); i += 16u) {
+    // (PHASE 5 reads the hit record PHASE 4 wrote, PHASE 8 the hit pass's: no closest-hit work)
+    for (uint32_t i = 0; i < ((PHASE == 5 || PHASE == 6 || PHASE == 8) ? 0u : n_sph * 16u); i += 16u) {
         const float4 s = ldcb16(S.spheres, opaque(i));
         if (COUNT && valid) cnt.c[kSphere]++;
         const SphereProj q = sphere_perp(s, vr);
@@ -1070,7 +1073,8 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     // divisor domain with its RN(1/d) already in the ray, so when the host found the numerators
     // inside theirs too, t = RN(a / d) costs 3 VALU instead of the 11 of IEEE `/`.
     const bool room_p =
-        kRoom && PHASE != 5 && PHASE != 6 && !RTX_ABL_PPLANE && (active & ~ballot(finite3(vr.ox, vr.oy, vr.oz))) == 0;
+        kRoom && PHASE != 5 && PHASE != 6 && PHASE != 8 && !RTX_ABL_PPLANE &&
+        (active & ~ballot(finite3(vr.ox, vr.oy, vr.oz))) == 0;
     if (room_p) {
         // the view's record through a readfirstlane'd index: scalar loads (the view index
         // itself stays a VGPR value; making it uniform everywhere measured slower)
@@ -1095,7 +1099,8 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
             best_idx = b ? static_cast<uint32_t>(k * 32) : best_idx;
         });
     }
-    for (uint32_t i = 0; i < ((RTX_ABL_PPLANE || room_p || PHASE == 5 || PHASE == 6) ? 0u : n_pl * 32u); i += 32u) {
+    for (uint32_t i = 0; i < ((RTX_ABL_PPLANE || room_p || PHASE == 5 || PHASE == 6 || PHASE == 8) ? 0u : n_pl * 32u);
+         i += 32u) {
         float4 p0, p1;
         ldcb32(S.planes, opaque(i), p0, p1);
         if (COUNT && valid) cnt.c[kPlane]++;
@@ -1192,6 +1197,20 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         hx = r0.x; hy = r0.y; hz = r0.z; nx = r0.w; ny = r1.x; nz = r1.y;
         mat = __float_as_uint(r1.z);
         did = __float_as_uint(r1.w) != 0u;
+    } else if (PHASE == 8) {
+        // Deferred shading: closestHit from the stored hit pass (rtx.h, rtx_aov_planes).  Lanes outside
+        // the frame load nothing and hit nothing; the material index is clamped before any material
+        // load, whatever the planes hold (a stale pass, planes the caller edited).
+        if (valid) {
+            const size_t o = static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
+                             static_cast<size_t>(px);
+            did = F.aov_primitive[o] != 0u;
+            best_t = F.aov_depth[o];
+            nx = F.aov_normal[3 * o]; ny = F.aov_normal[3 * o + 1]; nz = F.aov_normal[3 * o + 2];
+            const uint32_t m = F.aov_material[o], top = S.n_materials - 1u;
+            mat = m < top ? m : top;
+        }
+        if (did) { hx = vr.ox + vr.dx * best_t; hy = vr.oy + vr.dy * best_t; hz = vr.oz + vr.dz * best_t; }
     } else if (did) {
         hx = vr.ox + vr.dx * best_t; hy = vr.oy + vr.dy * best_t; hz = vr.oz + vr.dz * best_t;
         if (best_kind == 1) {
@@ -1311,10 +1330,11 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
                 unsigned long long live = hitmask;
                 const bool sfast = (hitmask & sslow) == 0 && S.tri_fast;
                 const int soct =
-                    (sfast && S.oct_bytes && (PHASE == 0 || PHASE == 5) && n_mesh) ? batch_octant(sr, hitmask) : -1;
+                    (sfast && S.oct_bytes && (PHASE == 0 || PHASE == 5 || PHASE == 8) && n_mesh) ? batch_octant(sr, hitmask) : -1;
                 // exact cull of the light's anchor: lanes with mag <= cull_T[li] (and a direction
                 // normalised from at least 2^-30)
-                const bool scull = kCull && S.cull_stride && sfast && (PHASE == 0 || PHASE == 2 || PHASE == 5) && n_mesh;
+                const bool scull =
+                    kCull && S.cull_stride && sfast && (PHASE == 0 || PHASE == 2 || PHASE == 5 || PHASE == 8) && n_mesh;
                 CullRay sq{};
                 if (scull)
                     sq = cull_ray(S.cull + static_cast<size_t>(kMaxViews + li) * (S.cull_stride / 16u), sr,
@@ -1377,7 +1397,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
 #if RTX_STAMPS
                 const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
 #endif
-                for (uint32_t mi = 0; mi < ((RTX_ABL_SMESH || !(PHASE == 0 || PHASE == 5)) ? 0u : n_mesh); ++mi) {
+                for (uint32_t mi = 0; mi < ((RTX_ABL_SMESH || !(PHASE == 0 || PHASE == 5 || PHASE == 8)) ? 0u : n_mesh); ++mi) {
                     if (!live) break;
                     float st = 0.f;
                     uint32_t stri = 0;
@@ -1584,7 +1604,7 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
     uint32_t tile, part = 0, light = 0;
     // PHASE 4/5: the light-major frame (FrameArgs::lm_*): PHASE 4 = PHASE 0 up to the hit record,
     // PHASE 5 = item (tile, light), the tiles in dispatch order and a tile's lights consecutive
-    if (PHASE == 0 || PHASE == 4 || PHASE == 6 || PHASE == 7) {
+    if (PHASE == 0 || PHASE == 4 || PHASE == 6 || PHASE == 7 || PHASE == 8) {
         if (widx >= F.n_tiles) return;
         tile = F.order ? ldc(F.order, widx) : widx;
         if (F.heavy_flag && ldc(F.heavy_flag, tile)) return;   // rendered by the split launches
@@ -2417,6 +2437,12 @@ void launch_hit_pass(bool deep, bool hstk, bool cull, dim3 grid, hipStream_t s, 
     case 0: hipLaunchKernelGGL((rtx_render_kernel<false, 7>), grid, dim3(kBlockThreads), 0, s, d, F); break;
     default: no_instantiation("this hit pass");
     }
+}
+
+void launch_deferred(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene& d, const FrameArgs& F) {
+    if (hstk) hipLaunchKernelGGL((rtx_render_kernel<false, 8, true, 0, true>), grid, dim3(kBlockThreads), 0, s, d, F);
+    else if (deep) hipLaunchKernelGGL((rtx_render_kernel<false, 8, true>), grid, dim3(kBlockThreads), 0, s, d, F);
+    else launch_phase<8>(variant, grid, s, d, F);
 }
 
 template <bool ANY>

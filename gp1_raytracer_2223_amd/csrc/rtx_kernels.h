@@ -241,6 +241,9 @@ struct FrameArgs {
     // Hit pass (PHASE 7, rtx_render_aov*): the planes of rtx_aov_planes in HBM, view v at
     // v * width * height elements (3 x that for the normal), and the RTX_AOV_* bits to write; a plane
     // outside the mask is never touched (its pointer may be null).  Last, so that no field above moves.
+    // Deferred shading (PHASE 8, rtx_shade_aov*) reads all four instead, at the same elements, and writes
+    // out_px / out_rgb like PHASE 0; `order` may be the frames' (a permutation of the same tiles), and
+    // cost, heavy_flag, lm_* and counters are null.
     uint32_t aov_mask;
     float* __restrict__ aov_depth;
     float* __restrict__ aov_normal;

@@ -21,6 +21,10 @@ void launch_render_one(bool count, bool deep, bool hstk, bool cull, dim3 grid, h
 // The hit pass (PHASE 7): the generic kernel with every stack, or with the exact cull.
 void launch_hit_pass(bool deep, bool hstk, bool cull, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
                      const rtxd::FrameArgs& F);
+// Deferred shading (PHASE 8): the frame's specialised variant (-1: generic) with the cull variant when
+// the scene has cull records, or the generic kernel with the deep stacks (which walk without the cull).
+void launch_deferred(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
+                     const rtxd::FrameArgs& F);
 // A ray query (rtx_query_kernel): closest hit or occlusion (`any`) with the default stack, the deep
 // one, or the deep one in HBM; grid.x = the launch's waves, ceil(Q.n / 64) / kWavesPerBlock.
 void launch_query(bool any, bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,

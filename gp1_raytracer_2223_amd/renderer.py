@@ -64,6 +64,7 @@ class DeviceContext:
         self.h = h
         self.device = device
         self._uploaded = None
+        self._aov_shape = None   # (width, height, views) of the last hit pass queued through this object
 
     def close(self):
         if getattr(self, "h", None):
@@ -148,6 +149,7 @@ class DeviceContext:
         out = aov_struct(planes)
         abi.check(self.lib.rtx_render_aov(self.h, C.byref(cam), C.byref(params), int(mask), C.byref(out)),
                   "rtx_render_aov", self.h)
+        self._aov_shape = (params.width, params.height, 1)
         return planes
 
     def render_aov_async(self, cams, params: abi.RenderParams, mask: int = AOV_ALL) -> None:
@@ -157,6 +159,7 @@ class DeviceContext:
         arr = (abi.Camera * len(cams))(*cams)
         abi.check(self.lib.rtx_render_aov_async(self.h, arr, len(cams), C.byref(params), int(mask)),
                   "rtx_render_aov_async", self.h)
+        self._aov_shape = (params.width, params.height, len(cams))
 
     def gather_aov_async(self, planes: dict) -> None:
         """Queue the D2H copy of the rows the last hit pass owns into full-frame host planes
@@ -261,6 +264,33 @@ class DeviceContext:
         ms = C.c_float()
         abi.check(self.lib.rtx_time_aov_frames(self.h, C.byref(cam), C.byref(params), int(mask), int(iters),
                                                C.byref(ms)), "rtx_time_aov_frames", self.h)
+        self._aov_shape = (params.width, params.height, 1)
+        return ms.value
+
+    def shade_aov_async(self, params: abi.RenderParams, want_rgb: bool = False) -> None:
+        """Queue deferred shading of the last hit pass into the colour frame buffer (rtx_shade_aov_async):
+        `params` supplies the lighting mode, shadows and pixel format, the pass everything else."""
+        abi.check(self.lib.rtx_shade_aov_async(self.h, C.byref(params), int(want_rgb)), "rtx_shade_aov_async", self.h)
+
+    def shade_aov(self, params: abi.RenderParams, want_rgb: bool = True):
+        """Deferred shading of the last hit pass (rtx_shade_aov), blocking: (pixels, rgb) like render(), of
+        the pass's size (every view of a multi-view pass, one after the other; rows a striped pass does
+        not own stay zero)."""
+        if self._aov_shape is None:   # no pass through this object: the library says why
+            self.shade_aov_async(params, want_rgb)
+            raise RuntimeError("shade_aov: the last hit pass was not queued through this object, its size is unknown")
+        n = self._aov_shape[0] * self._aov_shape[1] * self._aov_shape[2]
+        px = np.zeros(n, np.uint32)
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.lib.rtx_shade_aov(self.h, C.byref(params), px.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                    rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_shade_aov", self.h)
+        return px, rgb
+
+    def time_shade_aov(self, params: abi.RenderParams, want_rgb: bool, iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_shade_aov(self.h, C.byref(params), int(want_rgb), int(iters), C.byref(ms)),
+                  "rtx_time_shade_aov", self.h)
         return ms.value
 
     def time_frames(self, cam, params, iters: int) -> float:
@@ -503,6 +533,24 @@ class Renderer:
         the planes of `mask` as flat numpy arrays; rows this renderer's stripes do not own stay 0."""
         _, cam = self._view(scene, upload)
         return self.ctx.render_aov(cam, self.params(), mask)
+
+    def ShadeAOV(self, want_rgb: bool = False) -> np.ndarray:
+        """Deferred shading (rtx_shade_aov; not in the reference's Renderer): the frame Render would
+        render, shaded from the last RenderAOV's planes (all four) with the renderer's CURRENT lighting
+        mode, shadows and pixel format, without tracing a primary ray.  Explicit: nothing is cached or
+        reused automatically, and the scene is whatever was uploaded last.  Blocking; fills self.buffer."""
+        n = self.m_Width * self.m_Height
+        if self.ctx._aov_shape != (self.m_Width, self.m_Height, 1):
+            if self.ctx._aov_shape is None:
+                self.ctx.shade_aov_async(self.params(), want_rgb)   # no pass yet: the library says why
+            raise RuntimeError(f"ShadeAOV: the context's last hit pass is {self.ctx._aov_shape}, not this renderer's")
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.ctx.lib.rtx_shade_aov(self.ctx.h, C.byref(self.params()),
+                                        self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_shade_aov", self.ctx.h)
+        self.rgb = rgb
+        return self.buffer
 
     def TraceRays(self, scene: HostScene, rays, mask: int = AOV_ALL, upload: bool = True) -> dict:
         """Scene::GetClosestHit on the caller's (n, 8) rays against `scene` (same upload bookkeeping as

@@ -30,7 +30,7 @@
  * and the scheduler's / exact cull's internals are in rtx_diag.h; the environment knobs the library
  * reads are listed in INTEGRATION.md (none of them changes a pixel).  In csrc/ the entry points
  * live by topic: rtx_context.hip, rtx_upload.hip, rtx_frame.hip, rtx_aov.hip (the hit pass),
- * rtx_query.hip (ray queries and shaded rays), rtx_adaptive.hip (adaptive supersampling), rtx_group.cpp and
+ * rtx_deferred.hip (deferred shading), rtx_query.hip (ray queries and shaded rays), rtx_adaptive.hip (adaptive supersampling), rtx_group.cpp and
  * rtx_anim_host.hip; the render kernel is rtx_hip.hip.
  */
 #ifndef RTX_H_
@@ -323,6 +323,46 @@ int rtx_gather_aov_async(rtx_ctx* ctx, const rtx_aov_planes* out);
 /* Device pointers of the HBM planes (NULL for a plane no mask has named yet); the passes queued so
  * far are complete in them after rtx_synchronize. */
 int rtx_device_aov_buffers(rtx_ctx* ctx, rtx_aov_planes* out);
+
+/* ---- deferred shading: the colour of a stored hit pass, without tracing it again -------
+ * rtx_shade_aov* runs everything after Scene::GetClosestHit of Renderer::RenderPixel
+ * (source/Renderer.cpp:100-181) on the records the context's last hit pass stored, and writes the
+ * colour frame buffer.  The pass supplies the size, the views, the stripes and the cameras (the
+ * context keeps them); `params` supplies lighting_mode, shadows_enabled and format, and its size and
+ * stripe fields are ignored.  The pass must have written all four planes (RTX_AOV_ALL).
+ *
+ * Per owned pixel the result is RenderPixel with closestHit taken from the planes: didHit =
+ * (primitive != 0), t = the depth plane's value, normal the normal plane's, materialIndex the material
+ * plane's, origin = ray.origin + t * ray.direction per component (one rounded multiply, one rounded
+ * add: Utils.h:67, 92, 162), and ray the frame's primary ray of that pixel and view.  From
+ * originOffset on it is the frame's code: the light loop in scene order, DoesHit, the mode's term,
+ * shadowFactor, MaxToOne, the quantisation.
+ *
+ * Guarantee: while the geometry, the material indices and the cameras are those of the pass, the
+ * frame buffer holds word for word, in both planes, what rtx_render_views_async with the pass's
+ * cameras, size and stripes and these mode, shadows and format leaves there; so it is the reference's
+ * frame bit for bit wherever the reference calls no powf.  Lights and material VALUES are read from
+ * the scene uploaded at the time of the call: upload a scene with other lights or material values
+ * (same geometry, same material indices) and shade again to relight the pass.  Geometry, material
+ * indices or a device Update (rtx_anim_update) that changed since the pass give unspecified colours
+ * (never an out-of-range load: the material index is clamped to the scene's); keeping them is the
+ * caller's responsibility.
+ *
+ * Afterwards the last-frame record is the pass's shape: rtx_download, rtx_gather_async and
+ * rtx_device_buffers work unchanged.  The call is no frame for the schedule or any policy (tile costs
+ * and order, split rendering and its tuner, motion mode, frames in flight stay as they were; it only
+ * reads the dispatch order of earlier frames of the same size, views and stripes, which changes no
+ * pixel), reads the planes and their record only, and queues on the context stream, ordered with the
+ * frames, passes, uploads and Updates before and after it.
+ * Errors (the context keeps working after each): NULL ctx or params, a lighting mode or format
+ * rtx_render rejects: RTX_E_INVALID; no scene, no pass yet, a last pass whose mask is not
+ * RTX_AOV_ALL, or a scene that now has fewer materials than at the time of the pass: RTX_E_STATE; a
+ * supersample factor other than 1 on the context: RTX_E_UNSUPPORTED.  rtx_download of out_rgb after
+ * want_rgb == 0 returns RTX_E_STATE, as after a frame. */
+int rtx_shade_aov_async(rtx_ctx* ctx, const rtx_render_params* params, int want_rgb);
+/* Blocking: the call above, then rtx_download into the caller's full-frame buffers (out_rgb may be
+ * NULL). */
+int rtx_shade_aov(rtx_ctx* ctx, const rtx_render_params* params, uint32_t* out_pixels, float* out_rgb);
 
 /* ---- ray queries: closest hit and occlusion for caller-supplied rays ---------------
  * The traversal behind a frame's rays, for rays the caller makes: a line-of-sight test, a pick ray,

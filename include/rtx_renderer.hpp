@@ -97,6 +97,14 @@ public:
         if (upload) Upload(s);
         return RenderAov(cam, mask);
     }
+    // Deferred shading (rtx_shade_aov; not in the reference): the frame Render would render, shaded
+    // from the last RenderAov's planes (all four) with the renderer's CURRENT lighting mode, shadows and
+    // pixel format, without tracing a primary ray.  Explicit: nothing is cached or reused on its own,
+    // and the scene is whatever was uploaded last.  Fills Pixels() (the renderer's size is the pass's).
+    void ShadeAov() {
+        const rtx_render_params p = Params();
+        Check(rtx_shade_aov(m_Ctx, &p, m_Pixels.data(), nullptr), "rtx_shade_aov");
+    }
 
     // Ray queries against the uploaded scene (rtx_trace_rays / rtx_occluded; not in the reference's
     // Renderer): Scene::GetClosestHit and Scene::DoesHit on the caller's rays, uninterpreted (rtx.h).
