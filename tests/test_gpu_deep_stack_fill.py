@@ -1,0 +1,387 @@
+"""Deep BVHs whose walks really fill the per-wave DFS stack, bit for bit against the reference.
+
+The chain of tests/test_gpu_deep_bvh.py selects the deep-stack kernel variants but never holds more than
+one pending entry (tests/test_deep_chain_cpu.py).  The left-deep chains of tests/deep_chain.py hold
+T - 1 = the tree's level depth in 36 of a 160 x 96 frame's 240 wave tiles, many of them neighbours in one
+workgroup, and in every wave of `rim_rays`: 63 of the 64-entry LDS stack (T = 64), 64 and 1023 of the
+1024-entry one (65, 1024) and 1024 of the 1025 entries per wave in HBM (1025).  A misaddressed entry, two
+waves' stacks overlapping, stacks sized for another launch or a shared counting stack then change pixels,
+hit records or work counters.  The reference recurses without a limit; the Bunny room's materials call
+no powf, so every comparison is word for word (a NaN equal to any NaN)."""
+import os
+import re
+from pathlib import Path
+
+import ctypes as C
+import numpy as np
+import pytest
+
+import adaptive_ref
+import aov_ref
+import deep_chain as dc
+import devbuf
+import oracle_bind
+import rayq_ref
+import shade_ref
+import ss_ref
+from gp1_raytracer_2223_amd import abi
+from gp1_raytracer_2223_amd.renderer import AOV_ALL, DeviceContext
+
+pytestmark = pytest.mark.gpu
+
+DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
+ROOT = Path(__file__).resolve().parents[1]
+W, H = dc.W, dc.H
+SIZES = (64, 65, 1024, 1025)
+CASES = [(T, layout) for T in SIZES for layout in dc.LAYOUTS]
+FRAME_CASES = [(T, layout) for T in (64, 65, 300, 1024, 1025) for layout in dc.LAYOUTS]
+TWO = [(T, layout) for T in (65, 1025) for layout in dc.LAYOUTS]
+MODES = ((3, 1), (0, 1))
+TAU = 8   # the oracle's plain frames have 1,400 to 4,300 pixels above it, most of them on the chain
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    """tests/shade_ref.c holds rayq_ref.c and aov_ref.c: one library checks the shaded rays, the queries
+    and the hit pass."""
+    lib = shade_ref.build(tmp_path_factory.mktemp("shade_ref"))
+    P = C.POINTER
+    lib.aov_ref_planes.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float),
+                                   P(C.c_uint32), P(C.c_uint32)]
+    lib.aov_ref_planes.restype = C.c_int
+    return lib
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = DeviceContext(DEV)
+    yield c
+    c.close()
+
+
+def _ctx_env(**env):
+    saved = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return DeviceContext(DEV)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+_scenes, _frames, _tiles, _planes = {}, {}, {}, {}
+
+
+def _scene(T, layout):
+    if (T, layout) not in _scenes:
+        _scenes[(T, layout)] = dc.left_deep_scene(T, layout)
+    return _scenes[(T, layout)][:2]
+
+
+def _oracle(T, layout, w=W, h=H, mode=3, shadows=1):
+    """The oracle's frame (computed once per case, never written to)."""
+    key = (T, layout, w, h, mode, shadows)
+    if key not in _frames:
+        s, cam = _scene(T, layout)
+        px, rgb = oracle_bind.render(s, cam, abi.make_params(w, h, mode, shadows))
+        px.setflags(write=False)
+        rgb.setflags(write=False)
+        _frames[key] = (px, rgb)
+    return _frames[key]
+
+
+def _full_tiles(T, layout):
+    """The wave tiles of the 160 x 96 frame that hold T - 1 pending entries, by the model."""
+    if (T, layout) not in _tiles:
+        s, cam = _scene(T, layout)
+        full = np.nonzero(dc.frame_high_water(s, cam) == T - 1)[0]
+        assert full.size == 36 and (np.diff(full) == 1).sum() >= 2, full
+        _tiles[(T, layout)] = full
+    return _tiles[(T, layout)]
+
+
+def _tile_rays(T, layout):
+    s, cam = _scene(T, layout)
+    p = abi.make_params(W, H)
+    return np.concatenate([dc.camera_tile_rays(cam, p, int(t)) for t in _full_tiles(T, layout)])
+
+
+def _ref_planes(checker, T, layout):
+    if (T, layout) not in _planes:
+        s, cam = _scene(T, layout)
+        _planes[(T, layout)] = aov_ref.planes(checker, s, cam, W, H)
+    return _planes[(T, layout)]
+
+
+def _same(got, want, what):
+    """Pixels equal, colour planes equal as uint32 (test_gpu_cull._same: a NaN equal to any NaN)."""
+    bad = np.nonzero(got[0] != want[0])[0]
+    assert bad.size == 0, f"{what}: {bad.size} pixels differ, first at (x, y) = {(int(bad[0]) % W, int(bad[0]) // W)} of a " \
+                          f"{W}-wide frame, wave tile {int(bad[0]) // W // 8 * (W // 8) + int(bad[0]) % W // 8}"
+    na, nb = np.isnan(got[1]), np.isnan(want[1])
+    assert np.array_equal(na, nb), f"{what}: NaN positions differ"
+    assert np.array_equal(got[1].view(np.uint32)[~na], want[1].view(np.uint32)[~nb]), f"{what}: colour planes differ"
+
+
+def _same_any_width(got, want, what):
+    assert np.array_equal(got[0], want[0]), f"{what}: {(got[0] != want[0]).sum()} pixels differ"
+    assert aov_ref.same(got[1], want[1]), f"{what}: colour planes differ"
+
+
+# ---- 1. frames --------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("T,layout", FRAME_CASES)
+def test_frames_and_work_counters(ctx, T, layout):
+    """Each frame three times (tile order, then the cost-ordered dispatch).  The counting variant walks
+    with its second stack (sT, hstkT); a lost or repeated entry changes the slab and triangle counters
+    even where its triangle is smaller than a pixel."""
+    s, cam = _scene(T, layout)
+    _full_tiles(T, layout)   # (the model's 36 full tiles: asserted)
+    ctx.upload(s)
+    for mode, sh in MODES:
+        want = _oracle(T, layout, W, H, mode, sh)
+        for frame in range(3):
+            _same(ctx.render(cam, abi.make_params(W, H, mode, sh)), want, f"T={T} {layout} m{mode} frame {frame}")
+    assert np.unique(_oracle(T, layout)[0]).size > 200   # (the chain is in view)
+    p = abi.make_params(W, H)
+    got, want = ctx.count_work(cam, p), oracle_bind.count(s, cam, p)
+    assert np.array_equal(got, want), dict(zip(oracle_bind.COUNTER_NAMES, zip(got.tolist(), want.tolist())))
+
+
+# ---- 2. the 64-entry stack at its limit ----------------------------------------------------------------
+
+CULL = {"RTX_CULL_MIN_SA": "0", "RTX_CULL_RATIO": "0"}
+SPLIT = {"RTX_SPLIT": "force", "RTX_SPLIT_PARTS": "8"}
+
+
+@pytest.fixture(scope="module")
+def plain_ctx():
+    c = _ctx_env(RTX_NO_CULL="1")
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("layout", dc.LAYOUTS)
+@pytest.mark.parametrize("which", ["cull", "split", "cull_split"])
+def test_the_64_entry_stack_at_its_limit(plain_ctx, which, layout):
+    """T = 64: 63 levels, the last tree the 64-entry LDS stack serves, under the ordered walk of the exact
+    cull and the part walks of the split launches."""
+    T = 64
+    env = {**(CULL if "cull" in which else {}), **(SPLIT if "split" in which else {})}
+    s, cam = _scene(T, layout)
+    c = _ctx_env(**env)
+    try:
+        c.upload(s)
+        plain_ctx.upload(s)
+        for mode, sh in MODES:
+            p = abi.make_params(W, H, mode, sh)
+            want = _oracle(T, layout, W, H, mode, sh)
+            for frame in range(3):
+                got = c.render(cam, p)
+                _same(got, want, f"{which} {layout} m{mode} frame {frame} against the oracle")
+            _same(got, plain_ctx.render(cam, p), f"{which} {layout} m{mode} against the unculled walk")
+        if "cull" in which:
+            assert c.cull_info()[0], "the chain renders without the exact cull"
+        if "split" in which:
+            assert c.split_info()[0] > 0 and c.split_info()[1] > 1, c.split_info()
+    finally:
+        c.close()
+
+
+# ---- 3. supersampling --------------------------------------------------------------------------------
+
+_hi = {}
+
+
+def _oracle_hi(T, layout):
+    if (T, layout) not in _hi:
+        s, cam = _scene(T, layout)
+        _, hi = oracle_bind.render(s, cam, abi.make_params(2 * W, 2 * H))
+        hi.setflags(write=False)
+        _hi[(T, layout)] = hi
+    return _hi[(T, layout)]
+
+
+@pytest.mark.parametrize("T,layout", TWO)
+def test_supersampling(T, layout):
+    s, cam = _scene(T, layout)
+    rgb = ss_ref.resolve(_oracle_hi(T, layout), W, H, 2)
+    c = DeviceContext(DEV)
+    try:
+        c.upload(s)
+        c.set_supersample(2)
+        for frame in range(2):
+            _same(c.render(cam, abi.make_params(W, H)), (ss_ref.quantize(rgb), rgb), f"T={T} {layout} k2 frame {frame}")
+        got = c.count_work(cam, abi.make_params(W, H))
+        assert np.array_equal(got, oracle_bind.count(s, cam, abi.make_params(2 * W, 2 * H)))
+    finally:
+        c.close()
+
+
+# ---- 4. the hit pass and deferred shading ----------------------------------------------------------------
+
+@pytest.mark.parametrize("T,layout", CASES)
+def test_hit_pass_and_deferred_shade(ctx, checker, T, layout):
+    s, cam = _scene(T, layout)
+    ctx.upload(s)
+    frames = {}
+    for mode, sh in MODES:
+        frames[(mode, sh)] = ctx.render(cam, abi.make_params(W, H, mode, sh))
+        _same(frames[(mode, sh)], _oracle(T, layout, W, H, mode, sh), f"T={T} {layout} m{mode}")
+    got = ctx.render_aov(cam, abi.make_params(W, H), AOV_ALL)
+    bad = aov_ref.diff(got, _ref_planes(checker, T, layout))
+    assert not bad, f"T={T} {layout}: planes {bad} differ"
+    tri = aov_ref.kind(got["primitive"]) == abi.RTX_PRIM_TRIANGLE
+    seen = np.unique(aov_ref.index(got["primitive"])[tri]).size
+    if layout == "centred":   # every triangle of the short chains is some pixel's closest hit
+        assert seen == (T if T <= 65 else 118), seen
+    else:
+        assert seen >= 17, seen
+    for mode, sh in MODES:   # one pass, both modes, every owned word proved written
+        devbuf.poison(ctx, W * H, rgb=True)
+        ctx.shade_aov_async(abi.make_params(1, 1, mode, sh), True)
+        devbuf.check(ctx, abi.make_params(W, H, mode, sh), 1, frames[(mode, sh)][0], frames[(mode, sh)][1],
+                     f"T={T} {layout} deferred m{mode}")
+
+
+# ---- 5. adaptive supersampling ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("T,layout", TWO)
+def test_adaptive(ctx, checker, T, layout):
+    """Persistent waves: with the stacks in HBM one stack per resident wave, reused from item to item."""
+    s, cam = _scene(T, layout)
+    P = _oracle(T, layout)
+    S = adaptive_ref.supersampled(_oracle_hi(T, layout), W, H, 2)
+    E = adaptive_ref.edges(P[0], W, H, TAU)
+    on_chain = aov_ref.kind(_ref_planes(checker, T, layout)["primitive"]) == abi.RTX_PRIM_TRIANGLE
+    assert 0 < int(E.sum()) < W * H and int((E & on_chain).sum()) > 1000
+    ctx.upload(s)
+    for frame in range(2):
+        got = ctx.render_adaptive(cam, abi.make_params(W, H), 2, TAU)
+        assert ctx.adaptive_refined() == int(E.sum())
+        _same(got, (adaptive_ref.compose(P[0], S[0], E), adaptive_ref.compose(P[1], S[1], E)),
+              f"T={T} {layout} adaptive frame {frame}")
+
+
+# ---- 6. ray queries ------------------------------------------------------------------------------------
+
+def _query(c, checker, s, rays, what, lengths=()):
+    planes, occ = rayq_ref.trace(checker, s, rays), rayq_ref.occluded(checker, s, rays)
+    for n in (rays.shape[0],) + tuple(lengths):
+        got = c.trace_rays(rays[:n], AOV_ALL)
+        bad = aov_ref.diff(got, rayq_ref.prefix(planes, n))
+        first = np.nonzero(got["primitive"] != planes["primitive"][:n])[0][:8].tolist()
+        assert not bad, f"{what}, n = {n}: planes {bad} differ (primitive first at rays {first})"
+        o = c.occluded(rays[:n])
+        assert np.array_equal(o, occ[:n]), f"{what}, n = {n}: occlusion differs at rays {np.nonzero(o != occ[:n])[0][:8].tolist()}"
+    return planes, occ
+
+
+@pytest.mark.parametrize("T,layout", CASES)
+def test_ray_queries(ctx, checker, T, layout):
+    s, cam = _scene(T, layout)
+    ctx.upload(s)
+    rays, tri = dc.rim_rays(s, cam)
+    planes, occ = _query(ctx, checker, s, rays, f"T={T} {layout} rim rays", lengths=(1, 63, 64, 65))
+    rim = tri >= 0
+    assert np.array_equal(aov_ref.index(planes["primitive"][rim]), np.arange(T)) and occ.all()
+    # the any-hit walks that must pop every entry: nothing occludes the corner layout's axis
+    waves = dc.axis_waves(s, cam)
+    _, occ = _query(ctx, checker, s, waves, f"T={T} {layout} axis waves", lengths=(64, 65))
+    assert (occ[[0, 63, 64, 128, 129]] == (layout == "centred")).all()
+    # the frame's 36 full tiles as caller-supplied rays, neighbours in one workgroup
+    tiles = _tile_rays(T, layout)
+    assert tiles.shape[0] == 36 * 64
+    _query(ctx, checker, s, tiles, f"T={T} {layout} full tiles")
+
+
+def _launch_rays(max_depth: int) -> int:
+    """rtx_query.hip's launch_rays for a tree with HBM stacks, from the constants of rtx_kernels.h."""
+    text = (ROOT / "gp1_raytracer_2223_amd" / "csrc" / "rtx_kernels.h").read_text()
+    chunk = re.search(r"kQueryChunkRays = 1u << (\d+);", text)
+    stack = re.search(r"kQueryStackBytes = size_t\((\d+)\) << (\d+);", text)
+    block = re.search(r"#define RTX_BLOCK_THREADS (\d+)", text)
+    assert chunk and stack and block and "kWavesPerBlock = kBlockThreads / 64;" in text, \
+        "rtx_kernels.h no longer states the launch's limits this way"
+    wpb = int(block.group(1)) // 64
+    per_wave = (max_depth + 1) * (16 + 8)   # a uint4 and the counting walk's 64-bit mask per entry
+    waves = max((int(stack.group(1)) << int(stack.group(2))) // per_wave, wpb)
+    return min(1 << int(chunk.group(1)), waves // wpb * wpb * 64)
+
+
+@pytest.mark.parametrize("layout", dc.LAYOUTS)
+def test_a_large_query_sizes_the_hbm_stacks_per_launch(ctx, checker, layout):
+    """T = 1025: 24,600 B of stack per wave and at most 256 MB of stacks a launch, about 698,000 rays; the
+    rim set repeated to more than four launches' worth.  Its length is no multiple of 64, so every repeat
+    puts the rays into other lanes."""
+    T = 1025
+    s, cam = _scene(T, layout)
+    chunk = _launch_rays(T - 1)
+    assert 64 <= chunk < 1 << 20 and chunk % 64 == 0, chunk
+    n = 4 * chunk + 1000
+    base, _ = dc.rim_rays(s, cam)
+    reps = -(-n // base.shape[0])
+    rays = np.tile(base, (reps, 1))[:n]
+    planes, occ = rayq_ref.trace(checker, s, base), rayq_ref.occluded(checker, s, base)
+    want = {k: np.tile(v, reps)[:(3 * n if k == "normal" else n)] for k, v in planes.items()}
+    ctx.upload(s)
+    got = ctx.trace_rays(rays)
+    bad = aov_ref.diff(got, want)
+    first = np.nonzero(got["primitive"] != want["primitive"])[0][:8].tolist()
+    assert not bad, f"planes {bad} differ (primitive first at rays {first}; a launch is {chunk} rays)"
+    assert np.array_equal(ctx.occluded(rays), np.tile(occ, reps)[:n])
+
+
+# ---- 7. shaded rays --------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("T,layout", CASES)
+def test_shaded_rays(ctx, checker, T, layout):
+    """The shadow rays of these hits are any-hit walks on full stacks."""
+    s, cam = _scene(T, layout)
+    ctx.upload(s)
+    rim, _ = dc.rim_rays(s, cam)
+    for what, rays in (("rim rays", rim), ("full tiles", _tile_rays(T, layout))):
+        for mode, sh in MODES:
+            p = shade_ref.params(mode, sh)
+            want_px, want_rgb, flags = shade_ref.shade(checker, s, rays, p)
+            assert ((flags & shade_ref.HIT) != 0).all() and np.unique(want_px).size > 1   # (no constant pattern)
+            px, rgb = ctx.shade_rays(rays, p)
+            bad = np.nonzero(px != want_px)[0]
+            assert bad.size == 0, f"T={T} {layout} {what} m{mode}: pixels differ at rays {bad[:8].tolist()}"
+            assert aov_ref.same(rgb, want_rgb), f"T={T} {layout} {what} m{mode}: rgb differs"
+    # the full tiles' rays shade to the frame's pixels
+    p = abi.make_params(W, H)
+    px, _ = ctx.shade_rays(_tile_rays(T, layout), p)
+    frame = _oracle(T, layout)[0].reshape(H // 8, 8, W // 8, 8).transpose(0, 2, 1, 3).reshape(-1, 64)
+    assert np.array_equal(px.reshape(-1, 64), frame[_full_tiles(T, layout)])
+
+
+# ---- 8. the HBM stacks across launch sizes ------------------------------------------------------------------
+
+@pytest.mark.parametrize("layout", dc.LAYOUTS)
+def test_hbm_stacks_follow_the_launch(checker, layout):
+    """One context: a small frame, a larger one, the small one again, a query and a deferred shade.  The
+    stacks are regrown and rebound per launch; each result equals its reference."""
+    T = 1025
+    s, cam = _scene(T, layout)
+    c = DeviceContext(DEV)
+    try:
+        c.upload(s)
+        for w, h in ((96, 64), (400, 224), (96, 64)):
+            _same_any_width(c.render(cam, abi.make_params(w, h)), _oracle(T, layout, w, h), f"{layout} {w}x{h}")
+        rays, _ = dc.rim_rays(s, cam)
+        _query(c, checker, s, rays, f"{layout} rim rays after the frames")
+        w, h = 96, 64
+        got = c.render_aov(cam, abi.make_params(w, h), AOV_ALL)
+        assert not aov_ref.diff(got, aov_ref.planes(checker, s, cam, w, h))
+        for mode, sh in MODES:
+            devbuf.poison(c, w * h, rgb=True)
+            c.shade_aov_async(abi.make_params(1, 1, mode, sh), True)
+            want = _oracle(T, layout, w, h, mode, sh)
+            devbuf.check(c, abi.make_params(w, h, mode, sh), 1, want[0], want[1], f"{layout} deferred m{mode}")
+        _same_any_width(c.render(cam, abi.make_params(400, 224)), _oracle(T, layout, 400, 224), f"{layout} 400x224 again")
+    finally:
+        c.close()
