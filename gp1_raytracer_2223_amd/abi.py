@@ -185,7 +185,9 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_time_ray_queries", "rtx_room_info", "rtx_schedule_xcd_order",
                "rtx_shade_rays", "rtx_shade_rays_device", "rtx_time_shade_rays",
                "rtx_render_adaptive_async", "rtx_render_adaptive", "rtx_adaptive_refined", "rtx_time_adaptive_frames",
-               "rtx_shade_aov_async", "rtx_shade_aov", "rtx_time_shade_aov"]
+               "rtx_shade_aov_async", "rtx_shade_aov", "rtx_time_shade_aov",
+               "rtx_render_shadows_async", "rtx_download_shadows", "rtx_gather_shadows_async",
+               "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows", "rtx_time_relight"]
 
 
 def load_hip() -> C.CDLL:
@@ -358,6 +360,19 @@ def load_hip() -> C.CDLL:
             lib.rtx_shade_aov.restype = C.c_int
             lib.rtx_time_shade_aov.argtypes = [VP, C.POINTER(RenderParams), C.c_int, C.c_int, C.POINTER(C.c_float)]
             lib.rtx_time_shade_aov.restype = C.c_int
+        if hasattr(lib, "rtx_relight"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_render_shadows_async.argtypes = [VP]
+            lib.rtx_download_shadows.argtypes = [VP, C.POINTER(C.c_uint32)]
+            lib.rtx_gather_shadows_async.argtypes = [VP, C.POINTER(C.c_uint32)]
+            lib.rtx_device_shadow_buffer.argtypes = [VP, C.POINTER(C.POINTER(C.c_uint32))]
+            lib.rtx_relight_async.argtypes = [VP, C.POINTER(RenderParams), C.c_int]
+            lib.rtx_relight.argtypes = [VP, C.POINTER(RenderParams), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+            lib.rtx_time_shadows.argtypes = [VP, C.c_int, C.POINTER(C.c_float)]
+            lib.rtx_time_relight.argtypes = [VP, C.POINTER(RenderParams), C.c_int, C.c_int, C.POINTER(C.c_float)]
+            for n in ("rtx_render_shadows_async", "rtx_download_shadows", "rtx_gather_shadows_async",
+                      "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows",
+                      "rtx_time_relight"):
+                getattr(lib, n).restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]
             lib.rtx_scene_image.restype = C.c_int

@@ -4,7 +4,7 @@
 //
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
-//              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T] [--deferred]
+//              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T] [--deferred] [--relight]
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -26,6 +26,9 @@
 // --deferred (single frames only: not with --benchmark, --sequence, --rays, --adaptive or --ss above 1) makes the
 // image from one hit pass plus deferred shading (rtx_render_aov, rtx_shade_aov) instead of a frame: the same
 // BMP, and with --aov the same planes, from one primary traversal.
+// --relight (single frames only, and not with --deferred: the combinations --deferred refuses) makes the image from
+// one hit pass, its shadow pass and a relight (rtx_render_aov, rtx_render_shadows_async, rtx_relight): the same BMP;
+// with --aov also PREFIX_shadow.u32, one word per pixel whose bit l says light l is occluded.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -321,7 +324,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
                              "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
-                             "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred]\n",
+                             "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred] [--relight]\n",
                      argv[0]);
         return 2;
     }
@@ -330,7 +333,7 @@ int main(int argc, char** argv) {
     int ad_k = 0, ad_t = 0;   // --adaptive K,T (0: not asked for)
     std::vector<float> seq;
     float t = -1.f;
-    bool shadows = true, device_update = false, deferred = false;
+    bool shadows = true, device_update = false, deferred = false, relight = false;
     int pos = 0;
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i];
@@ -349,6 +352,7 @@ int main(int argc, char** argv) {
         else if (a == "--inflight" && i + 1 < argc) inflight = std::max(1, std::min(8, std::atoi(argv[++i])));
         else if (a == "--device-update") device_update = true;
         else if (a == "--deferred") deferred = true;
+        else if (a == "--relight") relight = true;
         else if (a == "--ss") {   // checked here: a bad factor ends the program before any device work
             ss = i + 1 < argc ? std::atoi(argv[++i]) : 0;
             if (ss != 1 && ss != 2 && ss != 4 && ss != 8) {
@@ -375,6 +379,11 @@ int main(int argc, char** argv) {
     if (deferred && (bench || !seq.empty() || !rays_file.empty() || ad_k || ss > 1)) {   // before any device work
         std::fprintf(stderr, "--deferred shades a single frame's hit pass: not with --benchmark, --sequence, --rays, "
                              "--adaptive or --ss above 1\n");
+        return 2;
+    }
+    if (relight && (deferred || bench || !seq.empty() || !rays_file.empty() || ad_k || ss > 1)) {   // before any device work
+        std::fprintf(stderr, "--relight shades a single frame's hit pass and shadow pass: not with --deferred, --benchmark, "
+                             "--sequence, --rays, --adaptive or --ss above 1\n");
         return 2;
     }
     if (!aov.empty() && (bench || !seq.empty())) {
@@ -462,6 +471,20 @@ int main(int argc, char** argv) {
                     rc = 1;
                 } else {
                     std::printf("wrote %s_depth.f32 _normal.f32 _material.u32 _primitive.u32\n", aov.c_str());
+                }
+            }
+        } else if (relight) {   // one hit pass, its shadow rays stored, shaded from both; --aov writes all five planes
+            const rtx::Renderer::AovFrame f = r.RenderAov(hs, RTX_AOV_ALL, true);
+            const std::vector<uint32_t> bits = r.RenderShadows();
+            r.Relight();
+            if (!aov.empty()) {
+                if (!write_plane(aov + "_depth.f32", f.depth) || !write_plane(aov + "_normal.f32", f.normal) ||
+                    !write_plane(aov + "_material.u32", f.material) || !write_plane(aov + "_primitive.u32", f.primitive) ||
+                    !write_plane(aov + "_shadow.u32", bits)) {
+                    std::fprintf(stderr, "cannot write %s_*\n", aov.c_str());
+                    rc = 1;
+                } else {
+                    std::printf("wrote %s_depth.f32 _normal.f32 _material.u32 _primitive.u32 _shadow.u32\n", aov.c_str());
                 }
             }
         } else {

@@ -41,6 +41,7 @@ int aov_prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rende
         c->d_aov_depth.free(); c->d_aov_normal.free();
         c->d_aov_material.free(); c->d_aov_primitive.free();
         c->aov_last_mask = 0;   // (their contents are gone)
+        ++c->aov_serial;
         c->aov_cap = npx;
     }
     int rc = RTX_OK;
@@ -90,6 +91,7 @@ void aov_remember(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_ren
     c->aov_last_mask = mask;
     for (int v = 0; v < n_views; ++v) c->aov_last_cams[v] = cams[v];
     c->aov_last_materials = c->dev.n_materials;
+    ++c->aov_serial;   // (a shadow plane of an earlier pass is no longer this one's: rtx_relight.hip)
 }
 
 // ... of the last hit pass (rtx_ctx::aov_last*)

@@ -242,6 +242,15 @@ struct rtx_ctx {
     // number of materials of the scene it traced (its material plane's indices lie below it)
     rtx_camera aov_last_cams[kMaxViews] = {};
     uint32_t aov_last_materials = 0;
+    // Relighting (rtx_render_shadows_async, rtx_relight*: rtx_relight.hip).  The shadow plane in HBM, one
+    // word per pixel of the hit pass (bit l: light l occluded), and its validity record: the hit pass it
+    // belongs to, by the serial every hit pass bumps (0: no shadow pass yet), and the lights it was traced
+    // for, each as its origin's and type's bits.  light_keys is the same of the scene uploaded last.
+    uint64_t aov_serial = 0;
+    DevBuf<uint32_t> d_shadow{bufs};
+    uint64_t shadow_serial = 0;
+    std::vector<std::array<uint32_t, 4>> shadow_lights;
+    std::vector<std::array<uint32_t, 4>> light_keys;
     // Ray queries and shaded rays (rtx_trace_rays, rtx_occluded, rtx_shade_rays: rtx_query.hip): the host
     // variants' staging buffer in HBM, the rays and then every result array of one call; its cap = the
     // rays it holds

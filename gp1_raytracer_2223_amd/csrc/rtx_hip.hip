@@ -894,6 +894,11 @@ __device__ __forceinline__ uint32_t q8(float c) {
 // Deferred shading (rtx_shade_aov*) is the other half, also one launch:
 //   PHASE 8  grid (tiles):                 the hit record read from a stored hit pass's four planes (no
 //                                          closest-hit work), then PHASE 0 from originOffset on
+// The shadow pass (rtx_render_shadows_async) is PHASE 8 up to the occlusion decision:
+//   PHASE 9  grid (tiles):                 the hit record from the planes, every light's shadow ray by the
+//                                          walk PHASE 8 takes; bit l of the pixel's word (FrameArgs::occ_bits,
+//                                          here the shadow plane, frame layout) = light l is occluded
+// (rtx_relight_kernel, below, shades the planes plus that word without a ray.)
 // Every phase recomputes the primary ray and the sphere/plane hits with the same code, so
 // all of them see bit-identical values.
 // DEEP: the variant for scenes whose BVH is kStackDepth or more levels deep (a DFS stack of
@@ -915,6 +920,69 @@ __device__ __forceinline__ uint32_t q8(float c) {
 // epilogue (0, 3, 6): the frame is the sample frame and the epilogue resolves each pixel's k x k
 // samples across the wave.  A variant of its own so that the plain kernels stay the code they were
 // (as a run-time branch it moved their VGPR counts by 1-2: profiles/ss/resource_usage.txt).
+// The pieces of Renderer::RenderPixel that render_tile and rtx_relight_kernel (below) both run, each stated
+// once and expanded in both, so the relight's arithmetic is the frame's by construction.  Macros, not
+// functions: as __forceinline__ functions they left the values alone but moved the register allocation of
+// 128 of the render kernel's 162 instantiations (tools/codeobj_diff.py), and as macros render_tile is the
+// text it was.  They name the variables of the scope they expand in.
+// RTX_PRIMARY_DIR: the primary ray's direction dx, dy, dz, normalised from the magnitude dm
+// (Renderer.cpp:104-114; Matrix::TransformVector Matrix.cpp:35-42).
+// (px + 0.5f) / W and (2 * (py + 0.5f)) / H as Markstein quotients with the exact
+// reciprocals RN(1/W), RN(1/H) (divided on the host, FrameArgs): numerators in [0.5, 2^17], divisors in
+// [1, 2^16] lie inside div_rn's domain (rtx_fastdiv.h), so each is the IEEE quotient.
+#define RTX_PRIMARY_DIR(F, V)                                                                     \
+    const int W = static_cast<int>(F.width), H = static_cast<int>(F.height);                      \
+    const float fW = static_cast<float>(W), fH = static_cast<float>(H);                           \
+    const float cx = (2.f * div_rn(px + 0.5f, fW, F.inv_width) - 1) * F.aspect * V.fov;           \
+    const float cy = (1.f - div_rn(2.f * (py + 0.5f), fH, F.inv_height)) * V.fov;                 \
+    float dx = V.right[0] * cx + V.up[0] * cy + V.forward[0] * 1.f;                               \
+    float dy = V.right[1] * cx + V.up[1] * cy + V.forward[1] * 1.f;                               \
+    float dz = V.right[2] * cx + V.up[2] * cy + V.forward[2] * 1.f;                               \
+    const float dm = sqrtf(dx * dx + dy * dy + dz * dz);                                          \
+    div3_exact(dx, dy, dz, dm) /* dx /= dm; ... (Vector3::Normalize) */
+// RTX_LIGHT_DIR: LightUtils::GetDirectionToLight (Utils.h:341-353) from originOffset: lx, ly, lz normalised
+// from the magnitude mag (the shadow ray's tmax), for the light record L0 of type ltype.
+#define RTX_LIGHT_DIR()                                                                           \
+    const bool known = (ltype == RTX_LIGHT_POINT || ltype == RTX_LIGHT_DIRECTIONAL);              \
+    float lx = known ? L0.x - oox : 0.f, ly = known ? L0.y - ooy : 0.f, lz = known ? L0.z - ooz : 0.f; \
+    const float mag = sqrtf(lx * lx + ly * ly + lz * lz);                                         \
+    div3_exact(lx, ly, lz, mag)
+// RTX_LIGHT_TERM: one unoccluded light's term of lighting mode MODE (Renderer.cpp:143-175) added to fr, fg,
+// fb; KINDS and COUNT are shade's.
+#define RTX_LIGHT_TERM(MODE, KINDS, COUNT)                                                        \
+    if (MODE == RTX_MODE_COMBINED || MODE == RTX_MODE_RADIANCE) {                                 \
+        /* LightUtils::GetRadiance (Utils.h:355-369) at hit.origin */                             \
+        float s = 0.f;                                                                            \
+        bool any = true;                                                                          \
+        if (ltype == RTX_LIGHT_POINT) {                                                           \
+            const float ex = L0.x - hx, ey = L0.y - hy, ez = L0.z - hz;                           \
+            s = L1.w / (ex * ex + ey * ey + ez * ez);                                             \
+        } else if (ltype == RTX_LIGHT_DIRECTIONAL) {                                              \
+            s = L1.w;                                                                             \
+        } else {                                                                                  \
+            any = false;                                                                          \
+        }                                                                                         \
+        const float rr = any ? L1.x * s : 0.f, rg = any ? L1.y * s : 0.f, rb = any ? L1.z * s : 0.f; \
+        if (MODE == RTX_MODE_RADIANCE) {                                                          \
+            fr += rr; fg += rg; fb += rb;                                                         \
+        } else {                                                                                  \
+            const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);                              \
+            const RGB br = shade<KINDS>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, COUNT);  \
+            fr += (rr * oa) * br.r; fg += (rg * oa) * br.g; fb += (rb * oa) * br.b;               \
+        }                                                                                         \
+    } else if (MODE == RTX_MODE_OBSERVED_AREA) {                                                  \
+        const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);                                  \
+        fr += oa; fg += oa; fb += oa;                                                             \
+    } else if (MODE == RTX_MODE_BRDF) {                                                           \
+        const RGB br = shade<KINDS>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, COUNT);      \
+        fr += br.r; fg += br.g; fb += br.b;                                                       \
+    }
+// RTX_MAX_TO_ONE: ColorRGB::MaxToOne (ColorRGB.h:12-17) on fr, fg, fb.  RTX_PACK_PX: their frame-buffer word
+// in F's pixel format.
+#define RTX_MAX_TO_ONE()                                                                          \
+    const float mv = smax(fr, smax(fg, fb));                                                      \
+    if (mv > 1.f) { fr /= mv; fg /= mv; fb /= mv; }
+#define RTX_PACK_PX(F) ((q8(fr) << F.rshift) | (q8(fg) << F.gshift) | (q8(fb) << F.bshift) | F.amask)
 #define f_mode (kComb ? RTX_MODE_COMBINED : F.mode)
 #define f_shadows (kComb ? 1 : F.shadows)
 #define n_sph (kNoSph ? 0u : S.n_spheres)
@@ -989,6 +1057,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     constexpr bool kNoMesh = (SPEC & kSpecNoMesh) != 0;
     constexpr bool kRoom = (SPEC & kSpecRoomPlanes) != 0 && (SPEC & kSpecFivePlanes) != 0;
     constexpr bool kCullBack = (SPEC & kSpecCullBack) != 0 && !COUNT;
+    constexpr bool kStored = PHASE == 8 || PHASE == 9;   // the hit record is a stored hit pass's (the planes)
 #if RTX_STAMPS
     // diagnostic build only: per-wave {start, end, hw_id} in the counters buffer
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
@@ -1020,19 +1089,8 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     if (COUNT || RTX_STAMPS) for (int k = 0; k < kNumCounters; ++k) cnt.c[k] = 0;
     if (COUNT && valid) cnt.c[kPixels] = 1;
 
-    // ---- primary ray (Renderer.cpp:104-114; Matrix::TransformVector Matrix.cpp:35-42)
-    // (px + 0.5f) / W and (2 * (py + 0.5f)) / H as Markstein quotients with the exact
-    // reciprocals RN(1/W), RN(1/H) (divided on the host, FrameArgs): numerators in [0.5, 2^17], divisors in
-    // [1, 2^16] lie inside div_rn's domain (rtx_fastdiv.h), so each is the IEEE quotient.
-    const int W = static_cast<int>(F.width), H = static_cast<int>(F.height);
-    const float fW = static_cast<float>(W), fH = static_cast<float>(H);
-    const float cx = (2.f * div_rn(px + 0.5f, fW, F.inv_width) - 1) * F.aspect * V.fov;
-    const float cy = (1.f - div_rn(2.f * (py + 0.5f), fH, F.inv_height)) * V.fov;
-    float dx = V.right[0] * cx + V.up[0] * cy + V.forward[0] * 1.f;
-    float dy = V.right[1] * cx + V.up[1] * cy + V.forward[1] * 1.f;
-    float dz = V.right[2] * cx + V.up[2] * cy + V.forward[2] * 1.f;
-    const float dm = sqrtf(dx * dx + dy * dy + dz * dz);
-    div3_exact(dx, dy, dz, dm);   // dx /= dm; ... (Vector3::Normalize)
+    // ---- primary ray
+    RTX_PRIMARY_DIR(F, V);
     unsigned long long vslow;
     const Ray vr = make_ray(V.origin[0], V.origin[1], V.origin[2], dx, dy, dz, 0.0001f, FLT_MAX, vslow);
     const unsigned long long active = ballot(valid);
@@ -1054,7 +1112,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     // kind: 0 none, 1 sphere, 2 plane, 3 triangle; best_idx: the record's BYTE offset
     uint32_t best_kind = 0, best_idx = 0;
     // (PHASE 5 reads the hit record PHASE 4 wrote, PHASE 8 the hit pass's: no closest-hit work)
-    for (uint32_t i = 0; i < ((PHASE == 5 || PHASE == 6 || PHASE == 8) ? 0u : n_sph * 16u); i += 16u) {
+    for (uint32_t i = 0; i < ((PHASE == 5 || PHASE == 6 || kStored) ? 0u : n_sph * 16u); i += 16u) {
         const float4 s = ldcb16(S.spheres, opaque(i));
         if (COUNT && valid) cnt.c[kSphere]++;
         const SphereProj q = sphere_perp(s, vr);
@@ -1073,7 +1131,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     // divisor domain with its RN(1/d) already in the ray, so when the host found the numerators
     // inside theirs too, t = RN(a / d) costs 3 VALU instead of the 11 of IEEE `/`.
     const bool room_p =
-        kRoom && PHASE != 5 && PHASE != 6 && PHASE != 8 && !RTX_ABL_PPLANE &&
+        kRoom && PHASE != 5 && PHASE != 6 && !kStored && !RTX_ABL_PPLANE &&
         (active & ~ballot(finite3(vr.ox, vr.oy, vr.oz))) == 0;
     if (room_p) {
         // the view's record through a readfirstlane'd index: scalar loads (the view index
@@ -1099,7 +1157,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
             best_idx = b ? static_cast<uint32_t>(k * 32) : best_idx;
         });
     }
-    for (uint32_t i = 0; i < ((RTX_ABL_PPLANE || room_p || PHASE == 5 || PHASE == 6 || PHASE == 8) ? 0u : n_pl * 32u);
+    for (uint32_t i = 0; i < ((RTX_ABL_PPLANE || room_p || PHASE == 5 || PHASE == 6 || kStored) ? 0u : n_pl * 32u);
          i += 32u) {
         float4 p0, p1;
         ldcb32(S.planes, opaque(i), p0, p1);
@@ -1197,9 +1255,9 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         hx = r0.x; hy = r0.y; hz = r0.z; nx = r0.w; ny = r1.x; nz = r1.y;
         mat = __float_as_uint(r1.z);
         did = __float_as_uint(r1.w) != 0u;
-    } else if (PHASE == 8) {
-        // Deferred shading: closestHit from the stored hit pass (rtx.h, rtx_aov_planes).  Lanes outside
-        // the frame load nothing and hit nothing; the material index is clamped before any material
+    } else if (kStored) {
+        // Deferred shading and the shadow pass: closestHit from the stored hit pass (rtx.h, rtx_aov_planes).
+        // Lanes outside the frame load nothing and hit nothing; the material index is clamped before any material
         // load, whatever the planes hold (a stale pass, planes the caller edited).
         if (valid) {
             const size_t o = static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
@@ -1260,6 +1318,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     float fr = 0.f, fg = 0.f, fb = 0.f;
     const unsigned long long hitmask = ballot(did);
     unsigned long long lm_occ = 0;   // PHASE 5: the lanes whose shadow ray toward `light` is occluded
+    uint32_t sh_bits = 0;            // PHASE 9: bit l = this lane's shadow ray toward light l is occluded
     // The reference's light loop (Renderer.cpp:128-176).  Light-major frames run it in two launches:
     // PHASE 5 casts its one light's shadow ray and only records the occluded lanes; PHASE 6 (lm_shade)
     // runs it over every light with each light's occlusion the one PHASE 5 published
@@ -1314,10 +1373,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
             float4 L0, L1;
             ldcb32(S.lights, opaque(li * 32u), L0, L1);
             const int ltype = kPoint ? RTX_LIGHT_POINT : __float_as_int(L0.w);
-            const bool known = (ltype == RTX_LIGHT_POINT || ltype == RTX_LIGHT_DIRECTIONAL);
-            float lx = known ? L0.x - oox : 0.f, ly = known ? L0.y - ooy : 0.f, lz = known ? L0.z - ooz : 0.f;
-            const float mag = sqrtf(lx * lx + ly * ly + lz * lz);
-            div3_exact(lx, ly, lz, mag);
+            RTX_LIGHT_DIR();
             bool occ = false;
             if (lm_shade && f_shadows) {   // PHASE 6: published by the previous launch
                 const unsigned long long mk = F.lm_mask[static_cast<size_t>(tile) * F.lm_lights + li];
@@ -1330,11 +1386,12 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
                 unsigned long long live = hitmask;
                 const bool sfast = (hitmask & sslow) == 0 && S.tri_fast;
                 const int soct =
-                    (sfast && S.oct_bytes && (PHASE == 0 || PHASE == 5 || PHASE == 8) && n_mesh) ? batch_octant(sr, hitmask) : -1;
+                    (sfast && S.oct_bytes && (PHASE == 0 || PHASE == 5 || kStored) && n_mesh) ? batch_octant(sr, hitmask)
+                                                                                              : -1;
                 // exact cull of the light's anchor: lanes with mag <= cull_T[li] (and a direction
                 // normalised from at least 2^-30)
                 const bool scull =
-                    kCull && S.cull_stride && sfast && (PHASE == 0 || PHASE == 2 || PHASE == 5 || PHASE == 8) && n_mesh;
+                    kCull && S.cull_stride && sfast && (PHASE == 0 || PHASE == 2 || PHASE == 5 || kStored) && n_mesh;
                 CullRay sq{};
                 if (scull)
                     sq = cull_ray(S.cull + static_cast<size_t>(kMaxViews + li) * (S.cull_stride / 16u), sr,
@@ -1397,7 +1454,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
 #if RTX_STAMPS
                 const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
 #endif
-                for (uint32_t mi = 0; mi < ((RTX_ABL_SMESH || !(PHASE == 0 || PHASE == 5 || PHASE == 8)) ? 0u : n_mesh); ++mi) {
+                for (uint32_t mi = 0; mi < ((RTX_ABL_SMESH || !(PHASE == 0 || PHASE == 5 || kStored)) ? 0u : n_mesh); ++mi) {
                     if (!live) break;
                     float st = 0.f;
                     uint32_t stri = 0;
@@ -1456,6 +1513,10 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
                 lm_occ = ballot(occ);
                 continue;
             }
+            if (PHASE == 9) {   // the shadow pass keeps DoesHit's answer for every light and shades nothing
+                sh_bits |= (occ ? 1u : 0u) << li;
+                continue;
+            }
             if (!did) continue;
             if (occ) {
                 if (COUNT) cnt.c[kOccluded]++;
@@ -1463,35 +1524,15 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
                 continue;
             }
             if (COUNT) cnt.c[kShadeBase]++;
-            if (f_mode == RTX_MODE_COMBINED || f_mode == RTX_MODE_RADIANCE) {
-                // LightUtils::GetRadiance (Utils.h:355-369) at hit.origin
-                float s = 0.f;
-                bool any = true;
-                if (ltype == RTX_LIGHT_POINT) {
-                    const float ex = L0.x - hx, ey = L0.y - hy, ez = L0.z - hz;
-                    s = L1.w / (ex * ex + ey * ey + ez * ez);
-                } else if (ltype == RTX_LIGHT_DIRECTIONAL) {
-                    s = L1.w;
-                } else {
-                    any = false;
-                }
-                const float rr = any ? L1.x * s : 0.f, rg = any ? L1.y * s : 0.f, rb = any ? L1.z * s : 0.f;
-                if (f_mode == RTX_MODE_RADIANCE) {
-                    fr += rr; fg += rg; fb += rb;
-                } else {
-                    const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
-                    const RGB br = shade<kKinds>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, COUNT);
-                    fr += (rr * oa) * br.r; fg += (rg * oa) * br.g; fb += (rb * oa) * br.b;
-                }
-            } else if (f_mode == RTX_MODE_OBSERVED_AREA) {
-                const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
-                fr += oa; fg += oa; fb += oa;
-            } else if (f_mode == RTX_MODE_BRDF) {
-                const RGB br = shade<kKinds>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, COUNT);
-                fr += br.r; fg += br.g; fb += br.b;
-            }
+            RTX_LIGHT_TERM(f_mode, kKinds, COUNT)
         }
         if (did && PHASE != 5) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
+    }
+    if (PHASE == 9) {   // the shadow plane's word (rtx_render_shadows_async): a miss and a lightless scene store 0
+        if (valid)
+            F.occ_bits[static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
+                       static_cast<size_t>(px)] = sh_bits;
+        return;
     }
     if (PHASE == 5) {   // the light's occluded lanes for PHASE 6
         if (lane == 0) F.lm_mask[static_cast<size_t>(tile) * F.lm_lights + light] = lm_occ;
@@ -1507,9 +1548,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         F.hit_key[slot] = ~0ull;
         F.occ_bits[slot] = 0u;
     }
-    // ColorRGB::MaxToOne (ColorRGB.h:12-17)
-    const float mv = smax(fr, smax(fg, fb));
-    if (mv > 1.f) { fr /= mv; fg /= mv; fb /= mv; }
+    RTX_MAX_TO_ONE()
     if constexpr (SS) {
         // Supersampled frame: this lane's sample is (px & (k - 1), py & (k - 1)) of pixel (px / k, py / k),
         // k = 1 << ss_log2 dividing the tile's 8, so the wave holds every sample of its pixels and a
@@ -1523,7 +1562,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         if (valid && ((lane | (lane >> 3)) & m) == 0) {
             const size_t o = (static_cast<size_t>(view) * F.out_height + (static_cast<uint32_t>(py) >> n)) * F.out_width +
                              (static_cast<uint32_t>(px) >> n);
-            F.out_px[o] = (q8(fr) << F.rshift) | (q8(fg) << F.gshift) | (q8(fb) << F.bshift) | F.amask;
+            F.out_px[o] = RTX_PACK_PX(F);
             if (F.out_rgb) {
                 F.out_rgb[3 * o] = fr; F.out_rgb[3 * o + 1] = fg; F.out_rgb[3 * o + 2] = fb;
             }
@@ -1531,7 +1570,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     } else if (valid) {
         const size_t o = static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
                          static_cast<size_t>(px);
-        F.out_px[o] = (q8(fr) << F.rshift) | (q8(fg) << F.gshift) | (q8(fb) << F.bshift) | F.amask;
+        F.out_px[o] = RTX_PACK_PX(F);
         if (F.out_rgb) {
             F.out_rgb[3 * o] = fr; F.out_rgb[3 * o + 1] = fg; F.out_rgb[3 * o + 2] = fb;
         }
@@ -1604,7 +1643,7 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
     uint32_t tile, part = 0, light = 0;
     // PHASE 4/5: the light-major frame (FrameArgs::lm_*): PHASE 4 = PHASE 0 up to the hit record,
     // PHASE 5 = item (tile, light), the tiles in dispatch order and a tile's lights consecutive
-    if (PHASE == 0 || PHASE == 4 || PHASE == 6 || PHASE == 7 || PHASE == 8) {
+    if (PHASE == 0 || PHASE == 4 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9) {
         if (widx >= F.n_tiles) return;
         tile = F.order ? ldc(F.order, widx) : widx;
         if (F.heavy_flag && ldc(F.heavy_flag, tile)) return;   // rendered by the split launches
@@ -2353,6 +2392,94 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
     }
 }
 
+// ====================================================================== relighting
+// Renderer::RenderPixel from originOffset on (Renderer.cpp:126-181) for a stored hit pass whose shadow
+// rays are stored too (rtx_relight*, rtx.h): PHASE 8 with DoesHit replaced by the pixel's bit of the shadow
+// plane, so no ray is cast, nothing is walked, and the kernel needs neither LDS nor a stack.  One lane per
+// pixel, a wave = 64 consecutive pixels of a row (RelightArgs), so the five plane loads and the stores are
+// full-width; the view, the row and the lights are wave-uniform (cameras and lights come by scalar loads).
+// The arithmetic is render_tile's by construction: RTX_PRIMARY_DIR, RTX_LIGHT_DIR, RTX_LIGHT_TERM (with the
+// generic shade<0>: a specialised variant compiles the same operations for the kinds its scene has),
+// RTX_MAX_TO_ONE and RTX_PACK_PX are the text render_tile expands, over div_rn, div3_exact, shade, smax and
+// q8, the functions it calls; the hit point's rebuild is worded as PHASE 8 words it.  The material index is
+// clamped as in PHASE 8; a lane outside the row loads and stores nothing.
+__global__ void __launch_bounds__(kRelightThreads) rtx_relight_kernel(const DevScene S, const RelightArgs A) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t widx = uni(blockIdx.x * (kRelightThreads / 64u) + (threadIdx.x >> 6));
+    const uint32_t per_view = A.segs * A.rows;
+    if (widx >= per_view * A.n_views) return;
+    const uint32_t view = widx / per_view;
+    const uint32_t rem = widx - view * per_view;
+    const uint32_t j = rem / A.segs, seg = rem - j * A.segs;
+    unsigned long long row = j;
+    if (A.stripe_rows) {
+        // view v owns the stripes s with s % step == (first - v) mod step (rtx.h)
+        const uint32_t first = (A.stripe_first + A.stripe_step - view % A.stripe_step) % A.stripe_step;
+        const uint32_t k = j / A.stripe_rows, sub = j % A.stripe_rows;
+        row = (first + static_cast<unsigned long long>(k) * A.stripe_step) * A.stripe_rows + sub;
+    }
+    if (row >= A.height) return;
+    const ViewCam& V = A.cam[view];
+    const int px = static_cast<int>(seg * 64u + lane), py = static_cast<int>(row);
+    const bool valid = px < static_cast<int>(A.width);
+    RTX_PRIMARY_DIR(A, V);
+    (void)dm;
+
+    // ---- closestHit from the planes, as PHASE 8 reads it
+    const size_t o = static_cast<size_t>(view) * A.width * A.height + static_cast<size_t>(py) * A.width +
+                     static_cast<size_t>(px);
+    bool did = false;
+    float t = FLT_MAX, nx = 0.f, ny = 0.f, nz = 0.f;
+    float hx = 0.f, hy = 0.f, hz = 0.f;
+    uint32_t mat = 0, bits = 0;
+    if (valid) {
+        did = A.primitive[o] != 0u;
+        t = A.depth[o];
+        nx = A.normal[3 * o]; ny = A.normal[3 * o + 1]; nz = A.normal[3 * o + 2];
+        const uint32_t m = A.material[o], top = S.n_materials - 1u;
+        mat = m < top ? m : top;
+        if (A.shadows) bits = A.shadow[o];
+    }
+    if (did) { hx = V.origin[0] + dx * t; hy = V.origin[1] + dy * t; hz = V.origin[2] + dz * t; }
+
+    // ---- the reference's light loop (Renderer.cpp:128-176), DoesHit answered by the shadow plane
+    float shadowFactor = 1.f;
+    float fr = 0.f, fg = 0.f, fb = 0.f;
+    Counts cnt;   // (never counted)
+    if (ballot(did)) {
+        const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
+        const float vx = -dx, vy = -dy, vz = -dz;
+        for (uint32_t li = 0; li < S.n_lights; ++li) {
+            float4 L0, L1;
+            ldcb32(S.lights, opaque(li * 32u), L0, L1);
+            const int ltype = __float_as_int(L0.w);
+            RTX_LIGHT_DIR();
+            (void)mag;   // (the shadow ray's tmax: no ray here)
+            if (!did) continue;
+            // (with shadows on the host has checked the plane's light count against the scene's, at most 32)
+            if (A.shadows && li < 32u && ((bits >> li) & 1u)) {
+                shadowFactor *= 0.95f;
+                continue;
+            }
+            RTX_LIGHT_TERM(A.mode, 0, false)
+        }
+        if (did) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
+    }
+    RTX_MAX_TO_ONE()
+    if (valid) {
+        A.out_px[o] = RTX_PACK_PX(A);
+        if (A.out_rgb) {
+            A.out_rgb[3 * o] = fr; A.out_rgb[3 * o + 1] = fg; A.out_rgb[3 * o + 2] = fb;
+        }
+    }
+}
+
+#undef RTX_PRIMARY_DIR
+#undef RTX_LIGHT_DIR
+#undef RTX_LIGHT_TERM
+#undef RTX_MAX_TO_ONE
+#undef RTX_PACK_PX
+
 // ====================================================================== launches
 namespace {
 
@@ -2443,6 +2570,16 @@ void launch_deferred(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s
     if (hstk) hipLaunchKernelGGL((rtx_render_kernel<false, 8, true, 0, true>), grid, dim3(kBlockThreads), 0, s, d, F);
     else if (deep) hipLaunchKernelGGL((rtx_render_kernel<false, 8, true>), grid, dim3(kBlockThreads), 0, s, d, F);
     else launch_phase<8>(variant, grid, s, d, F);
+}
+
+void launch_shadows(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s, const DevScene& d, const FrameArgs& F) {
+    if (hstk) hipLaunchKernelGGL((rtx_render_kernel<false, 9, true, 0, true>), grid, dim3(kBlockThreads), 0, s, d, F);
+    else if (deep) hipLaunchKernelGGL((rtx_render_kernel<false, 9, true>), grid, dim3(kBlockThreads), 0, s, d, F);
+    else launch_phase<9>(variant, grid, s, d, F);
+}
+
+void launch_relight(dim3 grid, hipStream_t s, const DevScene& d, const RelightArgs& A) {
+    hipLaunchKernelGGL(rtx_relight_kernel, grid, dim3(kRelightThreads), 0, s, d, A);
 }
 
 template <bool ANY>

@@ -244,6 +244,9 @@ struct FrameArgs {
     // Deferred shading (PHASE 8, rtx_shade_aov*) reads all four instead, at the same elements, and writes
     // out_px / out_rgb like PHASE 0; `order` may be the frames' (a permutation of the same tiles), and
     // cost, heavy_flag, lm_* and counters are null.
+    // The shadow pass (PHASE 9, rtx_render_shadows_async) reads them the same way and writes, instead of a
+    // colour, the pixel's word of occlusion bits through `occ_bits`, which for this launch is the shadow plane
+    // in the frame's layout (view v at v * width * height), not the split frames' per-heavy-pixel buffer.
     uint32_t aov_mask;
     float* __restrict__ aov_depth;
     float* __restrict__ aov_normal;
@@ -312,6 +315,35 @@ struct AdaptiveArgs {
     const uint32_t* __restrict__ count;
     uint32_t* __restrict__ out_px;
     float* __restrict__ out_rgb;
+};
+
+// Relighting (rtx_relight*): one launch of rtx_relight_kernel over the rows a stored hit pass
+// owns.  A wave is 64 consecutive pixels of one row of one view (kRelightThreads / 64 waves a workgroup,
+// independent), so every plane load and the output store is a full-width row piece; wave w of the launch is
+// segment w % segs of owned row (w / segs) % rows of view w / (segs * rows), segs = ceil(width / 64).  Owned
+// row j of view v is frame row j without stripes, else row j % stripe_rows of the view's (j / stripe_rows)-th
+// owned stripe (FrameArgs' rule); a row at or past `height` is skipped.  The planes are the hit pass's (view v
+// at v * width * height elements) plus the shadow plane (bit l of a pixel = light l occluded), which is read
+// only with shadows on and may be null otherwise.
+constexpr int kRelightThreads = 256;
+constexpr int kMaxShadowLights = 32;   // lights with a bit in the shadow plane's word (PHASE 9)
+struct RelightArgs {
+    ViewCam cam[kMaxViews];
+    uint32_t n_views;
+    float aspect, inv_width, inv_height;
+    uint32_t width, height;
+    int32_t mode, shadows;
+    uint32_t rshift, gshift, bshift, amask;
+    uint32_t segs, rows;          // waves per row, owned rows per view (the largest owner's)
+    uint32_t stripe_rows;         // 0: whole image
+    uint32_t stripe_first, stripe_step;
+    const float* __restrict__ depth;
+    const float* __restrict__ normal;
+    const uint32_t* __restrict__ material;
+    const uint32_t* __restrict__ primitive;
+    const uint32_t* __restrict__ shadow;
+    uint32_t* __restrict__ out_px;
+    float* __restrict__ out_rgb;     // may be null
 };
 
 // Light-major frames (opt-in: RTX_LIGHT_MAJOR=1 always, =auto while a launch has at most kLmSlotsPercent /

@@ -25,6 +25,11 @@ void launch_hit_pass(bool deep, bool hstk, bool cull, dim3 grid, hipStream_t s, 
 // the scene has cull records, or the generic kernel with the deep stacks (which walk without the cull).
 void launch_deferred(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
                      const rtxd::FrameArgs& F);
+// The shadow pass (PHASE 9): the instantiation launch_deferred would take, variant for variant.
+void launch_shadows(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
+                    const rtxd::FrameArgs& F);
+// Relighting (rtx_relight_kernel): grid.x workgroups of kRelightThreads, one wave per 64-pixel row piece.
+void launch_relight(dim3 grid, hipStream_t s, const rtxd::DevScene& d, const rtxd::RelightArgs& A);
 // A ray query (rtx_query_kernel): closest hit or occlusion (`any`) with the default stack, the deep
 // one, or the deep one in HBM; grid.x = the launch's waves, ceil(Q.n / 64) / kWavesPerBlock.
 void launch_query(bool any, bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,

@@ -1,0 +1,268 @@
+// rtx_relight.hip — relighting behind the C-ABI: the shadow pass (PHASE 9: rtx_render_shadows_async, its
+// plane and its copies), the relight that shades the last hit pass plus that plane without a ray
+// (rtx_relight*, rtx_relight_kernel), and their timing entry points.
+#include <cstring>
+
+#include "rtx_ctx.h"
+#include "rtx_launch.h"
+
+using namespace rtxh;
+
+namespace {
+
+// What both passes ask of the context before anything else: a scene, no supersampling, and a last hit
+// pass with all four planes (the checks of deferred shading, rtx_deferred.hip, in its order).
+int pass_checks(rtx_ctx* c, const char* what) {
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    if (c->ss_log2)
+        return fail(c, RTX_E_UNSUPPORTED, std::string("no ") + what + " on a supersampled context (factor " +
+                                              std::to_string(1u << c->ss_log2) + "): the hit pass has one record per pixel");
+    if (!c->aov_last_mask) return fail(c, RTX_E_STATE, "no hit pass rendered yet");
+    if (c->aov_last_mask != static_cast<uint32_t>(RTX_AOV_ALL))
+        return fail(c, RTX_E_STATE, std::string(what) + " needs all four planes: the last hit pass wrote mask " +
+                                        std::to_string(c->aov_last_mask));
+    return RTX_OK;
+}
+
+// The dispatch order of the context's last colour frames when they had the pass's tile set: read, never
+// written, as deferred shading reads it (rtx_deferred.hip).
+const uint32_t* frames_order(rtx_ctx* c, const rtx_render_params& shape, int n_views) {
+    const std::string tk = tiles_key(shape.width, shape.height, n_views, shape.stripe_rows, shape.stripe_first,
+                                     shape.stripe_step);
+    if (c->sched_enabled && c->sched_ready && c->sched_key.compare(0, tk.size(), tk) == 0)
+        return (c->xcd_order ? c->d_order_xcd : c->d_order).get();
+    return nullptr;
+}
+
+// ---- the shadow pass (PHASE 9) ------------------------------------------------------------------
+
+// Checks, the plane and the launch record of a shadow pass over the last hit pass.  The pass gives the
+// shape and the cameras; the kernel runs as the Combined frame with shadows would (that decides the
+// specialised variant, and with it the walk).  Nothing of the colour frames' state is written, and the
+// hit planes and their record are only read.
+int shadows_prepare(rtx_ctx* c, FrameArgs& F, dim3& grid) {
+    if (!c) return RTX_E_INVALID;
+    if (const int rc = pass_checks(c, "shadow pass"); rc != RTX_OK) return rc;
+    if (c->dev.n_lights > static_cast<uint32_t>(kMaxShadowLights))
+        return fail(c, RTX_E_UNSUPPORTED, "the shadow plane holds " + std::to_string(kMaxShadowLights) +
+                                              " lights, the scene has " + std::to_string(c->dev.n_lights));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;   // (on the context stream, like the hit pass)
+    rtx_render_params shape = c->aov_last;
+    shape.lighting_mode = RTX_MODE_COMBINED;
+    shape.shadows_enabled = 1;
+    const int n_views = c->aov_last_views;
+    const size_t npx = static_cast<size_t>(shape.width) * shape.height * static_cast<size_t>(n_views);
+    if (npx > c->d_shadow.cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->shadow_serial = 0;   // (its contents are gone)
+        if (const int rc = c->d_shadow.grow(c, npx); rc != RTX_OK) return rc;
+    }
+    frame_shape(c, c->aov_last_cams, n_views, &shape, shape, 0u, F, grid);
+    F.order = frames_order(c, shape, n_views);
+    F.aov_mask = RTX_AOV_ALL;   // the planes the kernel reads
+    F.aov_depth = c->d_aov_depth;
+    F.aov_normal = c->d_aov_normal;
+    F.aov_material = c->d_aov_material;
+    F.aov_primitive = c->d_aov_primitive;
+    F.occ_bits = c->d_shadow;   // the word the kernel writes, in the frame's layout
+    // the light anchors' cull records, when this is the first launch after an upload (as deferred_prepare)
+    if (!c->facts.deep_stack && !c->facts.hbm_stack && c->dev.cull_stride && c->cull_boxes_pending) {
+        FrameArgs L = F;
+        L.n_views = 0;
+        if (const int rc = cull_views(c, L); rc != RTX_OK) return rc;
+    }
+    return RTX_OK;
+}
+
+int shadows_launch(rtx_ctx* c, const FrameArgs& F, dim3 grid) {
+    if (grid.x == 0) return RTX_OK;
+    const bool deep = c->facts.deep_stack || c->facts.hbm_stack;
+    if (c->facts.hbm_stack)
+        if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
+    const int v = (c->no_spec || deep) ? -1 : spec_variant(c->facts.spec | kSpecCombShadows);
+    launch_shadows(v, deep, c->facts.hbm_stack, grid, c->stream, c->dev, F);
+    HIP_TRY(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// The plane's validity record: the hit pass it belongs to and the lights it was traced for.
+void shadows_remember(rtx_ctx* c) {
+    c->shadow_serial = c->aov_serial;
+    c->shadow_lights = c->light_keys;
+}
+
+// The plane is the last hit pass's: a pass since then may have another shape, and its rows are what a
+// copy reads.
+int shadows_current(rtx_ctx* c) {
+    if (!c->shadow_serial) return fail(c, RTX_E_STATE, "no shadow pass rendered yet");
+    if (c->shadow_serial != c->aov_serial || !c->aov_last_mask)
+        return fail(c, RTX_E_STATE, "the shadow plane belongs to an earlier hit pass: render the shadow pass again");
+    return RTX_OK;
+}
+
+int queue_shadow_copy(rtx_ctx* c, uint32_t* out) {
+    if (!c || !out) return RTX_E_INVALID;
+    if (const int rc = shadows_current(c); rc != RTX_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const CopyPlane plane = {reinterpret_cast<char*>(out), reinterpret_cast<const char*>(c->d_shadow.get()), 4};
+    return queue_rows(c, c->aov_last, c->aov_last_views, &plane, 1);
+}
+
+// ---- the relight --------------------------------------------------------------------------------
+
+// Checks, the frame buffer and the launch record of a relight of the last hit pass: deferred shading's
+// (rtx_deferred.hip), plus the shadow plane's validity with shadows on.
+int relight_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, RelightArgs& A, dim3& grid,
+                    rtx_render_params& shape) {
+    if (!c || !p) return RTX_E_INVALID;
+    if (p->lighting_mode < 0 || p->lighting_mode >= RTX_MODE_COUNT) return fail(c, RTX_E_INVALID, "bad lighting mode");
+    if (p->format.rshift > 24 || p->format.gshift > 24 || p->format.bshift > 24)
+        return fail(c, RTX_E_INVALID, "bad pixel format");
+    if (const int rc = pass_checks(c, "relight"); rc != RTX_OK) return rc;
+    if (c->dev.n_materials < c->aov_last_materials)
+        return fail(c, RTX_E_STATE, "the scene has " + std::to_string(c->dev.n_materials) +
+                                        " materials, the hit pass was traced with " +
+                                        std::to_string(c->aov_last_materials));
+    if (c->dev.n_materials == 0) return fail(c, RTX_E_STATE, "the scene has no material");
+    const bool shadows = p->shadows_enabled != 0;
+    if (shadows) {
+        if (const int rc = shadows_current(c); rc != RTX_OK) return rc;
+        if (c->light_keys != c->shadow_lights)
+            return fail(c, RTX_E_STATE, "the uploaded lights' count, origins or types are not those the shadow pass was "
+                                        "traced for: render the shadow pass again");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // behind a pending split chain, which writes the frame buffer this call sizes and writes
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    shape = c->aov_last;
+    shape.lighting_mode = p->lighting_mode;
+    shape.shadows_enabled = p->shadows_enabled;
+    shape.format = p->format;
+    const int n_views = c->aov_last_views;
+    const size_t npx = static_cast<size_t>(shape.width) * shape.height * static_cast<size_t>(n_views);
+    if (const int rc = frame_buffers(c, npx, want_rgb); rc != RTX_OK) return rc;
+    // the frame's own launch record: its cameras, aspect and reciprocals are the relight's, value for value
+    FrameArgs F;
+    dim3 tiles;
+    frame_shape(c, c->aov_last_cams, n_views, &shape, shape, 0u, F, tiles);
+    std::memset(&A, 0, sizeof A);
+    for (int v = 0; v < n_views; ++v) A.cam[v] = F.cam[v];
+    A.n_views = F.n_views;
+    A.aspect = F.aspect; A.inv_width = F.inv_width; A.inv_height = F.inv_height;
+    A.width = F.width; A.height = F.height;
+    A.mode = F.mode; A.shadows = F.shadows;
+    A.rshift = F.rshift; A.gshift = F.gshift; A.bshift = F.bshift; A.amask = F.amask;
+    A.segs = (F.width + 63u) / 64u;
+    A.rows = F.height;
+    if (F.groups_per_stripe) {   // the largest owner's stripes, row for row (a stripe taller than the frame: its rows)
+        A.stripe_rows = F.groups_per_stripe * kWaveTile;
+        A.stripe_first = F.stripe_first; A.stripe_step = F.stripe_step;
+        if (A.stripe_rows < F.height) A.rows = F.tiles_y * kWaveTile;
+    }
+    A.depth = c->d_aov_depth;
+    A.normal = c->d_aov_normal;
+    A.material = c->d_aov_material;
+    A.primitive = c->d_aov_primitive;
+    A.shadow = shadows ? c->d_shadow.get() : nullptr;
+    A.out_px = c->d_px;
+    A.out_rgb = want_rgb ? c->d_rgb.get() : nullptr;
+    const uint32_t waves = A.segs * A.rows * A.n_views, per = kRelightThreads / 64u;
+    grid = dim3((waves + per - 1) / per, 1, 1);
+    return RTX_OK;
+}
+
+int relight_launch(rtx_ctx* c, const RelightArgs& A, dim3 grid) {
+    if (grid.x == 0) return RTX_OK;
+    launch_relight(grid, c->stream, c->dev, A);
+    HIP_TRY(c, hipGetLastError());
+    return RTX_OK;
+}
+
+}  // namespace
+
+extern "C" int rtx_render_shadows_async(rtx_ctx* c) {
+    FrameArgs F;
+    dim3 grid;
+    int rc = shadows_prepare(c, F, grid);
+    if (rc != RTX_OK) return rc;
+    rc = shadows_launch(c, F, grid);
+    if (rc != RTX_OK) return rc;
+    shadows_remember(c);
+    return RTX_OK;
+}
+
+extern "C" int rtx_gather_shadows_async(rtx_ctx* c, uint32_t* out) { return queue_shadow_copy(c, out); }
+
+extern "C" int rtx_download_shadows(rtx_ctx* c, uint32_t* out) {
+    const int rc = queue_shadow_copy(c, out);
+    if (rc != RTX_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+extern "C" int rtx_device_shadow_buffer(rtx_ctx* c, uint32_t** d) {
+    if (!c || !d) return RTX_E_INVALID;
+    *d = c->d_shadow;
+    return RTX_OK;
+}
+
+extern "C" int rtx_time_shadows(rtx_ctx* c, int iters, float* mean_ms) {
+    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
+    FrameArgs F;
+    dim3 grid;
+    int rc = shadows_prepare(c, F, grid);
+    if (rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        rc = shadows_launch(c, F, grid);
+        if (rc != RTX_OK) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
+    shadows_remember(c);
+    return RTX_OK;
+}
+
+extern "C" int rtx_relight_async(rtx_ctx* c, const rtx_render_params* p, int want_rgb) {
+    RelightArgs A;
+    dim3 grid;
+    rtx_render_params shape;
+    int rc = relight_prepare(c, p, want_rgb != 0, A, grid, shape);
+    if (rc != RTX_OK) return rc;
+    rc = relight_launch(c, A, grid);
+    if (rc != RTX_OK) return rc;
+    remember(c, &shape, c->aov_last_views, want_rgb != 0);
+    return RTX_OK;
+}
+
+extern "C" int rtx_relight(rtx_ctx* c, const rtx_render_params* p, uint32_t* out_px, float* out_rgb) {
+    if (!out_px) return RTX_E_INVALID;
+    const int rc = rtx_relight_async(c, p, out_rgb != nullptr);
+    if (rc != RTX_OK) return rc;
+    return rtx_download(c, out_px, out_rgb);
+}
+
+extern "C" int rtx_time_relight(rtx_ctx* c, const rtx_render_params* p, int want_rgb, int iters, float* mean_ms) {
+    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
+    RelightArgs A;
+    dim3 grid;
+    rtx_render_params shape;
+    int rc = relight_prepare(c, p, want_rgb != 0, A, grid, shape);
+    if (rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        rc = relight_launch(c, A, grid);
+        if (rc != RTX_OK) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
+    remember(c, &shape, c->aov_last_views, want_rgb != 0);
+    return RTX_OK;
+}

@@ -1,6 +1,7 @@
 // rtx_upload.hip — the commit of a packed scene (rtx_pack.h) to the context: its next HBM image,
 // the copies, DevScene and the context's scene state.  The upload-time knobs are read here.
 #include <cstdlib>
+#include <cstring>
 
 #include "rtx_ctx.h"
 
@@ -139,6 +140,12 @@ void set_scene_state(rtx_ctx* c, const PackedScene& P, const rtx_ctx::SceneBuf& 
     c->h_parts_base = c->h_parts;
     c->parts_dev = reinterpret_cast<int4*>(B.d + P.sec[kSecParts].off);
     c->refine.reset_upload(c->refinable);
+    // the lights a shadow ray depends on (origin and type, bit for bit): rtx_relight's validity check
+    c->light_keys.resize(P.n_lights);
+    for (uint32_t i = 0; i < P.n_lights; ++i) {
+        const float4 l = P.lights[2 * i];
+        std::memcpy(c->light_keys[i].data(), &l, 16);
+    }
     c->has_scene = true;
     ++c->scene_gen;
 }

@@ -293,6 +293,63 @@ class DeviceContext:
                   "rtx_time_shade_aov", self.h)
         return ms.value
 
+    def _pass_pixels(self, what: str) -> int:
+        if self._aov_shape is None:
+            raise RuntimeError(f"{what}: the last hit pass was not queued through this object, its size is unknown")
+        return self._aov_shape[0] * self._aov_shape[1] * self._aov_shape[2]
+
+    def render_shadows_async(self) -> None:
+        """Queue the shadow pass of the last hit pass (rtx_render_shadows_async): per pixel one word whose bit
+        l says that light l of the uploaded scene is occluded, kept in HBM for relight()."""
+        abi.check(self.lib.rtx_render_shadows_async(self.h), "rtx_render_shadows_async", self.h)
+
+    def download_shadows(self, out: np.ndarray | None = None) -> np.ndarray:
+        """Copy the shadow plane's owned rows into a full-frame uint32 array and wait (rtx_download_shadows);
+        rows the pass does not own keep what `out` held (zero in a new array)."""
+        if out is None:
+            out = np.zeros(self._pass_pixels("download_shadows"), np.uint32)
+        abi.check(self.lib.rtx_download_shadows(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                  "rtx_download_shadows", self.h)
+        return out
+
+    def gather_shadows_async(self, out: np.ndarray) -> None:
+        abi.check(self.lib.rtx_gather_shadows_async(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                  "rtx_gather_shadows_async", self.h)
+
+    def device_shadow_buffer(self) -> int:
+        """Device address of the shadow plane (0 before the first shadow pass)."""
+        d = C.POINTER(C.c_uint32)()
+        abi.check(self.lib.rtx_device_shadow_buffer(self.h, C.byref(d)), "rtx_device_shadow_buffer", self.h)
+        return C.cast(d, C.c_void_p).value or 0
+
+    def relight_async(self, params: abi.RenderParams, want_rgb: bool = False) -> None:
+        """Queue the relight of the last hit pass into the colour frame buffer (rtx_relight_async): `params`
+        supplies the lighting mode, shadows and pixel format; with shadows the shadow plane answers DoesHit."""
+        abi.check(self.lib.rtx_relight_async(self.h, C.byref(params), int(want_rgb)), "rtx_relight_async", self.h)
+
+    def relight(self, params: abi.RenderParams, want_rgb: bool = True):
+        """The relight (rtx_relight), blocking: (pixels, rgb) like shade_aov()."""
+        if self._aov_shape is None:   # no pass through this object: the library says why
+            self.relight_async(params, want_rgb)
+        n = self._pass_pixels("relight")
+        px = np.zeros(n, np.uint32)
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.lib.rtx_relight(self.h, C.byref(params), px.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                  rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_relight", self.h)
+        return px, rgb
+
+    def time_shadows(self, iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_shadows(self.h, int(iters), C.byref(ms)), "rtx_time_shadows", self.h)
+        return ms.value
+
+    def time_relight(self, params: abi.RenderParams, want_rgb: bool, iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_relight(self.h, C.byref(params), int(want_rgb), int(iters), C.byref(ms)),
+                  "rtx_time_relight", self.h)
+        return ms.value
+
     def time_frames(self, cam, params, iters: int) -> float:
         ms = C.c_float()
         abi.check(self.lib.rtx_time_frames(self.h, C.byref(cam), C.byref(params), int(iters), C.byref(ms)),
@@ -549,6 +606,35 @@ class Renderer:
                                         self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
                                         rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
         abi.check(rc, "rtx_shade_aov", self.ctx.h)
+        self.rgb = rgb
+        return self.buffer
+
+    def _own_pass(self, what: str, probe) -> None:
+        if self.ctx._aov_shape != (self.m_Width, self.m_Height, 1):
+            if self.ctx._aov_shape is None:
+                probe()   # no pass yet: the library says why
+            raise RuntimeError(f"{what}: the context's last hit pass is {self.ctx._aov_shape}, not this renderer's")
+
+    def RenderShadows(self) -> np.ndarray:
+        """The shadow pass of the last RenderAOV (rtx_render_shadows_async; not in the reference's Renderer):
+        per pixel a word whose bit l says light l of the scene uploaded last is occluded, kept on the device
+        for Relight and returned.  Blocking."""
+        self._own_pass("RenderShadows", self.ctx.render_shadows_async)
+        self.ctx.render_shadows_async()
+        return self.ctx.download_shadows()
+
+    def Relight(self, want_rgb: bool = False) -> np.ndarray:
+        """The frame Render would render, shaded from the last RenderAOV's planes and the last
+        RenderShadows' bits without casting a ray (rtx_relight), with the renderer's CURRENT lighting mode,
+        shadows and pixel format; light colours, intensities and material values are the scene's uploaded
+        last.  Explicit, like ShadeAOV.  Blocking; fills self.buffer."""
+        self._own_pass("Relight", lambda: self.ctx.relight_async(self.params(), want_rgb))
+        n = self.m_Width * self.m_Height
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.ctx.lib.rtx_relight(self.ctx.h, C.byref(self.params()),
+                                      self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_relight", self.ctx.h)
         self.rgb = rgb
         return self.buffer
 

@@ -30,7 +30,7 @@
  * and the scheduler's / exact cull's internals are in rtx_diag.h; the environment knobs the library
  * reads are listed in INTEGRATION.md (none of them changes a pixel).  In csrc/ the entry points
  * live by topic: rtx_context.hip, rtx_upload.hip, rtx_frame.hip, rtx_aov.hip (the hit pass),
- * rtx_deferred.hip (deferred shading), rtx_query.hip (ray queries and shaded rays), rtx_adaptive.hip (adaptive supersampling), rtx_group.cpp and
+ * rtx_deferred.hip (deferred shading), rtx_relight.hip (the shadow pass and the relight), rtx_query.hip (ray queries and shaded rays), rtx_adaptive.hip (adaptive supersampling), rtx_group.cpp and
  * rtx_anim_host.hip; the render kernel is rtx_hip.hip.
  */
 #ifndef RTX_H_
@@ -363,6 +363,67 @@ int rtx_shade_aov_async(rtx_ctx* ctx, const rtx_render_params* params, int want_
 /* Blocking: the call above, then rtx_download into the caller's full-frame buffers (out_rgb may be
  * NULL). */
 int rtx_shade_aov(rtx_ctx* ctx, const rtx_render_params* params, uint32_t* out_pixels, float* out_rgb);
+
+/* ---- relighting: a hit pass's shadow rays stored once, then shaded with no tracing ------
+ * A shadow ray depends only on the hit record and on the light's origin and type
+ * (LightUtils::GetDirectionToLight, Utils.h:341-353, is light.origin - origin for both types).  So a
+ * change of light colours or intensities, of any material value, of the lighting mode, of the shadow
+ * toggle or of the pixel format leaves every Scene::DoesHit result as it was.  The shadow pass stores
+ * those results beside the hit pass; the relight shades hit pass + results without casting a ray.
+ *
+ * rtx_render_shadows_async runs on the records of the context's last hit pass, which must have written
+ * all four planes (RTX_AOV_ALL); size, views, stripes and cameras are the pass's, as for rtx_shade_aov*.
+ * It writes one uint32_t per owned pixel into the shadow plane in HBM, view v at v * width * height:
+ *     bit l = didHit && Scene::DoesHit(Ray{originOffset, directionToLight_l, 0.0001f, |l|})
+ * the test of Renderer.cpp:130-141 for light l, with the hit taken from the planes as rtx_shade_aov
+ * takes it (originOffset = origin + normal * 0.0001f).  Every light's bit is defined (the reference's
+ * `continue` skips the shading, not the later lights); bits >= the scene's light count are 0, and so
+ * is a miss's word.  The walk is the one the frame's shadow rays take for the scene.  The context
+ * records which hit pass the plane belongs to (every hit pass makes an earlier plane stale) and the
+ * lights it was traced for: their count, and each one's origin and type, bit for bit.
+ * It is no frame for the schedule or any policy, reads the frames' dispatch order as rtx_shade_aov
+ * does, and queues on the context stream.
+ * Errors (the context keeps working after each): NULL ctx: RTX_E_INVALID; no scene, no hit pass yet or
+ * a last pass whose mask is not RTX_AOV_ALL: RTX_E_STATE; a supersample factor other than 1, or a scene
+ * with more than 32 lights: RTX_E_UNSUPPORTED. */
+int rtx_render_shadows_async(rtx_ctx* ctx);
+/* The plane, by the rules of the hit pass's copies (rtx_download_aov, rtx_gather_aov_async,
+ * rtx_device_aov_buffers): `out` is a full-frame array of width * height * views words of which only
+ * the rows the pass owns are written; download blocks, gather queues the copy on the context stream.
+ * NULL ctx or out: RTX_E_INVALID; no shadow pass yet, or a hit pass since: RTX_E_STATE.  The device
+ * pointer (NULL before the first shadow pass) stays valid until a larger pass or rtx_destroy; the
+ * passes queued so far are complete in it after rtx_synchronize. */
+int rtx_download_shadows(rtx_ctx* ctx, uint32_t* out);
+int rtx_gather_shadows_async(rtx_ctx* ctx, uint32_t* out);
+int rtx_device_shadow_buffer(rtx_ctx* ctx, uint32_t** d);
+
+/* rtx_relight* is rtx_shade_aov* with DoesHit answered by the shadow plane: `params` supplies
+ * lighting_mode, shadows_enabled and format (its size and stripe fields are ignored), the hit pass
+ * everything else.  Per owned pixel the result is Renderer::RenderPixel from originOffset on
+ * (Renderer.cpp:126-181), the hit rebuilt from the planes as rtx_shade_aov rebuilds it; with shadows
+ * on, light l is occluded when bit l of the pixel's word is set; with shadows off the plane is neither
+ * read nor required.  It writes the colour frame buffer and sets the last-frame record to the pass's
+ * shape, so rtx_download, rtx_gather_async and rtx_device_buffers work unchanged.
+ *
+ * Guarantee: while the geometry, the material indices, the cameras and the lights' count, origins and
+ * types are those of the two passes, the frame buffer holds word for word, in both planes, what
+ * rtx_render_views_async leaves there for the pass's cameras, size and stripes and these mode, shadows
+ * and format; so it is the reference's frame bit for bit wherever the reference calls no powf.  Light
+ * colours and intensities and material VALUES are read from the scene uploaded at the time of the
+ * call: upload, relight, upload, relight is the relighting loop, each step one pass over the planes.
+ * The host checks the lights (below); changed geometry, material indices or a device Update since the
+ * passes are the caller's responsibility, exactly as for rtx_shade_aov (colours unspecified, loads in
+ * range).
+ *
+ * The call is no frame for the schedule or any policy, casts no ray, and queues on the context
+ * stream, behind a pending split chain.
+ * Errors: those of rtx_shade_aov, and with shadows_enabled: no shadow pass yet, a hit pass newer than
+ * the shadow plane, or uploaded lights whose count, or any origin or type, differ bitwise from the
+ * recorded ones: RTX_E_STATE. */
+int rtx_relight_async(rtx_ctx* ctx, const rtx_render_params* params, int want_rgb);
+/* Blocking: the call above, then rtx_download into the caller's full-frame buffers (out_rgb may be
+ * NULL). */
+int rtx_relight(rtx_ctx* ctx, const rtx_render_params* params, uint32_t* out_pixels, float* out_rgb);
 
 /* ---- ray queries: closest hit and occlusion for caller-supplied rays ---------------
  * The traversal behind a frame's rays, for rays the caller makes: a line-of-sight test, a pick ray,

@@ -5,7 +5,7 @@
  * the exact cull, the device Update's phase stamps).  None of these has a counterpart in the
  * reference's Renderer (source/Renderer.h:17-61); the benchmark (bench.py), the tools and the tests
  * use them.  Same conventions as rtx.h: RTX_OK or a negative RTX_E_* code, nothing throws.
- * (Implemented in csrc/rtx_diag.hip; the hit pass's timing in rtx_aov.hip, deferred shading's in rtx_deferred.hip, the device Update's
+ * (Implemented in csrc/rtx_diag.hip; the hit pass's timing in rtx_aov.hip, deferred shading's in rtx_deferred.hip, relighting's in rtx_relight.hip, the device Update's
  * stamps in rtx_anim_host.hip.)
  */
 #ifndef RTX_DIAG_H_
@@ -31,6 +31,11 @@ int rtx_time_aov_frames(rtx_ctx* ctx, const rtx_camera* cam, const rtx_render_pa
  * shades of the last hit pass, the mean device time of one in ms.  The frame buffer then holds the
  * shaded pass, as after rtx_shade_aov_async. */
 int rtx_time_shade_aov(rtx_ctx* ctx, const rtx_render_params* params, int want_rgb, int iters, float* mean_ms);
+/* The same for relighting (rtx.h): `iters` back-to-back shadow passes (rtx_render_shadows_async) or relights
+ * (rtx_relight_async(params, want_rgb)) of the last hit pass, the mean device time of one in ms.  The
+ * shadow plane or the frame buffer then holds the result, as after the call timed. */
+int rtx_time_shadows(rtx_ctx* ctx, int iters, float* mean_ms);
+int rtx_time_relight(rtx_ctx* ctx, const rtx_render_params* params, int want_rgb, int iters, float* mean_ms);
 /* The same for a ray query on device pointers (rtx.h): `iters` back-to-back queries of the same n rays,
  * the mean device time of one in ms.  what 0: rtx_trace_rays_device(d_rays, n, mask, d_out); 1:
  * rtx_occluded_device(d_rays, n, d_occ); 2: the yardstick, a device-to-device copy of the n rays (32 n

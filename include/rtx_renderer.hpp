@@ -105,6 +105,21 @@ public:
         const rtx_render_params p = Params();
         Check(rtx_shade_aov(m_Ctx, &p, m_Pixels.data(), nullptr), "rtx_shade_aov");
     }
+    // Relighting (rtx_render_shadows_async, rtx_relight; not in the reference).  RenderShadows stores the
+    // shadow rays of the last RenderAov (all four planes) for the uploaded lights, one word of occlusion bits
+    // per pixel, and returns them.  Relight then shades that pass with the renderer's CURRENT lighting mode,
+    // shadows and pixel format without casting a ray, reading light colours, intensities and material values
+    // from the scene uploaded last; it fills Pixels().  Explicit, like ShadeAov.
+    std::vector<uint32_t> RenderShadows() {
+        std::vector<uint32_t> bits(static_cast<size_t>(m_Width) * m_Height);
+        Check(rtx_render_shadows_async(m_Ctx), "rtx_render_shadows_async");
+        Check(rtx_download_shadows(m_Ctx, bits.data()), "rtx_download_shadows");
+        return bits;
+    }
+    void Relight() {
+        const rtx_render_params p = Params();
+        Check(rtx_relight(m_Ctx, &p, m_Pixels.data(), nullptr), "rtx_relight");
+    }
 
     // Ray queries against the uploaded scene (rtx_trace_rays / rtx_occluded; not in the reference's
     // Renderer): Scene::GetClosestHit and Scene::DoesHit on the caller's rays, uninterpreted (rtx.h).
