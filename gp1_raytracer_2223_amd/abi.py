@@ -152,6 +152,8 @@ def load_host() -> C.CDLL:
         lib.rtx_host_scene_animated.restype = C.c_int
         lib.rtx_host_camera_set.argtypes = [VP, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]
         lib.rtx_host_camera_set.restype = C.c_int
+        lib.rtx_host_light_set_origin.argtypes = [VP, C.c_uint32, C.POINTER(C.c_float)]
+        lib.rtx_host_light_set_origin.restype = C.c_int
         lib.rtx_host_parse_obj.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32),
                                            C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
                                            C.c_uint32, C.c_uint32]
@@ -187,7 +189,8 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_render_adaptive_async", "rtx_render_adaptive", "rtx_adaptive_refined", "rtx_time_adaptive_frames",
                "rtx_shade_aov_async", "rtx_shade_aov", "rtx_time_shade_aov",
                "rtx_render_shadows_async", "rtx_download_shadows", "rtx_gather_shadows_async",
-               "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows", "rtx_time_relight"]
+               "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows", "rtx_time_relight",
+               "rtx_update_shadows_async", "rtx_refresh_shadows_async", "rtx_time_shadows_update"]
 
 
 def load_hip() -> C.CDLL:
@@ -372,6 +375,12 @@ def load_hip() -> C.CDLL:
             for n in ("rtx_render_shadows_async", "rtx_download_shadows", "rtx_gather_shadows_async",
                       "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows",
                       "rtx_time_relight"):
+                getattr(lib, n).restype = C.c_int
+        if hasattr(lib, "rtx_update_shadows_async"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_update_shadows_async.argtypes = [VP, C.c_uint32]
+            lib.rtx_refresh_shadows_async.argtypes = [VP, C.POINTER(C.c_uint32)]
+            lib.rtx_time_shadows_update.argtypes = [VP, C.c_uint32, C.c_int, C.POINTER(C.c_float)]
+            for n in ("rtx_update_shadows_async", "rtx_refresh_shadows_async", "rtx_time_shadows_update"):
                 getattr(lib, n).restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]

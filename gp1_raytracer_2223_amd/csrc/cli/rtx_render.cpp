@@ -5,6 +5,7 @@
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
 //              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T] [--deferred] [--relight]
+//              [--move-light L,X,Y,Z]...
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -29,7 +30,12 @@
 // --relight (single frames only, and not with --deferred: the combinations --deferred refuses) makes the image from
 // one hit pass, its shadow pass and a relight (rtx_render_aov, rtx_render_shadows_async, rtx_relight): the same BMP;
 // with --aov also PREFIX_shadow.u32, one word per pixel whose bit l says light l is occluded.
+// --move-light L,X,Y,Z (repeatable) sets light L's origin to (X, Y, Z) before anything is uploaded, for any run.
+// With --relight the hit pass and the full shadow pass run with the scene's ORIGINAL lights; then the moved scene is
+// uploaded, rtx_refresh_shadows_async re-traces only the moved lights, and the relight makes the image: the same
+// BMP as the plain run with the same moves, and with --aov the refreshed PREFIX_shadow.u32.
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <chrono>
 #include <condition_variable>
@@ -44,6 +50,7 @@
 #include <memory>
 #include <numeric>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <sys/resource.h>
@@ -324,7 +331,7 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
                              "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
-                             "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred] [--relight]\n",
+                             "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred] [--relight] [--move-light L,X,Y,Z]...\n",
                      argv[0]);
         return 2;
     }
@@ -334,6 +341,7 @@ int main(int argc, char** argv) {
     std::vector<float> seq;
     float t = -1.f;
     bool shadows = true, device_update = false, deferred = false, relight = false;
+    std::vector<std::pair<uint32_t, std::array<float, 3>>> moves;   // --move-light, in the order given
     int pos = 0;
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i];
@@ -367,6 +375,17 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "--adaptive K,T: the factor K must be 2, 4 or 8 and the threshold T 0..255\n");
                 return 2;
             }
+        }
+        else if (a == "--move-light") {   // checked here: a malformed move ends the program before any device work
+            int l = -1;
+            std::array<float, 3> o{};
+            char tail = 0;
+            const int got = i + 1 < argc ? std::sscanf(argv[++i], "%d,%f,%f,%f%c", &l, &o[0], &o[1], &o[2], &tail) : 0;
+            if (got != 4 || l < 0) {
+                std::fprintf(stderr, "--move-light L,X,Y,Z: a light index (0 or above) and three coordinates\n");
+                return 2;
+            }
+            moves.push_back({static_cast<uint32_t>(l), o});
         }
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else if (a == "--aov" && i + 1 < argc) aov = argv[++i];
@@ -420,6 +439,31 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "scene %s: %s\n", scene.c_str(), err);
         return 1;
     }
+    // --move-light: the scene's own origins are kept for --relight's first two passes; a light the scene does
+    // not have is refused here, before any device work
+    std::vector<std::pair<uint32_t, std::array<float, 3>>> unmoved;
+    {
+        rtx_scene s0;
+        rtx_camera c0;
+        if (!moves.empty() && rtx_host_scene_view(hs, &s0, &c0) != RTX_OK) {
+            std::fprintf(stderr, "rtx_host_scene_view failed\n");
+            rtx_host_scene_destroy(hs);
+            return 1;
+        }
+        for (const auto& m : moves) {
+            if (m.first >= s0.n_lights) {
+                std::fprintf(stderr, "--move-light: scene %s has %u lights, no light %u\n", scene.c_str(), s0.n_lights, m.first);
+                rtx_host_scene_destroy(hs);
+                return 2;
+            }
+            const float* o = s0.lights[m.first].origin;
+            unmoved.push_back({m.first, {o[0], o[1], o[2]}});
+        }
+    }
+    auto place_lights = [](rtx_host_scene* h, const std::vector<std::pair<uint32_t, std::array<float, 3>>>& to) {
+        for (const auto& m : to) rtx_host_light_set_origin(h, m.first, m.second.data());
+    };
+    place_lights(hs, moves);
     if (t >= 0.f) rtx_host_scene_update(hs, t);
     // the pipelined loop's second host scene (run_benchmark): animated scenes, frames in flight,
     // host Update
@@ -432,6 +476,7 @@ int main(int argc, char** argv) {
             char e2[512] = {0};
             if (rtx_host_scene_create(scene.c_str(), assets.empty() ? nullptr : assets.c_str(), &h, e2, sizeof e2) != RTX_OK)
                 break;   // (fewer Updates in flight, or the loop unpipelined)
+            place_lights(h, moves);
             v.push_back(h);
         }
         return v;
@@ -474,8 +519,21 @@ int main(int argc, char** argv) {
                 }
             }
         } else if (relight) {   // one hit pass, its shadow rays stored, shaded from both; --aov writes all five planes
+            // (--move-light: both passes with the scene's own lights, in reverse so that a light moved twice gets
+            // its first origin back; then the moved scene, and a refresh that traces the moved lights only)
+            place_lights(hs, {unmoved.rbegin(), unmoved.rend()});
             const rtx::Renderer::AovFrame f = r.RenderAov(hs, RTX_AOV_ALL, true);
-            const std::vector<uint32_t> bits = r.RenderShadows();
+            std::vector<uint32_t> bits = r.RenderShadows();
+            if (!moves.empty()) {
+                place_lights(hs, moves);
+                rtx_scene s;
+                rtx_camera cam;
+                if (rtx_host_scene_view(hs, &s, &cam) != RTX_OK) throw std::runtime_error("rtx_host_scene_view failed");
+                r.Upload(s);
+                uint32_t traced = 0;
+                bits = r.RefreshShadows(&traced);
+                std::printf("refreshed the shadow plane: light mask 0x%x re-traced\n", traced);
+            }
             r.Relight();
             if (!aov.empty()) {
                 if (!write_plane(aov + "_depth.f32", f.depth) || !write_plane(aov + "_normal.f32", f.normal) ||

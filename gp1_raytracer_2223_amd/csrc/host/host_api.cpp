@@ -131,6 +131,12 @@ extern "C" int rtx_host_camera_set(rtx_host_scene* s, const float origin[3], flo
     return RTX_OK;
 }
 
+extern "C" int rtx_host_light_set_origin(rtx_host_scene* s, uint32_t light, const float origin[3]) {
+    if (!s || !origin || light >= s->scene->m_Lights.size()) return RTX_E_INVALID;
+    for (int k = 0; k < 3; ++k) s->scene->m_Lights[light].origin[k] = origin[k];
+    return RTX_OK;
+}
+
 extern "C" int rtx_host_parse_obj(const char* path, float* positions, uint32_t* n_positions, float* normals,
                                   int32_t* indices, uint32_t* n_indices, uint32_t cap_pos, uint32_t cap_idx) {
     if (!path || !n_positions || !n_indices) return RTX_E_INVALID;

@@ -1325,8 +1325,16 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     // (FrameArgs::lm_mask), no shadow ray cast.
     constexpr bool lm_shade = PHASE == 6;
     if (hitmask) {
-        const uint32_t l_first = (PHASE == 2 || PHASE == 5) ? light : 0u;
-        const uint32_t l_end = (PHASE == 2 || PHASE == 5) ? light + 1 : (RTX_ABL_LIGHTS ? 0u : S.n_lights);
+        // PHASE 9: the lights to trace are a wave-uniform mask (FrameArgs::lm_lights, rtx_kernels.h), and the loop
+        // runs from its lowest to its highest set bit: the first light, which fills the plane-numerator
+        // cache below, is the first traced one
+        uint32_t sh_trace = 0u;
+        if constexpr (PHASE == 9) sh_trace = uni(F.lm_lights);
+        const uint32_t l_first = (PHASE == 2 || PHASE == 5) ? light
+                                 : (PHASE == 9 && sh_trace) ? static_cast<uint32_t>(__builtin_ctz(sh_trace)) : 0u;
+        const uint32_t l_end = (PHASE == 2 || PHASE == 5) ? light + 1
+                               : PHASE == 9 ? (sh_trace ? 32u - static_cast<uint32_t>(__builtin_clz(sh_trace)) : 0u)
+                                            : (RTX_ABL_LIGHTS ? 0u : S.n_lights);
         // originOffset = hit.origin + hit.normal * 0.0001f (Renderer.cpp:126)
         const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
         const float vx = -dx, vy = -dy, vz = -dz;
@@ -1370,6 +1378,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         const bool room_s = kRoom && PHASE != 2 && !RTX_ABL_SPLANE && !room_clear &&
                             (hitmask & ~ballot(finite3(oox, ooy, ooz))) == 0;
         for (uint32_t li = l_first; li < l_end; ++li) {
+            if (PHASE == 9 && !((sh_trace >> li) & 1u)) continue;   // (scalar: a light outside the trace mask)
             float4 L0, L1;
             ldcb32(S.lights, opaque(li * 32u), L0, L1);
             const int ltype = kPoint ? RTX_LIGHT_POINT : __float_as_int(L0.w);
@@ -1529,9 +1538,14 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         if (did && PHASE != 5) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
     }
     if (PHASE == 9) {   // the shadow plane's word (rtx_render_shadows_async): a miss and a lightless scene store 0
-        if (valid)
-            F.occ_bits[static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
-                       static_cast<size_t>(px)] = sh_bits;
+        // An update (rtx_update_shadows_async) carries the untraced lights' bits over: new = (old & keep) |
+        // traced, keep in FrameArgs::heavy_n.  The full pass has keep = 0 and never reads the plane.
+        const uint32_t keep = uni(F.heavy_n);
+        if (valid) {
+            const size_t o = static_cast<size_t>(view) * F.width * F.height + static_cast<size_t>(py) * F.width +
+                             static_cast<size_t>(px);
+            F.occ_bits[o] = sh_bits | (keep ? F.occ_bits[o] & keep : 0u);
+        }
         return;
     }
     if (PHASE == 5) {   // the light's occluded lanes for PHASE 6

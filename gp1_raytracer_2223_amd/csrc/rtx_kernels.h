@@ -247,6 +247,13 @@ struct FrameArgs {
     // The shadow pass (PHASE 9, rtx_render_shadows_async) reads them the same way and writes, instead of a
     // colour, the pixel's word of occlusion bits through `occ_bits`, which for this launch is the shadow plane
     // in the frame's layout (view v at v * width * height), not the split frames' per-heavy-pixel buffer.
+    // Two more fields mean something else in a PHASE 9 launch, which reads neither as declared (lm_lights
+    // is read by PHASE 5 / 6 only, heavy_n by the split launches' PHASE 1 / 2 / 3 only), so that the kernarg
+    // does not grow: `lm_lights` is the TRACE mask (bit l: cast light l's shadow ray; the light loop runs
+    // from its lowest to its highest set bit) and `heavy_n` the KEEP mask of the stored word,
+    //     occ_bits[o] = traced | (keep ? occ_bits[o] & keep : 0).
+    // The full pass is trace = every light, keep = 0, and loads nothing from the plane
+    // (rtx_update_shadows_async, rtx.h).  part_cost stays 0.
     uint32_t aov_mask;
     float* __restrict__ aov_depth;
     float* __restrict__ aov_normal;

@@ -1,5 +1,6 @@
 // rtx_relight.hip — relighting behind the C-ABI: the shadow pass (PHASE 9: rtx_render_shadows_async, its
-// plane and its copies), the relight that shades the last hit pass plus that plane without a ray
+// plane and its copies; rtx_update_shadows_async and rtx_refresh_shadows_async, the same pass over a subset
+// of the lights, merged into the plane), the relight that shades the last hit pass plus that plane without a ray
 // (rtx_relight*, rtx_relight_kernel), and their timing entry points.
 #include <cstring>
 
@@ -40,12 +41,24 @@ const uint32_t* frames_order(rtx_ctx* c, const rtx_render_params& shape, int n_v
 // shape and the cameras; the kernel runs as the Combined frame with shadows would (that decides the
 // specialised variant, and with it the walk).  Nothing of the colour frames' state is written, and the
 // hit planes and their record are only read.
-int shadows_prepare(rtx_ctx* c, FrameArgs& F, dim3& grid) {
+// (its two halves: what every shadow pass checks first, and everything after; an update's own checks go
+// between them.  `trace` names the lights whose shadow rays are cast and `keep` the bits of the stored
+// word that are carried over, new = (old & keep) | traced: the full pass is every light and 0.)
+int shadows_checks(rtx_ctx* c) {
     if (!c) return RTX_E_INVALID;
     if (const int rc = pass_checks(c, "shadow pass"); rc != RTX_OK) return rc;
     if (c->dev.n_lights > static_cast<uint32_t>(kMaxShadowLights))
         return fail(c, RTX_E_UNSUPPORTED, "the shadow plane holds " + std::to_string(kMaxShadowLights) +
                                               " lights, the scene has " + std::to_string(c->dev.n_lights));
+    return RTX_OK;
+}
+
+// Bit l for every uploaded light l (at most kMaxShadowLights = 32 of them, after shadows_checks).
+uint32_t all_lights(const rtx_ctx* c) {
+    return c->dev.n_lights >= 32u ? ~0u : (1u << c->dev.n_lights) - 1u;
+}
+
+int shadows_build(rtx_ctx* c, FrameArgs& F, dim3& grid, uint32_t trace, uint32_t keep) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = join_split(c); rc != RTX_OK) return rc;   // (on the context stream, like the hit pass)
     rtx_render_params shape = c->aov_last;
@@ -66,6 +79,8 @@ int shadows_prepare(rtx_ctx* c, FrameArgs& F, dim3& grid) {
     F.aov_material = c->d_aov_material;
     F.aov_primitive = c->d_aov_primitive;
     F.occ_bits = c->d_shadow;   // the word the kernel writes, in the frame's layout
+    F.lm_lights = trace & all_lights(c);   // (PHASE 9 reads these two as its masks: rtx_kernels.h)
+    F.heavy_n = keep & all_lights(c);
     // the light anchors' cull records, when this is the first launch after an upload (as deferred_prepare)
     if (!c->facts.deep_stack && !c->facts.hbm_stack && c->dev.cull_stride && c->cull_boxes_pending) {
         FrameArgs L = F;
@@ -73,6 +88,11 @@ int shadows_prepare(rtx_ctx* c, FrameArgs& F, dim3& grid) {
         if (const int rc = cull_views(c, L); rc != RTX_OK) return rc;
     }
     return RTX_OK;
+}
+
+int shadows_prepare(rtx_ctx* c, FrameArgs& F, dim3& grid) {
+    if (const int rc = shadows_checks(c); rc != RTX_OK) return rc;
+    return shadows_build(c, F, grid, all_lights(c), 0u);
 }
 
 int shadows_launch(rtx_ctx* c, const FrameArgs& F, dim3 grid) {
@@ -99,6 +119,41 @@ int shadows_current(rtx_ctx* c) {
     if (c->shadow_serial != c->aov_serial || !c->aov_last_mask)
         return fail(c, RTX_E_STATE, "the shadow plane belongs to an earlier hit pass: render the shadow pass again");
     return RTX_OK;
+}
+
+// ---- the incremental shadow pass ----------------------------------------------------------------
+
+// rtx_update_shadows_async's checks after the pass's own: a current plane, the recorded light count, a mask
+// inside it, and every light outside the mask where the plane recorded it.  Nothing is changed.
+int update_checks(rtx_ctx* c, uint32_t lights) {
+    if (const int rc = shadows_checks(c); rc != RTX_OK) return rc;
+    if (const int rc = shadows_current(c); rc != RTX_OK) return rc;
+    if (c->light_keys.size() != c->shadow_lights.size())
+        return fail(c, RTX_E_STATE, "the scene has " + std::to_string(c->light_keys.size()) +
+                                        " lights, the shadow plane was traced for " +
+                                        std::to_string(c->shadow_lights.size()) + ": refresh or render the shadow pass");
+    if (lights & ~all_lights(c))
+        return fail(c, RTX_E_INVALID, "the light mask names a light at or above the scene's " +
+                                          std::to_string(c->dev.n_lights));
+    for (size_t l = 0; l < c->light_keys.size(); ++l)
+        if (!((lights >> l) & 1u) && c->light_keys[l] != c->shadow_lights[l])
+            return fail(c, RTX_E_STATE, "light " + std::to_string(l) + " is outside the mask, and its origin or type is "
+                                            "not the one the shadow plane was traced for");
+    return RTX_OK;
+}
+
+// The lights whose bit of the plane is not valid for the uploaded scene: a changed origin or type, or a
+// light the recorded pass did not have.
+uint32_t dirty_lights(const rtx_ctx* c) {
+    uint32_t dirty = 0;
+    for (size_t l = 0; l < c->light_keys.size(); ++l)
+        if (l >= c->shadow_lights.size() || c->light_keys[l] != c->shadow_lights[l]) dirty |= 1u << l;
+    return dirty;
+}
+
+// Whether there is a plane of the last hit pass to merge into (shadows_current, without the message).
+bool plane_current(const rtx_ctx* c) {
+    return c->shadow_serial && c->shadow_serial == c->aov_serial && c->aov_last_mask;
 }
 
 int queue_shadow_copy(rtx_ctx* c, uint32_t* out) {
@@ -188,6 +243,61 @@ extern "C" int rtx_render_shadows_async(rtx_ctx* c) {
     if (rc != RTX_OK) return rc;
     rc = shadows_launch(c, F, grid);
     if (rc != RTX_OK) return rc;
+    shadows_remember(c);
+    return RTX_OK;
+}
+
+extern "C" int rtx_update_shadows_async(rtx_ctx* c, uint32_t lights) {
+    if (const int rc = update_checks(c, lights); rc != RTX_OK) return rc;
+    if (!lights) return RTX_OK;   // (nothing named and, by the checks, nothing changed)
+    FrameArgs F;
+    dim3 grid;
+    int rc = shadows_build(c, F, grid, lights, ~lights);
+    if (rc != RTX_OK) return rc;
+    rc = shadows_launch(c, F, grid);
+    if (rc != RTX_OK) return rc;
+    shadows_remember(c);
+    return RTX_OK;
+}
+
+extern "C" int rtx_refresh_shadows_async(rtx_ctx* c, uint32_t* traced) {
+    if (const int rc = shadows_checks(c); rc != RTX_OK) return rc;
+    const bool merge = plane_current(c);   // (a current plane holds the pass's pixels: no growth below)
+    const uint32_t trace = merge ? dirty_lights(c) : all_lights(c);
+    if (merge && !trace && c->shadow_lights.size() <= c->light_keys.size()) {   // nothing to trace or to clear
+        if (traced) *traced = 0u;
+        return RTX_OK;
+    }
+    FrameArgs F;
+    dim3 grid;
+    int rc = shadows_build(c, F, grid, trace, merge ? ~trace : 0u);
+    if (rc != RTX_OK) return rc;
+    rc = shadows_launch(c, F, grid);
+    if (rc != RTX_OK) return rc;
+    shadows_remember(c);
+    if (traced) *traced = trace;
+    return RTX_OK;
+}
+
+extern "C" int rtx_time_shadows_update(rtx_ctx* c, uint32_t lights, int iters, float* mean_ms) {
+    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
+    if (const int rc = update_checks(c, lights); rc != RTX_OK) return rc;
+    *mean_ms = 0.f;
+    if (!lights) return RTX_OK;
+    FrameArgs F;
+    dim3 grid;
+    int rc = shadows_build(c, F, grid, lights, ~lights);
+    if (rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        rc = shadows_launch(c, F, grid);
+        if (rc != RTX_OK) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
     shadows_remember(c);
     return RTX_OK;
 }

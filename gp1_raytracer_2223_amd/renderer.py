@@ -303,6 +303,20 @@ class DeviceContext:
         l says that light l of the uploaded scene is occluded, kept in HBM for relight()."""
         abi.check(self.lib.rtx_render_shadows_async(self.h), "rtx_render_shadows_async", self.h)
 
+    def update_shadows_async(self, lights: int) -> None:
+        """Queue the shadow pass for the lights named in `lights` only (bit l = light l) and merge their bits
+        into the plane (rtx_update_shadows_async); every other light must be where the plane recorded it."""
+        abi.check(self.lib.rtx_update_shadows_async(self.h, int(lights) & 0xFFFFFFFF), "rtx_update_shadows_async",
+                  self.h)
+
+    def refresh_shadows_async(self) -> int:
+        """Make the plane valid for the uploaded lights at the least cost (rtx_refresh_shadows_async): the
+        full pass without a current plane, else one launch over the lights that changed.  Returns the mask
+        of the lights traced (0: nothing was launched, or only removed lights' bits were cleared)."""
+        traced = C.c_uint32()
+        abi.check(self.lib.rtx_refresh_shadows_async(self.h, C.byref(traced)), "rtx_refresh_shadows_async", self.h)
+        return traced.value
+
     def download_shadows(self, out: np.ndarray | None = None) -> np.ndarray:
         """Copy the shadow plane's owned rows into a full-frame uint32 array and wait (rtx_download_shadows);
         rows the pass does not own keep what `out` held (zero in a new array)."""
@@ -342,6 +356,12 @@ class DeviceContext:
     def time_shadows(self, iters: int) -> float:
         ms = C.c_float()
         abi.check(self.lib.rtx_time_shadows(self.h, int(iters), C.byref(ms)), "rtx_time_shadows", self.h)
+        return ms.value
+
+    def time_shadows_update(self, lights: int, iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_shadows_update(self.h, int(lights) & 0xFFFFFFFF, int(iters), C.byref(ms)),
+                  "rtx_time_shadows_update", self.h)
         return ms.value
 
     def time_relight(self, params: abi.RenderParams, want_rgb: bool, iters: int) -> float:
@@ -621,6 +641,22 @@ class Renderer:
         for Relight and returned.  Blocking."""
         self._own_pass("RenderShadows", self.ctx.render_shadows_async)
         self.ctx.render_shadows_async()
+        return self.ctx.download_shadows()
+
+    def UpdateShadows(self, lights: int) -> np.ndarray:
+        """RenderShadows for the lights named in `lights` only (bit l = light l), merged into the plane
+        (rtx_update_shadows_async): the step after an upload that moved those lights and no other.  Returns
+        the plane.  Blocking."""
+        self._own_pass("UpdateShadows", lambda: self.ctx.update_shadows_async(lights))
+        self.ctx.update_shadows_async(lights)
+        return self.ctx.download_shadows()
+
+    def RefreshShadows(self) -> np.ndarray:
+        """The plane made valid for the scene uploaded last at the least cost (rtx_refresh_shadows_async):
+        only the lights that moved, appeared or went are traced or cleared; the full pass when there is no
+        plane of the last RenderAOV.  Returns the plane.  Blocking."""
+        self._own_pass("RefreshShadows", self.ctx.refresh_shadows_async)
+        self.ctx.refresh_shadows_async()
         return self.ctx.download_shadows()
 
     def Relight(self, want_rgb: bool = False) -> np.ndarray:

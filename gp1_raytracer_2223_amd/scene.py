@@ -94,6 +94,11 @@ class HostScene:
         o = (C.c_float * 3)(*origin)
         abi.check(self._lib.rtx_host_camera_set(self._h, o, fov_degrees, pitch, yaw), "rtx_host_camera_set")
 
+    def set_light_origin(self, light: int, origin) -> None:
+        """Move light `light` (rtx_host_light_set_origin): upload again, then refresh the shadow plane."""
+        o = (C.c_float * 3)(*origin)
+        abi.check(self._lib.rtx_host_light_set_origin(self._h, int(light), o), "rtx_host_light_set_origin")
+
     def view(self) -> tuple[abi.Scene, abi.Camera]:
         """The flat scene (pointers into this object's arrays, valid until its next update) and
         the camera.  Both hold a reference to this HostScene, so `HostScene(name).view()` keeps the

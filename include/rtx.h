@@ -397,6 +397,40 @@ int rtx_download_shadows(rtx_ctx* ctx, uint32_t* out);
 int rtx_gather_shadows_async(rtx_ctx* ctx, uint32_t* out);
 int rtx_device_shadow_buffer(rtx_ctx* ctx, uint32_t** d);
 
+/* ---- incremental shadow pass: re-trace only the lights that moved ---------------------------
+ * Bit l of a pixel's word depends only on the stored hit record and on light l's origin and type, so a
+ * light that moved invalidates its own bit and no other.  The two calls below are the shadow pass over
+ * a subset of the lights: the same checks in the same order, the same shape, views, stripes and
+ * cameras, the same walk and kernel, no frame for any policy, nothing of the colour frame buffer or of
+ * the hit planes written.  They differ from rtx_render_shadows_async in the lights traced and in how
+ * the word is stored.  For every owned pixel
+ *     new = (old & keep) | traced
+ * where bit l of `traced` is the shadow pass's bit l for the scene uploaded now when l is in the trace
+ * mask (0 otherwise), and `keep` holds the bits below the uploaded light count that are not traced and
+ * were valid before.  Rows the pass does not own are not touched.  The full pass is keep = 0; it does
+ * not read the plane.
+ *
+ * rtx_update_shadows_async traces the lights named in `lights` (bit l = light l).  It needs a current
+ * plane (a shadow pass of the last hit pass) and an uploaded light count equal to the recorded one;
+ * every light NOT named must have the recorded origin and type, bit for bit, so the plane is never
+ * left silently stale.  A named light whose key did not change is traced again (the same word).
+ * lights == 0 with nothing changed launches nothing.  On success the recorded lights become the
+ * uploaded ones, and rtx_relight* with shadows on is accepted.
+ * Errors (the plane and its record are then as before): those of rtx_render_shadows_async in its order;
+ * then no shadow pass yet, a hit pass newer than the plane, a changed light count, or a light outside
+ * `lights` whose origin or type changed (the message names the first): RTX_E_STATE; a bit of `lights`
+ * at or above the light count: RTX_E_INVALID.
+ *
+ * rtx_refresh_shadows_async makes the plane valid for the uploaded lights at the least cost.  Without a
+ * current plane (none yet, a newer hit pass, a larger pass) it is the full pass and *traced is the mask
+ * of all lights.  Otherwise the lights whose origin or type differ from the recorded ones, and the
+ * lights at or above the recorded count (appended), are traced in one launch and *traced is their
+ * mask; the bits of removed trailing lights are cleared by the same launch (one with an empty trace
+ * mask when nothing else changed).  Nothing to trace and nothing to clear: no launch, *traced = 0.
+ * `traced` may be NULL.  Errors: those of rtx_render_shadows_async. */
+int rtx_update_shadows_async(rtx_ctx* ctx, uint32_t lights);
+int rtx_refresh_shadows_async(rtx_ctx* ctx, uint32_t* traced);
+
 /* rtx_relight* is rtx_shade_aov* with DoesHit answered by the shadow plane: `params` supplies
  * lighting_mode, shadows_enabled and format (its size and stripe fields are ignored), the hit pass
  * everything else.  Per owned pixel the result is Renderer::RenderPixel from originOffset on

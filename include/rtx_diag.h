@@ -36,6 +36,10 @@ int rtx_time_shade_aov(rtx_ctx* ctx, const rtx_render_params* params, int want_r
  * shadow plane or the frame buffer then holds the result, as after the call timed. */
 int rtx_time_shadows(rtx_ctx* ctx, int iters, float* mean_ms);
 int rtx_time_relight(rtx_ctx* ctx, const rtx_render_params* params, int want_rgb, int iters, float* mean_ms);
+/* The same for the incremental shadow pass: `iters` back-to-back launches of rtx_update_shadows_async(lights)
+ * under its checks, the mean device time of one in ms.  Re-tracing is idempotent, so the plane and its
+ * record are then as after one call.  iters <= 0 or a NULL mean_ms: RTX_E_INVALID. */
+int rtx_time_shadows_update(rtx_ctx* ctx, uint32_t lights, int iters, float* mean_ms);
 /* The same for a ray query on device pointers (rtx.h): `iters` back-to-back queries of the same n rays,
  * the mean device time of one in ms.  what 0: rtx_trace_rays_device(d_rays, n, mask, d_out); 1:
  * rtx_occluded_device(d_rays, n, d_occ); 2: the yardstick, a device-to-device copy of the n rays (32 n

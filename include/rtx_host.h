@@ -45,6 +45,9 @@ int rtx_host_scene_animated(const rtx_host_scene* s);
 /* Camera controls (Camera.h): origin, fov in degrees (SetCameraFOV), pitch/yaw in
  * radians (CalculateForwardVector). */
 int rtx_host_camera_set(rtx_host_scene* s, const float origin[3], float fov_degrees, float pitch, float yaw);
+/* A light's origin (the scene's light `light`, in the order the scene added them): the edit a relighting
+ * loop makes between uploads.  RTX_E_INVALID for a NULL argument or a light the scene does not have. */
+int rtx_host_light_set_origin(rtx_host_scene* s, uint32_t light, const float origin[3]);
 
 /* Device-side Update (rtx_anim_*, rtx.h).  The meshes Update(t) turns (count returned,
  * ids written up to `capacity`), one mesh's object-space state, and the final transforms

@@ -116,6 +116,22 @@ public:
         Check(rtx_download_shadows(m_Ctx, bits.data()), "rtx_download_shadows");
         return bits;
     }
+    // The incremental shadow pass (rtx_update_shadows_async, rtx_refresh_shadows_async): after an upload that
+    // moved lights, UpdateShadows re-traces the lights named in `lights` (bit l = light l; every other light
+    // must be where the plane recorded it) and RefreshShadows re-traces whichever lights changed, or all of
+    // them when there is no plane of the last RenderAov.  Both return the plane as RenderShadows does.
+    std::vector<uint32_t> UpdateShadows(uint32_t lights) {
+        std::vector<uint32_t> bits(static_cast<size_t>(m_Width) * m_Height);
+        Check(rtx_update_shadows_async(m_Ctx, lights), "rtx_update_shadows_async");
+        Check(rtx_download_shadows(m_Ctx, bits.data()), "rtx_download_shadows");
+        return bits;
+    }
+    std::vector<uint32_t> RefreshShadows(uint32_t* traced = nullptr) {
+        std::vector<uint32_t> bits(static_cast<size_t>(m_Width) * m_Height);
+        Check(rtx_refresh_shadows_async(m_Ctx, traced), "rtx_refresh_shadows_async");
+        Check(rtx_download_shadows(m_Ctx, bits.data()), "rtx_download_shadows");
+        return bits;
+    }
     void Relight() {
         const rtx_render_params p = Params();
         Check(rtx_relight(m_Ctx, &p, m_Pixels.data(), nullptr), "rtx_relight");

@@ -5,7 +5,7 @@ JSON line per figure and one summary line (medians, ranges, the ratios) per scen
     python tools/relight_time.py SCENE[,SCENE...] WxH REPEATS ITERS
 
 Combined lighting, shadows on.  The series: the frame, the shade of a stored hit pass (rtx_shade_aov, which traces
-every shadow ray again), the shadow pass (paid once per light arrangement), the relight with pixels only and with
+every shadow ray again), the shadow pass (a moved light pays less: tools/shadow_update_time.py), the relight with pixels only and with
 both planes, and a device-to-device copy of 32 bytes per pixel: the relight reads 28 (depth 4, normal 12, material
 4, primitive 4, shadow word 4) and writes 4.  The copy reads and writes its 32, so it moves twice the relight's
 bytes; half of it is the floor.
