@@ -190,7 +190,8 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_shade_aov_async", "rtx_shade_aov", "rtx_time_shade_aov",
                "rtx_render_shadows_async", "rtx_download_shadows", "rtx_gather_shadows_async",
                "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows", "rtx_time_relight",
-               "rtx_update_shadows_async", "rtx_refresh_shadows_async", "rtx_time_shadows_update"]
+               "rtx_update_shadows_async", "rtx_refresh_shadows_async", "rtx_time_shadows_update",
+               "rtx_relight_resolve_async", "rtx_relight_resolve", "rtx_time_relight_resolve"]
 
 
 def load_hip() -> C.CDLL:
@@ -376,6 +377,14 @@ def load_hip() -> C.CDLL:
                       "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows",
                       "rtx_time_relight"):
                 getattr(lib, n).restype = C.c_int
+            if hasattr(lib, "rtx_relight_resolve"):   # (the resolved relight: later than the relight itself)
+                lib.rtx_relight_resolve_async.argtypes = [VP, C.POINTER(RenderParams), C.c_uint32, C.c_int]
+                lib.rtx_relight_resolve.argtypes = [VP, C.POINTER(RenderParams), C.c_uint32, C.POINTER(C.c_uint32),
+                                                    C.POINTER(C.c_float)]
+                lib.rtx_time_relight_resolve.argtypes = [VP, C.POINTER(RenderParams), C.c_uint32, C.c_int, C.c_int,
+                                                         C.POINTER(C.c_float)]
+                for n in ("rtx_relight_resolve_async", "rtx_relight_resolve", "rtx_time_relight_resolve"):
+                    getattr(lib, n).restype = C.c_int
         if hasattr(lib, "rtx_update_shadows_async"):   # absent only in older experiment builds (RTX_HIP_LIB)
             lib.rtx_update_shadows_async.argtypes = [VP, C.c_uint32]
             lib.rtx_refresh_shadows_async.argtypes = [VP, C.POINTER(C.c_uint32)]

@@ -5,7 +5,7 @@
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
 //              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T] [--deferred] [--relight]
-//              [--move-light L,X,Y,Z]...
+//              [--resolve K] [--move-light L,X,Y,Z]...
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -30,6 +30,10 @@
 // --relight (single frames only, and not with --deferred: the combinations --deferred refuses) makes the image from
 // one hit pass, its shadow pass and a relight (rtx_render_aov, rtx_render_shadows_async, rtx_relight): the same BMP;
 // with --aov also PREFIX_shadow.u32, one word per pixel whose bit l says light l is occluded.
+// --resolve K (K = 2, 4 or 8; only with --relight, and not with --aov) makes the W x H image anti-aliased from stored
+// passes: the hit pass and the shadow pass run at K*W x K*H and the resolved relight (rtx_relight_resolve) shades
+// every stored sample and box-filters each pixel's K x K: the same BMP as the plain run with --ss K.  --move-light
+// works as with plain --relight, the refresh running at sample size.
 // --move-light L,X,Y,Z (repeatable) sets light L's origin to (X, Y, Z) before anything is uploaded, for any run.
 // With --relight the hit pass and the full shadow pass run with the scene's ORIGINAL lights; then the moved scene is
 // uploaded, rtx_refresh_shadows_async re-traces only the moved lights, and the relight makes the image: the same
@@ -331,13 +335,15 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
                              "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
-                             "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred] [--relight] [--move-light L,X,Y,Z]...\n",
+                             "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred] [--relight] [--resolve K] "
+                             "[--move-light L,X,Y,Z]...\n",
                      argv[0]);
         return 2;
     }
     std::string scene = argv[1], out = "RayTracing_Buffer.bmp", assets, aov, rays_file;
     int W = 640, H = 480, mode = 3, frames = 1, bench = 0, inflight = 2, ss = 1;
     int ad_k = 0, ad_t = 0;   // --adaptive K,T (0: not asked for)
+    int resolve = 0;          // --resolve K (0: not asked for)
     std::vector<float> seq;
     float t = -1.f;
     bool shadows = true, device_update = false, deferred = false, relight = false;
@@ -365,6 +371,14 @@ int main(int argc, char** argv) {
             ss = i + 1 < argc ? std::atoi(argv[++i]) : 0;
             if (ss != 1 && ss != 2 && ss != 4 && ss != 8) {
                 std::fprintf(stderr, "--ss: the supersample factor must be 1, 2, 4 or 8\n");
+                return 2;
+            }
+        }
+        else if (a == "--resolve") {   // checked here: a bad factor ends the program before any device work
+            char tail = 0;
+            const int got = i + 1 < argc ? std::sscanf(argv[++i], "%d%c", &resolve, &tail) : 0;
+            if (got != 1 || (resolve != 2 && resolve != 4 && resolve != 8)) {
+                std::fprintf(stderr, "--resolve K: the factor K must be 2, 4 or 8\n");
                 return 2;
             }
         }
@@ -403,6 +417,11 @@ int main(int argc, char** argv) {
     if (relight && (deferred || bench || !seq.empty() || !rays_file.empty() || ad_k || ss > 1)) {   // before any device work
         std::fprintf(stderr, "--relight shades a single frame's hit pass and shadow pass: not with --deferred, --benchmark, "
                              "--sequence, --rays, --adaptive or --ss above 1\n");
+        return 2;
+    }
+    if (resolve && (!relight || !aov.empty())) {   // before any device work
+        std::fprintf(stderr, "--resolve K resolves a relight of K x K stored samples per pixel: only with --relight, and not "
+                             "with --aov (the planes are the sample frame's)\n");
         return 2;
     }
     if (!aov.empty() && (bench || !seq.empty())) {
@@ -518,6 +537,22 @@ int main(int argc, char** argv) {
                     std::printf("wrote %s_depth.f32 _normal.f32 _material.u32 _primitive.u32\n", aov.c_str());
                 }
             }
+        } else if (relight && resolve) {   // the sample frame's two passes, every sample relit, each pixel's resolved
+            const uint32_t k = static_cast<uint32_t>(resolve);
+            place_lights(hs, {unmoved.rbegin(), unmoved.rend()});   // (--move-light: as below, at sample size)
+            r.RenderSamplePasses(hs, k, true);
+            if (!moves.empty()) {
+                place_lights(hs, moves);
+                rtx_scene s;
+                rtx_camera cam;
+                if (rtx_host_scene_view(hs, &s, &cam) != RTX_OK) throw std::runtime_error("rtx_host_scene_view failed");
+                r.Upload(s);
+                uint32_t traced = 0;
+                if (rtx_refresh_shadows_async(r.Context(), &traced) != RTX_OK)
+                    throw std::runtime_error(std::string("rtx_refresh_shadows_async: ") + rtx_last_error(r.Context()));
+                std::printf("refreshed the shadow plane: light mask 0x%x re-traced\n", traced);
+            }
+            r.RelightResolved();
         } else if (relight) {   // one hit pass, its shadow rays stored, shaded from both; --aov writes all five planes
             // (--move-light: both passes with the scene's own lights, in reverse so that a light moved twice gets
             // its first origin back; then the moved scene, and a refresh that traces the moved lights only)

@@ -2488,6 +2488,121 @@ __global__ void __launch_bounds__(kRelightThreads) rtx_relight_kernel(const DevS
     }
 }
 
+// The resolved relight (rtx_relight_resolve*, rtx.h): the stored hit pass is the k*W x k*H sample frame of a
+// W x H frame (K = 1 << N, N = 1..3), each sample is shaded exactly as rtx_relight_kernel shades a pixel (the
+// same macros over the sample frame's RelightArgs, up to and including RTX_MAX_TO_ONE), and the k x k samples
+// of an output pixel are resolved with rtx_set_supersample's box filter: per channel the adjacent-pair tree
+// over sx, then over sy, times the exact 1 / (k * k).
+// A wave is 64 consecutive samples of one sample row, as in rtx_relight_kernel, so every plane load stays a
+// full-width row piece; 64 is a multiple of K, so the wave holds whole pixels and a pixel's K lanes are inside
+// the row together.  It walks the K sample rows of ONE output row (A.rows, A.stripe_* and the row rule count
+// OUTPUT rows here): each iteration is the relight body for one sample row, then the x tree over lane bits
+// 0..N-1 (ss_add_xor<1>, <2>, <4>, the DPP exchanges of the supersampled frame; every lane of the wave
+// executes them: a lane outside the row loads and stores nothing but never returns early), then the y tree in
+// registers in pair order, (r0 + r1), (r2 + r3), then pairs of those: row sy is added to the pending sum of each
+// level whose bit of sy is set, and parked at the first level whose bit is clear (sy is wave-uniform, so these
+// are scalar branches and the pending sums are 3 N registers).  The lane with lane % K == 0 stores the pixel.
+// No LDS, no scratch, no stack.
+template <int N>
+__global__ void __launch_bounds__(kRelightThreads, N < 3 ? RTX_RESOLVE_WAVES : RTX_MIN_WAVES_PER_EU)
+rtx_relight_resolve_kernel(const DevScene S, const RelightArgs A) {
+    constexpr uint32_t K = 1u << N;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t widx = uni(blockIdx.x * (kRelightThreads / 64u) + (threadIdx.x >> 6));
+    const uint32_t per_view = A.segs * A.rows;
+    if (widx >= per_view * A.n_views) return;
+    const uint32_t view = widx / per_view;
+    const uint32_t rem = widx - view * per_view;
+    const uint32_t j = rem / A.segs, seg = rem - j * A.segs;
+    const uint32_t out_w = A.width >> N, out_h = A.height >> N;
+    unsigned long long orow = j;
+    if (A.stripe_rows) {
+        // view v owns the stripes s with s % step == (first - v) mod step (rtx.h), in output rows
+        const uint32_t first = (A.stripe_first + A.stripe_step - view % A.stripe_step) % A.stripe_step;
+        const uint32_t k = j / A.stripe_rows, sub = j % A.stripe_rows;
+        orow = (first + static_cast<unsigned long long>(k) * A.stripe_step) * A.stripe_rows + sub;
+    }
+    if (orow >= out_h) return;   // (wave-uniform)
+    const ViewCam& V = A.cam[view];
+    const int px = static_cast<int>(seg * 64u + lane);
+    const bool valid = px < static_cast<int>(A.width);
+    float p0r = 0.f, p0g = 0.f, p0b = 0.f, p1r = 0.f, p1g = 0.f, p1b = 0.f, p2r = 0.f, p2g = 0.f, p2b = 0.f;
+    float fr = 0.f, fg = 0.f, fb = 0.f;
+#pragma unroll 1
+    for (uint32_t sy = 0; sy < K; ++sy) {
+        const int py = static_cast<int>(static_cast<uint32_t>(orow) * K + sy);
+        RTX_PRIMARY_DIR(A, V);
+        (void)dm;
+
+        // ---- closestHit from the planes, as PHASE 8 reads it
+        const size_t o = static_cast<size_t>(view) * A.width * A.height + static_cast<size_t>(py) * A.width +
+                         static_cast<size_t>(px);
+        bool did = false;
+        float t = FLT_MAX, nx = 0.f, ny = 0.f, nz = 0.f;
+        float hx = 0.f, hy = 0.f, hz = 0.f;
+        uint32_t mat = 0, bits = 0;
+        if (valid) {
+            did = A.primitive[o] != 0u;
+            t = A.depth[o];
+            nx = A.normal[3 * o]; ny = A.normal[3 * o + 1]; nz = A.normal[3 * o + 2];
+            const uint32_t m = A.material[o], top = S.n_materials - 1u;
+            mat = m < top ? m : top;
+            if (A.shadows) bits = A.shadow[o];
+        }
+        if (did) { hx = V.origin[0] + dx * t; hy = V.origin[1] + dy * t; hz = V.origin[2] + dz * t; }
+
+        // ---- the reference's light loop (Renderer.cpp:128-176), DoesHit answered by the shadow plane
+        float shadowFactor = 1.f;
+        fr = 0.f; fg = 0.f; fb = 0.f;
+        Counts cnt;   // (never counted)
+        if (ballot(did)) {
+            const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
+            const float vx = -dx, vy = -dy, vz = -dz;
+            for (uint32_t li = 0; li < S.n_lights; ++li) {
+                float4 L0, L1;
+                ldcb32(S.lights, opaque(li * 32u), L0, L1);
+                const int ltype = __float_as_int(L0.w);
+                RTX_LIGHT_DIR();
+                (void)mag;   // (the shadow ray's tmax: no ray here)
+                if (!did) continue;
+                if (A.shadows && li < 32u && ((bits >> li) & 1u)) {
+                    shadowFactor *= 0.95f;
+                    continue;
+                }
+                RTX_LIGHT_TERM(A.mode, 0, false)
+            }
+            if (did) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
+        }
+        RTX_MAX_TO_ONE()
+        // ---- the x tree: this sample row's K samples of each pixel, in every lane of the pixel
+        ss_add_xor3<1>(fr, fg, fb);
+        if constexpr (N >= 2) ss_add_xor3<2>(fr, fg, fb);
+        if constexpr (N >= 3) ss_add_xor3<4>(fr, fg, fb);
+        // ---- the y tree: rows in adjacent pairs, then pairs of pairs
+        if (!(sy & 1u)) { p0r = fr; p0g = fg; p0b = fb; continue; }
+        fr = p0r + fr; fg = p0g + fg; fb = p0b + fb;
+        if constexpr (N >= 2) {
+            if (!(sy & 2u)) { p1r = fr; p1g = fg; p1b = fb; continue; }
+            fr = p1r + fr; fg = p1g + fg; fb = p1b + fb;
+        }
+        if constexpr (N >= 3) {
+            if (!(sy & 4u)) { p2r = fr; p2g = fg; p2b = fb; continue; }
+            fr = p2r + fr; fg = p2g + fg; fb = p2b + fb;
+        }
+    }
+    (void)p1r; (void)p1g; (void)p1b; (void)p2r; (void)p2g; (void)p2b;   // (levels a smaller K does not have)
+    const float w = __uint_as_float((127u - 2u * N) << 23);   // 2^(-2 log2 k)
+    fr *= w; fg *= w; fb *= w;
+    if (valid && (lane & (K - 1u)) == 0u) {
+        const size_t o = (static_cast<size_t>(view) * out_h + static_cast<size_t>(orow)) * out_w +
+                         (static_cast<uint32_t>(px) >> N);
+        A.out_px[o] = RTX_PACK_PX(A);
+        if (A.out_rgb) {
+            A.out_rgb[3 * o] = fr; A.out_rgb[3 * o + 1] = fg; A.out_rgb[3 * o + 2] = fb;
+        }
+    }
+}
+
 #undef RTX_PRIMARY_DIR
 #undef RTX_LIGHT_DIR
 #undef RTX_LIGHT_TERM
@@ -2594,6 +2709,15 @@ void launch_shadows(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s,
 
 void launch_relight(dim3 grid, hipStream_t s, const DevScene& d, const RelightArgs& A) {
     hipLaunchKernelGGL(rtx_relight_kernel, grid, dim3(kRelightThreads), 0, s, d, A);
+}
+
+void launch_relight_resolve(uint32_t ss_log2, dim3 grid, hipStream_t s, const DevScene& d, const RelightArgs& A) {
+    switch (ss_log2) {
+    case 1: hipLaunchKernelGGL(rtx_relight_resolve_kernel<1>, grid, dim3(kRelightThreads), 0, s, d, A); break;
+    case 2: hipLaunchKernelGGL(rtx_relight_resolve_kernel<2>, grid, dim3(kRelightThreads), 0, s, d, A); break;
+    case 3: hipLaunchKernelGGL(rtx_relight_resolve_kernel<3>, grid, dim3(kRelightThreads), 0, s, d, A); break;
+    default: no_instantiation("this resolve factor");
+    }
 }
 
 template <bool ANY>

@@ -332,6 +332,10 @@ struct AdaptiveArgs {
 // owned stripe (FrameArgs' rule); a row at or past `height` is skipped.  The planes are the hit pass's (view v
 // at v * width * height elements) plus the shadow plane (bit l of a pixel = light l occluded), which is read
 // only with shadows on and may be null otherwise.
+// The resolved relight (rtx_relight_resolve_kernel<N>, rtx_relight_resolve*) takes the same record for the
+// k*W x k*H sample frame, k = 1 << N: aspect, inv_*, width, height, segs and the planes are the sample
+// frame's, while `rows`, `stripe_rows` and the row rule count OUTPUT rows (a wave walks the k sample rows of
+// one output row), and out_px / out_rgb hold (width / k) x (height / k) pixels per view.
 constexpr int kRelightThreads = 256;
 constexpr int kMaxShadowLights = 32;   // lights with a bit in the shadow plane's word (PHASE 9)
 struct RelightArgs {

@@ -30,6 +30,10 @@ void launch_shadows(int variant, bool deep, bool hstk, dim3 grid, hipStream_t s,
                     const rtxd::FrameArgs& F);
 // Relighting (rtx_relight_kernel): grid.x workgroups of kRelightThreads, one wave per 64-pixel row piece.
 void launch_relight(dim3 grid, hipStream_t s, const rtxd::DevScene& d, const rtxd::RelightArgs& A);
+// The resolved relight (rtx_relight_resolve_kernel<ss_log2>, ss_log2 = 1..3): the same workgroups, one wave per
+// 64-sample piece of an OUTPUT row's sample rows; A describes the sample frame, its rows and stripes output rows.
+void launch_relight_resolve(uint32_t ss_log2, dim3 grid, hipStream_t s, const rtxd::DevScene& d,
+                            const rtxd::RelightArgs& A);
 // A ray query (rtx_query_kernel): closest hit or occlusion (`any`) with the default stack, the deep
 // one, or the deep one in HBM; grid.x = the launch's waves, ceil(Q.n / 64) / kWavesPerBlock.
 void launch_query(bool any, bool deep, bool hstk, dim3 grid, hipStream_t s, const rtxd::DevScene& d,

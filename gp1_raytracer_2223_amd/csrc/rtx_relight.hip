@@ -166,10 +166,9 @@ int queue_shadow_copy(rtx_ctx* c, uint32_t* out) {
 
 // ---- the relight --------------------------------------------------------------------------------
 
-// Checks, the frame buffer and the launch record of a relight of the last hit pass: deferred shading's
-// (rtx_deferred.hip), plus the shadow plane's validity with shadows on.
-int relight_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, RelightArgs& A, dim3& grid,
-                    rtx_render_params& shape) {
+// A relight's checks of the last hit pass: deferred shading's (rtx_deferred.hip), plus the shadow plane's
+// validity with shadows on.  Nothing is changed.
+int relight_checks(rtx_ctx* c, const rtx_render_params* p) {
     if (!c || !p) return RTX_E_INVALID;
     if (p->lighting_mode < 0 || p->lighting_mode >= RTX_MODE_COUNT) return fail(c, RTX_E_INVALID, "bad lighting mode");
     if (p->format.rshift > 24 || p->format.gshift > 24 || p->format.bshift > 24)
@@ -180,13 +179,22 @@ int relight_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, Relig
                                         " materials, the hit pass was traced with " +
                                         std::to_string(c->aov_last_materials));
     if (c->dev.n_materials == 0) return fail(c, RTX_E_STATE, "the scene has no material");
-    const bool shadows = p->shadows_enabled != 0;
-    if (shadows) {
+    if (p->shadows_enabled != 0) {
         if (const int rc = shadows_current(c); rc != RTX_OK) return rc;
         if (c->light_keys != c->shadow_lights)
             return fail(c, RTX_E_STATE, "the uploaded lights' count, origins or types are not those the shadow pass was "
                                         "traced for: render the shadow pass again");
     }
+    return RTX_OK;
+}
+
+// The frame buffer and the launch record of a relight of the last hit pass, after relight_checks.  With
+// ss > 0 (rtx_relight_resolve*, after resolve_checks) the pass is the sample frame of the frame `shape`, whose
+// sides and stripes are the pass's divided by k = 1 << ss: A describes the sample frame, its rows and stripes
+// count output rows (one wave walks an output row's k sample rows), and the frame buffer holds the output.
+int relight_build(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, uint32_t ss, RelightArgs& A, dim3& grid,
+                  rtx_render_params& shape) {
+    const bool shadows = p->shadows_enabled != 0;
     HIP_TRY(c, hipSetDevice(c->device));
     // behind a pending split chain, which writes the frame buffer this call sizes and writes
     if (const int rc = join_split(c); rc != RTX_OK) return rc;
@@ -195,7 +203,7 @@ int relight_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, Relig
     shape.shadows_enabled = p->shadows_enabled;
     shape.format = p->format;
     const int n_views = c->aov_last_views;
-    const size_t npx = static_cast<size_t>(shape.width) * shape.height * static_cast<size_t>(n_views);
+    const size_t npx = static_cast<size_t>(shape.width >> ss) * (shape.height >> ss) * static_cast<size_t>(n_views);
     if (const int rc = frame_buffers(c, npx, want_rgb); rc != RTX_OK) return rc;
     // the frame's own launch record: its cameras, aspect and reciprocals are the relight's, value for value
     FrameArgs F;
@@ -222,15 +230,47 @@ int relight_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, Relig
     A.shadow = shadows ? c->d_shadow.get() : nullptr;
     A.out_px = c->d_px;
     A.out_rgb = want_rgb ? c->d_rgb.get() : nullptr;
+    // (the resolve's divisions are exact: the sides by resolve_checks, a striped pass's stripe and owned rows as
+    // multiples of 16 k.  An unstriped pass's stripe_rows means nothing and may be anything: the output's record is 0.)
+    A.rows >>= ss; A.stripe_rows >>= ss;
+    shape.width >>= ss; shape.height >>= ss;
+    if (ss) shape.stripe_rows = F.groups_per_stripe ? shape.stripe_rows >> ss : 0u;
     const uint32_t waves = A.segs * A.rows * A.n_views, per = kRelightThreads / 64u;
     grid = dim3((waves + per - 1) / per, 1, 1);
     return RTX_OK;
 }
 
-int relight_launch(rtx_ctx* c, const RelightArgs& A, dim3 grid) {
+int relight_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, RelightArgs& A, dim3& grid,
+                    rtx_render_params& shape) {
+    if (const int rc = relight_checks(c, p); rc != RTX_OK) return rc;
+    return relight_build(c, p, want_rgb, 0u, A, grid, shape);
+}
+
+// ss = 0: the relight; else the resolved relight of factor 1 << ss.
+int relight_launch(rtx_ctx* c, const RelightArgs& A, dim3 grid, uint32_t ss = 0u) {
     if (grid.x == 0) return RTX_OK;
-    launch_relight(grid, c->stream, c->dev, A);
+    if (ss) launch_relight_resolve(ss, grid, c->stream, c->dev, A);
+    else launch_relight(grid, c->stream, c->dev, A);
     HIP_TRY(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// rtx_relight_resolve*'s checks, in the contract's order: the factor, the relight's own, then a pass that is a
+// whole number of k x k blocks whose output stripes are a legal frame shape.  `ss` = log2 k.
+int resolve_checks(rtx_ctx* c, const rtx_render_params* p, uint32_t k, uint32_t& ss) {
+    if (!c || !p) return RTX_E_INVALID;
+    if (k != 2 && k != 4 && k != 8) return fail(c, RTX_E_INVALID, "the resolve factor must be 2, 4 or 8");
+    ss = k == 8 ? 3u : (k == 4 ? 2u : 1u);
+    if (const int rc = relight_checks(c, p); rc != RTX_OK) return rc;
+    const rtx_render_params& s = c->aov_last;
+    if (s.width % k != 0 || s.height % k != 0)
+        return fail(c, RTX_E_INVALID, "the hit pass of " + std::to_string(s.width) + "x" + std::to_string(s.height) +
+                                          " is no sample frame of factor " + std::to_string(k) +
+                                          ": both sides must be multiples of it");
+    if (s.stripe_rows != 0 && s.stripe_step > 1 && s.stripe_rows % (16u * k) != 0)
+        return fail(c, RTX_E_UNSUPPORTED, "the pass's stripes of " + std::to_string(s.stripe_rows) +
+                                              " sample rows are no multiple of 16 output rows at factor " +
+                                              std::to_string(k));
     return RTX_OK;
 }
 
@@ -354,6 +394,51 @@ extern "C" int rtx_relight(rtx_ctx* c, const rtx_render_params* p, uint32_t* out
     const int rc = rtx_relight_async(c, p, out_rgb != nullptr);
     if (rc != RTX_OK) return rc;
     return rtx_download(c, out_px, out_rgb);
+}
+
+extern "C" int rtx_relight_resolve_async(rtx_ctx* c, const rtx_render_params* p, uint32_t k, int want_rgb) {
+    uint32_t ss = 0;
+    if (const int rc = resolve_checks(c, p, k, ss); rc != RTX_OK) return rc;
+    RelightArgs A;
+    dim3 grid;
+    rtx_render_params shape;
+    int rc = relight_build(c, p, want_rgb != 0, ss, A, grid, shape);
+    if (rc != RTX_OK) return rc;
+    rc = relight_launch(c, A, grid, ss);
+    if (rc != RTX_OK) return rc;
+    remember(c, &shape, c->aov_last_views, want_rgb != 0);
+    return RTX_OK;
+}
+
+extern "C" int rtx_relight_resolve(rtx_ctx* c, const rtx_render_params* p, uint32_t k, uint32_t* out_px, float* out_rgb) {
+    if (!out_px) return RTX_E_INVALID;
+    const int rc = rtx_relight_resolve_async(c, p, k, out_rgb != nullptr);
+    if (rc != RTX_OK) return rc;
+    return rtx_download(c, out_px, out_rgb);
+}
+
+extern "C" int rtx_time_relight_resolve(rtx_ctx* c, const rtx_render_params* p, uint32_t k, int want_rgb, int iters,
+                                        float* mean_ms) {
+    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
+    uint32_t ss = 0;
+    if (const int rc = resolve_checks(c, p, k, ss); rc != RTX_OK) return rc;
+    RelightArgs A;
+    dim3 grid;
+    rtx_render_params shape;
+    int rc = relight_build(c, p, want_rgb != 0, ss, A, grid, shape);
+    if (rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i) {
+        rc = relight_launch(c, A, grid, ss);
+        if (rc != RTX_OK) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
+    remember(c, &shape, c->aov_last_views, want_rgb != 0);
+    return RTX_OK;
 }
 
 extern "C" int rtx_time_relight(rtx_ctx* c, const rtx_render_params* p, int want_rgb, int iters, float* mean_ms) {

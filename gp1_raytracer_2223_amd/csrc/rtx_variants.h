@@ -33,6 +33,11 @@
 #ifndef RTX_SPEC_WAVES_PARTIAL
 #define RTX_SPEC_WAVES_PARTIAL 7
 #endif
+// the resolved relight's 2 x 2 and 4 x 4 kernels (rtx_relight_resolve_kernel<1>, <2>): 70 and 72 VGPRs.  The
+// 8 x 8 one keeps three pending row sums per channel and spills at 7, so it takes RTX_MIN_WAVES_PER_EU.
+#ifndef RTX_RESOLVE_WAVES
+#define RTX_RESOLVE_WAVES 7
+#endif
 
 // ---- formulation choices (product values; the other value is the measured alternative) ----
 // shadow-ray walks with cull records visit the child most lanes enter first (1) or left first (0)

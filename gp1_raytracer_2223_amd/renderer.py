@@ -353,6 +353,34 @@ class DeviceContext:
         abi.check(rc, "rtx_relight", self.h)
         return px, rgb
 
+    def relight_resolve_async(self, params: abi.RenderParams, k: int, want_rgb: bool = False) -> None:
+        """Queue the resolved relight (rtx_relight_resolve_async): the last hit pass of k*W x k*H is read as the
+        sample frame of a W x H frame, every sample is relit and each pixel's k x k samples are box-filtered as
+        rtx_set_supersample(k) defines; the frame buffer then holds the W x H frame."""
+        abi.check(self.lib.rtx_relight_resolve_async(self.h, C.byref(params), int(k), int(want_rgb)),
+                  "rtx_relight_resolve_async", self.h)
+
+    def relight_resolve(self, params: abi.RenderParams, k: int, want_rgb: bool = True):
+        """The resolved relight (rtx_relight_resolve), blocking: (pixels, rgb) of W*H*views pixels."""
+        if self._aov_shape is None or k not in (2, 4, 8):   # no array can be sized: the library says why
+            self.relight_resolve_async(params, k, want_rgb)
+            # (accepted: a pass queued behind this object's back; the frame is in the frame buffer, unsized here)
+            raise RuntimeError("relight_resolve: the last hit pass was not queued through this object, its size is "
+                               "unknown")
+        n = (self._aov_shape[0] // k) * (self._aov_shape[1] // k) * self._aov_shape[2]
+        px = np.zeros(n, np.uint32)
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.lib.rtx_relight_resolve(self.h, C.byref(params), int(k), px.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_relight_resolve", self.h)
+        return px, rgb
+
+    def time_relight_resolve(self, params: abi.RenderParams, k: int, want_rgb: bool, iters: int) -> float:
+        ms = C.c_float()
+        abi.check(self.lib.rtx_time_relight_resolve(self.h, C.byref(params), int(k), int(want_rgb), int(iters),
+                                                    C.byref(ms)), "rtx_time_relight_resolve", self.h)
+        return ms.value
+
     def time_shadows(self, iters: int) -> float:
         ms = C.c_float()
         abi.check(self.lib.rtx_time_shadows(self.h, int(iters), C.byref(ms)), "rtx_time_shadows", self.h)
@@ -671,6 +699,42 @@ class Renderer:
                                       self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
                                       rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
         abi.check(rc, "rtx_relight", self.ctx.h)
+        self.rgb = rgb
+        return self.buffer
+
+    def RenderSamplePasses(self, scene: HostScene, k: int, upload: bool = True) -> None:
+        """The passes an anti-aliased relighting loop starts from (not in the reference's Renderer): the hit pass
+        of the k*m_Width x k*m_Height sample frame of the frame Render would render (all four planes; stripes
+        k times as tall), then its shadow pass.  Both stay on the device for RelightResolved.  k in 2, 4, 8, on
+        a renderer whose own supersample factor is 1."""
+        if k not in (2, 4, 8):
+            raise ValueError(f"RenderSamplePasses: k must be 2, 4 or 8, not {k}")
+        _, cam = self._view(scene, upload)
+        sr, first, step = self.stripe if self.stripe else (0, 0, 1)
+        sp = abi.make_params(k * self.m_Width, k * self.m_Height, self.m_CurrentLightingMode, self.m_ShadowsEnabled,
+                             self.format, k * sr, first, step)
+        self.ctx.render_aov_async(cam, sp, AOV_ALL)
+        self.ctx.render_shadows_async()
+        self._sample_k = int(k)
+
+    def RelightResolved(self, want_rgb: bool = False) -> np.ndarray:
+        """The frame a renderer made with supersample=k would render, from the last RenderSamplePasses without
+        casting a ray (rtx_relight_resolve): every stored sample relit with the renderer's CURRENT lighting mode,
+        shadows and pixel format and the scene uploaded last, each pixel's k x k samples box-filtered.  After an
+        upload that moved a light, RefreshShadows' device call (ctx.refresh_shadows_async) comes first.
+        Explicit, like Relight.  Blocking; fills self.buffer."""
+        k = getattr(self, "_sample_k", 0)
+        if not k or self.ctx._aov_shape != (k * self.m_Width, k * self.m_Height, 1):
+            if self.ctx._aov_shape is None:
+                self.ctx.relight_resolve_async(self.params(), k or 2, want_rgb)   # no pass yet: the library says why
+            raise RuntimeError(f"RelightResolved: the context's last hit pass is {self.ctx._aov_shape}, not this "
+                               "renderer's sample pass (RenderSamplePasses)")
+        n = self.m_Width * self.m_Height
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        rc = self.ctx.lib.rtx_relight_resolve(self.ctx.h, C.byref(self.params()), k,
+                                              self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
+        abi.check(rc, "rtx_relight_resolve", self.ctx.h)
         self.rgb = rgb
         return self.buffer
 

@@ -459,6 +459,43 @@ int rtx_relight_async(rtx_ctx* ctx, const rtx_render_params* params, int want_rg
  * NULL). */
 int rtx_relight(rtx_ctx* ctx, const rtx_render_params* params, uint32_t* out_pixels, float* out_rgb);
 
+/* ---- resolved relighting: anti-aliased frames from a stored sample pass -------------------------
+ * rtx_set_supersample defines sample (X, Y) of a width x height frame as pixel (X, Y) of the reference's
+ * k*width x k*height frame.  So a hit pass of Ws x Hs = k*W x k*H pixels, taken on a context whose own
+ * supersample factor is 1, IS the sample pass of the W x H frame; the shadow pass and its incremental
+ * updates run on it unchanged.  rtx_relight_resolve* reads the context's last hit pass that way: every
+ * sample is shaded exactly as rtx_relight* shades a pixel of the Ws x Hs pass (up to and including
+ * MaxToOne), and pixel (x, y) of view v is the box filter of rtx_set_supersample over the samples
+ * (k x + sx, k y + sy): per channel the fp32 sum as an adjacent-pair tree over sx, then over sy, times
+ * 1/(k*k); then the quantisation with params->format.  `params` supplies lighting_mode, shadows_enabled
+ * and format (its size and stripe fields are ignored); the pass supplies cameras, views, size and stripes.
+ *
+ * Guarantee: while the geometry, the material indices, the cameras and the lights' count, origins and
+ * types are those of the passes, the frame buffer holds word for word, in both planes, what
+ * rtx_set_supersample(ctx, k) followed by rtx_render_views_async leaves there for the pass's cameras at
+ * W x H with the stripes {stripe_rows / k, stripe_first, stripe_step} and these mode, shadows and format;
+ * so it is the resolved reference frame bit for bit wherever the reference calls no powf.  Light colours
+ * and intensities and material VALUES are read from the scene uploaded at the time of the call, as by
+ * rtx_relight*: a colour, intensity, material, mode or shadow-toggle change of an anti-aliased frame is
+ * one pass over the planes, and a moved light its own shadow rays (rtx_refresh_shadows_async) on top.
+ *
+ * Afterwards the last-frame record is W x H, the pass's views, and the stripes {stripe_rows / k,
+ * stripe_first, stripe_step} (stripe_rows 0 for an unstriped pass, whose own value means nothing):
+ * rtx_download, rtx_gather_async and rtx_device_buffers work unchanged, and
+ * the frame buffer holds W*H*views pixels.  An output row is owned exactly when its k sample rows are.
+ * The call is no frame for the schedule or any policy, casts no ray, only reads the hit planes, the
+ * shadow plane and their records, and queues on the context stream, behind a pending split chain.
+ * Errors, in this order (the context keeps working after each): NULL ctx or params, k not 2, 4 or 8:
+ * RTX_E_INVALID; everything rtx_relight_async checks, in its order and with its codes (among them a
+ * supersample factor other than 1 on the context: RTX_E_UNSUPPORTED, the mode carries its own); Ws or
+ * Hs not divisible by k: RTX_E_INVALID; a striped pass (stripe_step > 1) whose stripe_rows is no
+ * multiple of 16*k, so that the output stripes would be no legal frame shape: RTX_E_UNSUPPORTED. */
+int rtx_relight_resolve_async(rtx_ctx* ctx, const rtx_render_params* params, uint32_t k, int want_rgb);
+/* Blocking: the call above, then rtx_download into the caller's full-frame W x H buffers (out_rgb may be
+ * NULL; out_pixels == NULL: RTX_E_INVALID). */
+int rtx_relight_resolve(rtx_ctx* ctx, const rtx_render_params* params, uint32_t k, uint32_t* out_pixels,
+                        float* out_rgb);
+
 /* ---- ray queries: closest hit and occlusion for caller-supplied rays ---------------
  * The traversal behind a frame's rays, for rays the caller makes: a line-of-sight test, a pick ray,
  * visibility from surface points, a bounce, a custom camera.

@@ -36,6 +36,11 @@ int rtx_time_shade_aov(rtx_ctx* ctx, const rtx_render_params* params, int want_r
  * shadow plane or the frame buffer then holds the result, as after the call timed. */
 int rtx_time_shadows(rtx_ctx* ctx, int iters, float* mean_ms);
 int rtx_time_relight(rtx_ctx* ctx, const rtx_render_params* params, int want_rgb, int iters, float* mean_ms);
+/* The same for the resolved relight (rtx_relight_resolve_async(params, k, want_rgb), rtx.h): `iters`
+ * back-to-back launches under its checks, the mean device time of one in ms.  The frame buffer and the
+ * last-frame record are then as after one call.  iters <= 0 or a NULL mean_ms: RTX_E_INVALID. */
+int rtx_time_relight_resolve(rtx_ctx* ctx, const rtx_render_params* params, uint32_t k, int want_rgb, int iters,
+                             float* mean_ms);
 /* The same for the incremental shadow pass: `iters` back-to-back launches of rtx_update_shadows_async(lights)
  * under its checks, the mean device time of one in ms.  Re-tracing is idempotent, so the plane and its
  * record are then as after one call.  iters <= 0 or a NULL mean_ms: RTX_E_INVALID. */

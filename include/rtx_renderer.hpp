@@ -38,6 +38,7 @@ public:
 
     void Render(const rtx_camera& cam) {
         const rtx_render_params p = Params();
+        m_Cam = cam; m_HaveCam = true;
         Check(rtx_render(m_Ctx, &cam, &p, m_Pixels.data(), nullptr), "rtx_render");
     }
 
@@ -54,6 +55,7 @@ public:
     // (0..255) in a channel, the plain pixel elsewhere.  AdaptiveRefined: how many pixels that was.
     void RenderAdaptive(const rtx_camera& cam, uint32_t k, uint32_t threshold) {
         const rtx_render_params p = Params();
+        m_Cam = cam; m_HaveCam = true;
         Check(rtx_render_adaptive(m_Ctx, &cam, &p, k, threshold, m_Pixels.data(), nullptr), "rtx_render_adaptive");
     }
     void RenderAdaptive(rtx_host_scene* scene, uint32_t k, uint32_t threshold, bool upload = true) {
@@ -78,6 +80,7 @@ public:
     };
     AovFrame RenderAov(const rtx_camera& cam, uint32_t mask = RTX_AOV_ALL) {
         const rtx_render_params p = Params();
+        m_Cam = cam; m_HaveCam = true;
         const size_t n = static_cast<size_t>(m_Width) * m_Height;
         AovFrame f;
         if (mask & RTX_AOV_DEPTH) f.depth.resize(n);
@@ -88,6 +91,7 @@ public:
                                     f.material.empty() ? nullptr : f.material.data(),
                                     f.primitive.empty() ? nullptr : f.primitive.data()};
         Check(rtx_render_aov(m_Ctx, &cam, &p, mask, &out), "rtx_render_aov");
+        m_SampleK = 0;   // (the context's last hit pass is this width x height one, no sample pass)
         return f;
     }
     AovFrame RenderAov(rtx_host_scene* scene, uint32_t mask = RTX_AOV_ALL, bool upload = true) {
@@ -102,6 +106,7 @@ public:
     // pixel format, without tracing a primary ray.  Explicit: nothing is cached or reused on its own,
     // and the scene is whatever was uploaded last.  Fills Pixels() (the renderer's size is the pass's).
     void ShadeAov() {
+        NoSamplePass("ShadeAov");
         const rtx_render_params p = Params();
         Check(rtx_shade_aov(m_Ctx, &p, m_Pixels.data(), nullptr), "rtx_shade_aov");
     }
@@ -111,7 +116,7 @@ public:
     // shadows and pixel format without casting a ray, reading light colours, intensities and material values
     // from the scene uploaded last; it fills Pixels().  Explicit, like ShadeAov.
     std::vector<uint32_t> RenderShadows() {
-        std::vector<uint32_t> bits(static_cast<size_t>(m_Width) * m_Height);
+        std::vector<uint32_t> bits(PassWords());
         Check(rtx_render_shadows_async(m_Ctx), "rtx_render_shadows_async");
         Check(rtx_download_shadows(m_Ctx, bits.data()), "rtx_download_shadows");
         return bits;
@@ -120,21 +125,60 @@ public:
     // moved lights, UpdateShadows re-traces the lights named in `lights` (bit l = light l; every other light
     // must be where the plane recorded it) and RefreshShadows re-traces whichever lights changed, or all of
     // them when there is no plane of the last RenderAov.  Both return the plane as RenderShadows does.
+    // After RenderSamplePasses (below) all three work on the sample pass: the plane they return is the
+    // k*width x k*height one.
     std::vector<uint32_t> UpdateShadows(uint32_t lights) {
-        std::vector<uint32_t> bits(static_cast<size_t>(m_Width) * m_Height);
+        std::vector<uint32_t> bits(PassWords());
         Check(rtx_update_shadows_async(m_Ctx, lights), "rtx_update_shadows_async");
         Check(rtx_download_shadows(m_Ctx, bits.data()), "rtx_download_shadows");
         return bits;
     }
     std::vector<uint32_t> RefreshShadows(uint32_t* traced = nullptr) {
-        std::vector<uint32_t> bits(static_cast<size_t>(m_Width) * m_Height);
+        std::vector<uint32_t> bits(PassWords());
         Check(rtx_refresh_shadows_async(m_Ctx, traced), "rtx_refresh_shadows_async");
         Check(rtx_download_shadows(m_Ctx, bits.data()), "rtx_download_shadows");
         return bits;
     }
     void Relight() {
+        NoSamplePass("Relight");
         const rtx_render_params p = Params();
         Check(rtx_relight(m_Ctx, &p, m_Pixels.data(), nullptr), "rtx_relight");
+    }
+    // Resolved relighting (rtx_relight_resolve; not in the reference): the anti-aliased form of the loop above.
+    // RenderSamplePasses stores the hit pass (all four planes) of the k*width x k*height sample frame of the
+    // frame Render would render, k = 2, 4 or 8, and its shadow pass; RelightResolved then fills Pixels() with the
+    // frame SetSupersample(k) + Render gives, from those passes alone: every sample relit with the renderer's
+    // CURRENT lighting mode, shadows and pixel format and the scene uploaded last, each pixel's k x k samples
+    // box-filtered.  After an upload that moved a light, RefreshShadows or UpdateShadows first: while the
+    // sample passes are the context's last, they run and return the plane at sample size, and ShadeAov and Relight,
+    // which would fill Pixels() with k*width x k*height pixels, throw; RenderAov ends that state.
+    // Without a camera the passes take the one of the last Render, RenderAdaptive or RenderAov.
+    void RenderSamplePasses(const rtx_camera& cam, uint32_t k) {
+        if (k != 2 && k != 4 && k != 8) throw std::runtime_error("RenderSamplePasses: k must be 2, 4 or 8");
+        rtx_render_params p = Params();
+        p.width *= k; p.height *= k;
+        m_Cam = cam; m_HaveCam = true;
+        // (a refused hit pass throws here and leaves the context's last pass, and m_SampleK, as they were)
+        Check(rtx_render_aov_async(m_Ctx, &cam, 1, &p, RTX_AOV_ALL), "rtx_render_aov_async");
+        m_SampleK = k;   // the context's last hit pass from here on, whatever the shadow pass answers
+        Check(rtx_render_shadows_async(m_Ctx), "rtx_render_shadows_async");
+    }
+    void RenderSamplePasses(uint32_t k) {
+        if (!m_HaveCam) throw std::runtime_error("RenderSamplePasses: no camera yet (Render or RenderAov first, or pass one)");
+        const rtx_camera cam = m_Cam;
+        RenderSamplePasses(cam, k);
+    }
+    void RenderSamplePasses(rtx_host_scene* scene, uint32_t k, bool upload = true) {
+        rtx_scene s;
+        rtx_camera cam;
+        Check(rtx_host_scene_view(scene, &s, &cam), "rtx_host_scene_view");
+        if (upload) Upload(s);
+        RenderSamplePasses(cam, k);
+    }
+    void RelightResolved() {
+        if (!m_SampleK) throw std::runtime_error("RelightResolved: no sample passes yet (RenderSamplePasses)");
+        const rtx_render_params p = Params();
+        Check(rtx_relight_resolve(m_Ctx, &p, m_SampleK, m_Pixels.data(), nullptr), "rtx_relight_resolve");
     }
 
     // Ray queries against the uploaded scene (rtx_trace_rays / rtx_occluded; not in the reference's
@@ -244,6 +288,18 @@ public:
         return p;
     }
 private:
+    // Words of a plane of the context's last hit pass as this renderer queued it: the sample pass's after
+    // RenderSamplePasses, else width x height.
+    size_t PassWords() const {
+        const size_t k = m_SampleK ? m_SampleK : 1;
+        return k * static_cast<size_t>(m_Width) * k * static_cast<size_t>(m_Height);
+    }
+    void NoSamplePass(const char* what) const {
+        if (m_SampleK)
+            throw std::runtime_error(std::string(what) + ": the last hit pass is RenderSamplePasses' " +
+                                     std::to_string(m_SampleK) + " x " + std::to_string(m_SampleK) +
+                                     " sample pass, larger than Pixels(); RelightResolved shades it, RenderAov replaces it");
+    }
     void Check(int rc, const char* what) const {
         if (rc != RTX_OK) throw std::runtime_error(std::string(what) + ": " + rtx_last_error(m_Ctx));
     }
@@ -251,6 +307,9 @@ private:
     rtx_ctx* m_Ctx{};
     int m_Width, m_Height;
     std::vector<uint32_t> m_Pixels;
+    rtx_camera m_Cam{};         // the camera of the last Render / RenderAdaptive / RenderAov / RenderSamplePasses
+    bool m_HaveCam{false};
+    uint32_t m_SampleK{0};      // the factor of the last RenderSamplePasses (0: none yet)
 };
 
 }  // namespace rtx
