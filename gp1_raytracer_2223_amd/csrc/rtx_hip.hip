@@ -1693,21 +1693,37 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
 #undef n_pl
 #undef n_mesh
 
-// ====================================================================== ray queries
-// Scene::GetClosestHit (ANY = false) and Scene::DoesHit (ANY = true) on caller-supplied rays
-// (rtx_trace_rays*, rtx_occluded*, rtx.h): rays 64w .. 64w + 63 are wave w, ray i lane i & 63, tail
-// lanes inactive; one wave is one workgroup.  Closest hit is the hit pass (PHASE 7 of render_tile) with
-// the ray read from memory and a linear output index; occlusion is the light loop's any-hit body on
-// the lane's own ray.  Both share every test and walk with the render kernel (sphere_perp / sphere_t,
-// plane_num / plane_den, mesh_traverse and below) and restate only the loops around them: with those
-// loops as helpers called from both, 94 of the render kernel's instantiations compiled to other code
-// (tools/codeobj_diff.py), and as it is they are the parent's instruction for instruction.
-// DEEP / HSTK: the DFS stacks, as there.
-// No exact cull: its records are anchored at a camera or a light, and a caller's ray has no anchor.
-//
-// A caller's ray is any eight floats, and the result is the reference's for them, so every shortcut
-// on the path that is proved for the renderer's own rays is taken per wave, when all ACTIVE lanes are
-// inside its domain, and the exact form otherwise:
+// ====================================================================== the ray kernels' shared bodies
+// Scene::GetClosestHit, Scene::DoesHit, the hit record and the reference's light loop for a ray that is
+// not render_tile's: rtx_query_kernel, rtx_shade_kernel and rtx_adaptive_kernel (below) all call these,
+// so each body is stated once for the three.  They share every test and walk with the render kernel
+// (sphere_perp / sphere_t, plane_num / plane_den, mesh_traverse and below, shade, the RTX_LIGHT_* macros)
+// but not these loops: with the loops as helpers called from render_tile too, 94 of the render kernel's
+// instantiations compiled to other code (tools/codeobj_diff.py).  So the helpers stand after render_tile,
+// which never calls them and is the parent's instruction for instruction
+// (profiles/ray_kernels_shared/codeobj_diff.txt).
+// The renderer's own shortcuts stay off here: no exact cull (its records are anchored at a camera or a
+// light, and a caller's ray has no anchor), no room a / d planes or room skip, no camera numerators, no
+// LDS numerator cache, no atomicMin key, no split phases.  sphere_perp / sphere_t, plane_num / plane_den,
+// the hit record's rebuild and div3_exact restate the reference for any operand.
+namespace {
+
+// A caller's ray: eight floats (rtx_ray), read with vector loads.  A tail lane keeps a harmless ray; it
+// is in no mask.
+struct QRay {
+    float v[8];
+};
+__device__ __forceinline__ Ray load_ray(const float* __restrict__ rays, uint32_t i, bool valid,
+                                        unsigned long long& slow) {
+    QRay q = {{0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 0.f}};
+    if (valid) q = *reinterpret_cast<const QRay*>(rays + static_cast<size_t>(i) * 8u);
+    return make_ray(q.v[0], q.v[1], q.v[2], q.v[3], q.v[4], q.v[5], q.v[6], q.v[7], slow);
+}
+
+// The walk a wave takes.  A ray here is any eight floats (a shadow ray starts wherever a caller's ray
+// put the hit point), and the result is the reference's for them, so every shortcut that is proved for
+// the renderer's own rays is taken per wave, when all ACTIVE lanes are inside its domain, and the exact
+// form otherwise:
 //   * rcp3_exact's domain (each |d_k| in [2^-60, 2^60]): make_ray's `slow`.  A slow lane has a zero,
 //     infinite or NaN inverse component, and v_min / v_max then drop a NaN that std::min / std::max
 //     keep: the wave takes kSlabExact.
@@ -1718,223 +1734,99 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2
 //     every active lane is not slow and has |d_k| <= 1 (so |d| <= sqrt 3) and |o_k| <= 2^40, and the scene
 //     is tri_fast; otherwise XC, Vector3::Cross as written plus the check.
 //   * the octant node copies: a wave that is fast in all of the above, S.oct_bytes, batch_octant >= 0.
-//   * plane_cand (any-hit) skips the division for lanes that cannot pass t >= tmin given tmin > 0, and
-//     its "beyond" test is stated for a finite tmax: taken when every active lane has tmin > 0 and
-//     |tmax| < inf (NaN fails); otherwise t = num / den is computed and tested as HitTest_Plane does
-//     (with tmin <= 0 a zero or negative t is a hit).  Closest hit always divides, as PHASE 7 does
-//     outside the room.
-//   * the room's a / d planes, the host's camera numerators and the LDS numerator cache belong to the
-//     renderer's rays and are not used; neither are the cull (|d| = 1 +- 3u) nor the atomicMin key.
-//   * sphere_perp / sphere_t, plane_num / plane_den, the hit record's rebuild and div3_exact restate the
-//     reference for any operand.
-struct QRay {
-    float v[8];
+struct WaveWalk {
+    bool slab_fast, fast;
+    int oct;
 };
-template <bool ANY, bool DEEP, bool HSTK>
-__global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_WAVES_PER_EU)
-    rtx_query_kernel(const DevScene S, const QueryArgs Q) {
-    constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
-    __shared__ uint4 stkE[kBlockThreads / 64][kDepth];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t widx = blockIdx.x * kWavesPerBlock + wave;
-    if (widx * 64u >= Q.n) return;
-    uint4* stk = stkE[wave];
-    if constexpr (HSTK) stk = S.hstk + static_cast<size_t>(widx) * S.hstk_depth;
-    const uint32_t i = widx * 64u + lane;
-    const bool valid = i < Q.n;
-    // the lane's ray: 32 bytes with vector loads (a tail lane keeps a harmless one; it is in no mask)
-    QRay q = {{0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 0.f}};
-    if (valid) q = *reinterpret_cast<const QRay*>(Q.rays + static_cast<size_t>(i) * 8u);
-    unsigned long long slow;
-    const Ray r = make_ray(q.v[0], q.v[1], q.v[2], q.v[3], q.v[4], q.v[5], q.v[6], q.v[7], slow);
-    const unsigned long long active = ballot(valid);
+__device__ __forceinline__ WaveWalk wave_walk(const DevScene& S, const Ray& r, unsigned long long slow,
+                                              unsigned long long active) {
     slow |= ballot(!finite3(r.ox, r.oy, r.oz));
-    const bool slab_fast = (active & slow) == 0;
+    WaveWalk w;
+    w.slab_fast = (active & slow) == 0;
     const bool tri_dom = fmaxf(fmaxf(fabsf(r.dx), fabsf(r.dy)), fabsf(r.dz)) <= 1.f &&
                          fmaxf(fmaxf(fabsf(r.ox), fabsf(r.oy)), fabsf(r.oz)) <= 0x1p40f;
     // (v_max drops a NaN component, and a lane with one is slow already)
-    const bool fast = slab_fast && S.tri_fast && (active & ~ballot(tri_dom)) == 0;
-    const int oct = (fast && S.oct_bytes) ? batch_octant(r, active) : -1;
-    Counts cnt;   // (never counted: the walks' COUNT is off)
+    w.fast = w.slab_fast && S.tri_fast && (active & ~ballot(tri_dom)) == 0;
+    w.oct = (w.fast && S.oct_bytes) ? batch_octant(r, active) : -1;
+    return w;
+}
 
-    if constexpr (ANY) {
-        // ---- Scene::DoesHit (Scene.cpp:68-96); `live` = lanes still without an occluder
-        unsigned long long live = active;
-        for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
-            const float4 s = ldcb16(S.spheres, opaque(k));
-            const SphereProj p = sphere_perp(s, r);
-            const unsigned long long near = ballot(!(s.w < p.perp)) & live;
-            if (!near) continue;
-            const float t = sphere_t(s, p);
-            live &= ~(near & ballot(!(t < r.tmin)) & ballot(!(t > r.tmax)));
+// One mesh by the wave's walk.  ANY: `mask` is `live`, which loses the occluded lanes.
+template <bool ANY>
+__device__ __forceinline__ void walk_mesh(const DevScene& S, const int4 M, const Ray& r, const WaveWalk& w,
+                                          unsigned long long mask, uint32_t lane, uint4* stk, float& t, uint32_t& tri,
+                                          unsigned long long& live, Counts& cnt) {
+    if (w.oct >= 0)
+        mesh_traverse<ANY, kSlabOct, false>(S, M, r, w.oct, mask, lane, stk, nullptr, t, tri, live, cnt);
+    else if (w.fast)
+        mesh_traverse<ANY, kSlabFast, false>(S, M, r, 0, mask, lane, stk, nullptr, t, tri, live, cnt);
+    else if (w.slab_fast)
+        mesh_traverse<ANY, kSlabFast, false, false, false, true>(S, M, r, 0, mask, lane, stk, nullptr, t, tri, live,
+                                                                 cnt);
+    else
+        mesh_traverse<ANY, kSlabExact, false, false, false, true>(S, M, r, 0, mask, lane, stk, nullptr, t, tri, live,
+                                                                  cnt);
+}
+
+// Scene::DoesHit (Scene.cpp:68-96) for the lanes of `active`; returns `live`, the lanes still without
+// an occluder.  plane_cand skips the division for lanes that cannot pass t >= tmin given tmin > 0, and
+// its "beyond" test is stated for a finite tmax: taken when every active lane has tmin > 0 and
+// |tmax| < inf (NaN fails); otherwise t = num / den is computed and tested as HitTest_Plane does (with
+// tmin <= 0 a zero or negative t is a hit).  (A shadow ray has tmin = 1e-4, so its domain is a finite
+// tmax = |l| in every hit lane.)
+__device__ __forceinline__ unsigned long long any_hit(const DevScene& S, const Ray& r, const WaveWalk& w,
+                                                      unsigned long long active, uint32_t lane, uint4* stk,
+                                                      Counts& cnt) {
+    unsigned long long live = active;
+    for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
+        const float4 s = ldcb16(S.spheres, opaque(k));
+        const SphereProj p = sphere_perp(s, r);
+        const unsigned long long near = ballot(!(s.w < p.perp)) & live;
+        if (!near) continue;
+        const float t = sphere_t(s, p);
+        live &= ~(near & ballot(!(t < r.tmin)) & ballot(!(t > r.tmax)));
+    }
+    const bool pl_dom = (active & ~ballot(r.tmin > 0.f && fabsf(r.tmax) < INFINITY)) == 0;
+    if (pl_dom) {
+        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
+            float4 p0, p1;
+            ldcb32(S.planes, opaque(k), p0, p1);
+            const float num = plane_num(p0, p1, r), den = plane_den(p1, r);
+            const unsigned long long cand = plane_cand(num, den, r.tmax) & live;
+            if (!cand) continue;   // also taken once no lane is live
+            const float t = num / den;
+            live &= ~(ballot(t >= r.tmin) & ballot(t < r.tmax) & cand);
         }
-        const bool pl_dom = (active & ~ballot(r.tmin > 0.f && fabsf(r.tmax) < INFINITY)) == 0;
-        if (pl_dom) {
-            for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
-                float4 p0, p1;
-                ldcb32(S.planes, opaque(k), p0, p1);
-                const float num = plane_num(p0, p1, r), den = plane_den(p1, r);
-                const unsigned long long cand = plane_cand(num, den, r.tmax) & live;
-                if (!cand) continue;   // also taken once no lane is live
-                const float t = num / den;
-                live &= ~(ballot(t >= r.tmin) & ballot(t < r.tmax) & cand);
-            }
-        } else {
-            for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
-                float4 p0, p1;
-                ldcb32(S.planes, opaque(k), p0, p1);
-                const float t = plane_num(p0, p1, r) / plane_den(p1, r);
-                live &= ~(ballot(t >= r.tmin) & ballot(t < r.tmax));
-            }
-        }
-        for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
-            if (!live) break;
-            float st = 0.f;
-            uint32_t stri = 0;
-            const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
-            if (oct >= 0)
-                mesh_traverse<true, kSlabOct, false>(S, M, r, oct, live, lane, stk, nullptr, st, stri, live, cnt);
-            else if (fast)
-                mesh_traverse<true, kSlabFast, false>(S, M, r, 0, live, lane, stk, nullptr, st, stri, live, cnt);
-            else if (slab_fast)
-                mesh_traverse<true, kSlabFast, false, false, false, true>(S, M, r, 0, live, lane, stk, nullptr, st,
-                                                                          stri, live, cnt);
-            else
-                mesh_traverse<true, kSlabExact, false, false, false, true>(S, M, r, 0, live, lane, stk, nullptr, st,
-                                                                           stri, live, cnt);
-        }
-        if (valid) Q.occ[i] = static_cast<uint8_t>(((live >> lane) & 1ull) ? 0u : 1u);
-        return;
     } else {
-        // ---- Scene::GetClosestHit (Scene.cpp:29-66), as PHASE 7 of render_tile
-        float best_t = FLT_MAX, sc_t = FLT_MAX;
-        uint32_t best_kind = 0, best_idx = 0;   // kind: 0 none, 1 sphere, 2 plane, 3 triangle; idx: BYTE offset
-        for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
-            const float4 s = ldcb16(S.spheres, opaque(k));
-            const SphereProj p = sphere_perp(s, r);
-            const unsigned long long near = ballot(!(s.w < p.perp)) & active;
-            if (!near) continue;
-            const float t = sphere_t(s, p);
-            const bool h = ((near >> lane) & 1ull) & !(t < r.tmin) & !(t > r.tmax);
-            sc_t = h ? t : sc_t;
-            const bool b = h & (t < best_t);
-            best_t = b ? t : best_t;
-            best_kind = b ? 1u : best_kind;
-            best_idx = b ? k : best_idx;
-        }
         for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
             float4 p0, p1;
             ldcb32(S.planes, opaque(k), p0, p1);
             const float t = plane_num(p0, p1, r) / plane_den(p1, r);
-            const bool h = valid & (t >= r.tmin) & (t < r.tmax);
-            sc_t = h ? t : sc_t;
-            const bool b = h & (t < best_t);
-            best_t = b ? t : best_t;
-            best_kind = b ? 2u : best_kind;
-            best_idx = b ? k : best_idx;
-        }
-        for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
-            const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
-            uint32_t sc_tri = 0;
-            unsigned long long unused = 0;
-            if (oct >= 0)
-                mesh_traverse<false, kSlabOct, false>(S, M, r, oct, active, lane, stk, nullptr, sc_t, sc_tri, unused,
-                                                      cnt);
-            else if (fast)
-                mesh_traverse<false, kSlabFast, false>(S, M, r, 0, active, lane, stk, nullptr, sc_t, sc_tri, unused,
-                                                       cnt);
-            else if (slab_fast)
-                mesh_traverse<false, kSlabFast, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr,
-                                                                           sc_t, sc_tri, unused, cnt);
-            else
-                mesh_traverse<false, kSlabExact, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr,
-                                                                            sc_t, sc_tri, unused, cnt);
-            if (sc_t < best_t) { best_t = sc_t; best_kind = 3; best_idx = sc_tri; }
-        }
-        // ---- hit record (rebuilt from t: ray.origin + t * ray.direction, Utils.h:62-64)
-        const bool did = best_kind != 0;
-        float nx = 0.f, ny = 0.f, nz = 0.f;
-        uint32_t mat = 0;
-        if (did) {
-            if (best_kind == 1) {
-                const float hx = r.ox + r.dx * best_t, hy = r.oy + r.dy * best_t, hz = r.oz + r.dz * best_t;
-                const float4 s = ldcb16(S.spheres, best_idx);
-                nx = hx - s.x; ny = hy - s.y; nz = hz - s.z;
-                const float m = sqrtf(nx * nx + ny * ny + nz * nz);   // closestHit.normal.Normalize()
-                div3_exact(nx, ny, nz, m);
-                mat = ldc(S.sphere_mat, best_idx >> 4);
-            } else if (best_kind == 2) {
-                float4 p0, p1;
-                ldcb32(S.planes, best_idx, p0, p1);
-                nx = p1.x; ny = p1.y; nz = p1.z;
-                mat = __float_as_uint(p0.w);
-            } else {
-                Tri T;
-                ldcb64(S.tris, best_idx, T.a, T.b, T.c, T.d);
-                nx = T.a.w; ny = T.b.w; nz = T.c.w;
-                mat = __float_as_uint(T.d.x);
-            }
-        }
-        if (valid) {
-            const size_t o = i;
-            const uint32_t m = uni(Q.mask);
-            if (m & RTX_AOV_DEPTH) Q.depth[o] = best_t;   // (a miss: the empty HitRecord's FLT_MAX)
-            if (m & RTX_AOV_NORMAL) {
-                Q.normal[3 * o] = nx; Q.normal[3 * o + 1] = ny; Q.normal[3 * o + 2] = nz;
-            }
-            if (m & RTX_AOV_MATERIAL) Q.material[o] = mat;
-            // best_idx is the record's byte offset: 16 B per sphere, 32 per plane, 64 per triangle
-            if (m & RTX_AOV_PRIMITIVE) Q.primitive[o] = did ? (best_kind << 30) | (best_idx >> (best_kind + 3u)) : 0u;
+            live &= ~(ballot(t >= r.tmin) & ballot(t < r.tmax));
         }
     }
+    for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
+        if (!live) break;
+        float st = 0.f;
+        uint32_t stri = 0;
+        const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
+        walk_mesh<true>(S, M, r, w, live, lane, stk, st, stri, live, cnt);
+    }
+    return live;
 }
 
-// ====================================================================== shaded rays
-// Renderer::RenderPixel from GetClosestHit on (Renderer.cpp:116-181) for caller-supplied rays
-// (rtx_shade_rays*, rtx.h): the ray is the caller's eight floats as rtx_query_kernel reads them, in its
-// layout (ray i = lane i & 63 of wave i / 64, tail lanes inactive and storing nothing), and viewDirection
-// is the ray's direction as given, so Material::Shade receives -direction whatever its length.
-// Closest hit is the query kernel's closest-hit body with its per-wave choice of walk; the hit record
-// is render_tile's (hit.origin = o + d * t included); the light loop is render_tile's generic one
-// (SPEC 0, shade<0>, no counters), and its shadow ray Ray{originOffset, l, 1e-4, |l|} runs the query
-// kernel's any-hit body with `hitmask` as the active mask: the shadow ray's own `slow` bits, origin,
-// |d_k| <= 1, |o_k| <= 2^40 and tmax decide the walk and the plane loop per wave, as for a query
-// (a caller's ray can put a hit point anywhere, so none of these is known beforehand).
-// The renderer's own shortcuts stay off: no exact cull (no anchor), no camera numerators, no room
-// planes or room skip, no LDS numerator cache, no atomicMin key, no split phases.  The loops are
-// restated, not shared with render_tile or rtx_query_kernel, for the reason given there.
-// Occupancy target: the generic kernel's (65 VGPRs, 7 waves per SIMD).  Asked for 8 waves the default
-// kernel fits 64 VGPRs without scratch and measured 2-3 % slower on W4_Bunny and W3 at 1080p
-// (profiles/shade/ab_waves8.txt), and the HBM-stack one spilled.
-template <bool DEEP, bool HSTK>
-__global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_WAVES_PER_EU)
-    rtx_shade_kernel(const DevScene S, const ShadeArgs Q) {
-    constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
-    __shared__ uint4 stkE[kBlockThreads / 64][kDepth];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t widx = blockIdx.x * kWavesPerBlock + wave;
-    if (widx * 64u >= Q.n) return;
-    uint4* stk = stkE[wave];
-    if constexpr (HSTK) stk = S.hstk + static_cast<size_t>(widx) * S.hstk_depth;
-    const uint32_t i = widx * 64u + lane;
-    const bool valid = i < Q.n;
-    // the lane's ray: 32 bytes with vector loads (a tail lane keeps a harmless one; it is in no mask)
-    QRay q = {{0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 0.f}};
-    if (valid) q = *reinterpret_cast<const QRay*>(Q.rays + static_cast<size_t>(i) * 8u);
-    unsigned long long slow;
-    const Ray r = make_ray(q.v[0], q.v[1], q.v[2], q.v[3], q.v[4], q.v[5], q.v[6], q.v[7], slow);
-    const unsigned long long active = ballot(valid);
-    slow |= ballot(!finite3(r.ox, r.oy, r.oz));
-    const bool slab_fast = (active & slow) == 0;
-    const bool tri_dom = fmaxf(fmaxf(fabsf(r.dx), fabsf(r.dy)), fabsf(r.dz)) <= 1.f &&
-                         fmaxf(fmaxf(fabsf(r.ox), fabsf(r.oy)), fabsf(r.oz)) <= 0x1p40f;
-    const bool fast = slab_fast && S.tri_fast && (active & ~ballot(tri_dom)) == 0;
-    const int oct = (fast && S.oct_bytes) ? batch_octant(r, active) : -1;
-    Counts cnt;   // (never counted: the walks' COUNT is off)
-
-    // ---- Scene::GetClosestHit (Scene.cpp:29-66), as rtx_query_kernel<false, ...>
+// Scene::GetClosestHit (Scene.cpp:29-66), as PHASE 7 of render_tile outside the room (the planes always
+// divide).  kind: 0 none, 1 sphere, 2 plane, 3 triangle; idx: the record's BYTE offset (16 B per sphere,
+// 32 per plane, 64 per triangle); a miss keeps the empty HitRecord's t = FLT_MAX.
+struct Closest {
+    float t;
+    uint32_t kind, idx;
+};
+__device__ __forceinline__ Closest closest_hit(const DevScene& S, const Ray& r, const WaveWalk& w,
+                                               unsigned long long active, bool valid, uint32_t lane, uint4* stk,
+                                               Counts& cnt) {
     float best_t = FLT_MAX, sc_t = FLT_MAX;
-    uint32_t best_kind = 0, best_idx = 0;   // kind: 0 none, 1 sphere, 2 plane, 3 triangle; idx: BYTE offset
+    uint32_t best_kind = 0, best_idx = 0;
     for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
         const float4 s = ldcb16(S.spheres, opaque(k));
         const SphereProj p = sphere_perp(s, r);
@@ -1963,49 +1855,58 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
         const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
         uint32_t sc_tri = 0;
         unsigned long long unused = 0;
-        if (oct >= 0)
-            mesh_traverse<false, kSlabOct, false>(S, M, r, oct, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
-        else if (fast)
-            mesh_traverse<false, kSlabFast, false>(S, M, r, 0, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
-        else if (slab_fast)
-            mesh_traverse<false, kSlabFast, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
-                                                                       sc_tri, unused, cnt);
-        else
-            mesh_traverse<false, kSlabExact, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
-                                                                        sc_tri, unused, cnt);
+        walk_mesh<false>(S, M, r, w, active, lane, stk, sc_t, sc_tri, unused, cnt);
         if (sc_t < best_t) { best_t = sc_t; best_kind = 3; best_idx = sc_tri; }
     }
+    return {best_t, best_kind, best_idx};
+}
 
-    // ---- hit record (rebuilt from t: ray.origin + t * ray.direction, Utils.h:62-64), as render_tile
-    const bool did = best_kind != 0;
-    float hx = 0.f, hy = 0.f, hz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
-    uint32_t mat = 0;
-    if (did) {
-        hx = r.ox + r.dx * best_t; hy = r.oy + r.dy * best_t; hz = r.oz + r.dz * best_t;
-        if (best_kind == 1) {
-            const float4 s = ldcb16(S.spheres, best_idx);
-            nx = hx - s.x; ny = hy - s.y; nz = hz - s.z;
-            const float m = sqrtf(nx * nx + ny * ny + nz * nz);   // closestHit.normal.Normalize()
-            div3_exact(nx, ny, nz, m);   // nx /= m; ny /= m; nz /= m
-            mat = ldc(S.sphere_mat, best_idx >> 4);
-        } else if (best_kind == 2) {
+// The hit record, rebuilt from t (ray.origin + t * ray.direction, Utils.h:62-64).  POINT: hit.origin for
+// every hit, as render_tile rebuilds it (the light loop needs it); without, only a sphere's normal does.
+struct HitRec {
+    float hx, hy, hz, nx, ny, nz;
+    uint32_t mat;
+};
+template <bool POINT>
+__device__ __forceinline__ HitRec hit_record(const DevScene& S, const Ray& r, const Closest& c) {
+    HitRec h = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0u};
+    if (c.kind != 0) {
+        if (POINT || c.kind == 1) {
+            h.hx = r.ox + r.dx * c.t; h.hy = r.oy + r.dy * c.t; h.hz = r.oz + r.dz * c.t;
+        }
+        if (c.kind == 1) {
+            const float4 s = ldcb16(S.spheres, c.idx);
+            h.nx = h.hx - s.x; h.ny = h.hy - s.y; h.nz = h.hz - s.z;
+            const float m = sqrtf(h.nx * h.nx + h.ny * h.ny + h.nz * h.nz);   // closestHit.normal.Normalize()
+            div3_exact(h.nx, h.ny, h.nz, m);   // nx /= m; ny /= m; nz /= m
+            h.mat = ldc(S.sphere_mat, c.idx >> 4);
+        } else if (c.kind == 2) {
             float4 p0, p1;
-            ldcb32(S.planes, best_idx, p0, p1);
-            nx = p1.x; ny = p1.y; nz = p1.z;
-            mat = __float_as_uint(p0.w);
+            ldcb32(S.planes, c.idx, p0, p1);
+            h.nx = p1.x; h.ny = p1.y; h.nz = p1.z;
+            h.mat = __float_as_uint(p0.w);
         } else {
             Tri T;
-            ldcb64(S.tris, best_idx, T.a, T.b, T.c, T.d);   // best_idx: byte offset
-            nx = T.a.w; ny = T.b.w; nz = T.c.w;
-            mat = __float_as_uint(T.d.x);
+            ldcb64(S.tris, c.idx, T.a, T.b, T.c, T.d);
+            h.nx = T.a.w; h.ny = T.b.w; h.nz = T.c.w;
+            h.mat = __float_as_uint(T.d.x);
         }
     }
+    return h;
+}
 
-    // ---- the reference's light loop (Renderer.cpp:128-176), as render_tile's generic one
+// The reference's light loop (Renderer.cpp:128-176) and ColorRGB::MaxToOne for the hit `h` of ray `r`:
+// render_tile's generic one (SPEC 0, shade<0>, no counters) in the macros it expands, with viewDirection
+// = -direction whatever its length.  The shadow ray Ray{originOffset, l, 1e-4, |l|} runs any_hit with
+// `hitmask` as the active mask, by the walk its own slow bits, origin and direction choose.
+__device__ __forceinline__ void light_loop(const DevScene& S, const Ray& r, const HitRec& h, bool did, int mode,
+                                           int shadows, uint32_t lane, uint4* stk, Counts& cnt, float& fr, float& fg,
+                                           float& fb) {
+    const float hx = h.hx, hy = h.hy, hz = h.hz, nx = h.nx, ny = h.ny, nz = h.nz;
+    const uint32_t mat = h.mat;
     float shadowFactor = 1.f;
-    float fr = 0.f, fg = 0.f, fb = 0.f;
+    fr = 0.f; fg = 0.f; fb = 0.f;
     const unsigned long long hitmask = ballot(did);
-    const int mode = Q.mode;
     if (hitmask) {
         // originOffset = hit.origin + hit.normal * 0.0001f (Renderer.cpp:126)
         const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
@@ -2014,68 +1915,13 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
             float4 L0, L1;
             ldcb32(S.lights, opaque(li * 32u), L0, L1);
             const int ltype = __float_as_int(L0.w);
-            const bool known = (ltype == RTX_LIGHT_POINT || ltype == RTX_LIGHT_DIRECTIONAL);
-            float lx = known ? L0.x - oox : 0.f, ly = known ? L0.y - ooy : 0.f, lz = known ? L0.z - ooz : 0.f;
-            const float mag = sqrtf(lx * lx + ly * ly + lz * lz);
-            div3_exact(lx, ly, lz, mag);
+            RTX_LIGHT_DIR();
             bool occ = false;
-            if (Q.shadows) {
-                // Scene::DoesHit (Scene.cpp:68-96) on Ray{originOffset, l, 1e-4, |l|}, as
-                // rtx_query_kernel<true, ...> with `hitmask` for `active`; `live` = lanes still without
-                // an occluder
+            if (shadows) {
                 unsigned long long sslow;
                 const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, 0.0001f, mag, sslow);
-                sslow |= ballot(!finite3(sr.ox, sr.oy, sr.oz));
-                const bool s_slab_fast = (hitmask & sslow) == 0;
-                const bool s_tri_dom = fmaxf(fmaxf(fabsf(sr.dx), fabsf(sr.dy)), fabsf(sr.dz)) <= 1.f &&
-                                       fmaxf(fmaxf(fabsf(sr.ox), fabsf(sr.oy)), fabsf(sr.oz)) <= 0x1p40f;
-                const bool sfast = s_slab_fast && S.tri_fast && (hitmask & ~ballot(s_tri_dom)) == 0;
-                const int soct = (sfast && S.oct_bytes) ? batch_octant(sr, hitmask) : -1;
-                unsigned long long live = hitmask;
-                for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
-                    const float4 s = ldcb16(S.spheres, opaque(k));
-                    const SphereProj p = sphere_perp(s, sr);
-                    const unsigned long long near = ballot(!(s.w < p.perp)) & live;
-                    if (!near) continue;
-                    const float t = sphere_t(s, p);
-                    live &= ~(near & ballot(!(t < sr.tmin)) & ballot(!(t > sr.tmax)));
-                }
-                // (tmin = 1e-4 > 0: plane_cand's domain is a finite tmax = |l| in every hit lane)
-                const bool pl_dom = (hitmask & ~ballot(sr.tmin > 0.f && fabsf(sr.tmax) < INFINITY)) == 0;
-                if (pl_dom) {
-                    for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
-                        float4 p0, p1;
-                        ldcb32(S.planes, opaque(k), p0, p1);
-                        const float num = plane_num(p0, p1, sr), den = plane_den(p1, sr);
-                        const unsigned long long cand = plane_cand(num, den, sr.tmax) & live;
-                        if (!cand) continue;   // also taken once no lane is live
-                        const float t = num / den;
-                        live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax) & cand);
-                    }
-                } else {
-                    for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
-                        float4 p0, p1;
-                        ldcb32(S.planes, opaque(k), p0, p1);
-                        const float t = plane_num(p0, p1, sr) / plane_den(p1, sr);
-                        live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax));
-                    }
-                }
-                for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
-                    if (!live) break;
-                    float st = 0.f;
-                    uint32_t stri = 0;
-                    const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
-                    if (soct >= 0)
-                        mesh_traverse<true, kSlabOct, false>(S, M, sr, soct, live, lane, stk, nullptr, st, stri, live, cnt);
-                    else if (sfast)
-                        mesh_traverse<true, kSlabFast, false>(S, M, sr, 0, live, lane, stk, nullptr, st, stri, live, cnt);
-                    else if (s_slab_fast)
-                        mesh_traverse<true, kSlabFast, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
-                                                                                  st, stri, live, cnt);
-                    else
-                        mesh_traverse<true, kSlabExact, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
-                                                                                   st, stri, live, cnt);
-                }
+                const WaveWalk sw = wave_walk(S, sr, sslow, hitmask);
+                const unsigned long long live = any_hit(S, sr, sw, hitmask, lane, stk, cnt);
                 occ = did & !((live >> lane) & 1ull);
             }
             if (!did) continue;
@@ -2083,39 +1929,90 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
                 shadowFactor *= 0.95f;
                 continue;
             }
-            if (mode == RTX_MODE_COMBINED || mode == RTX_MODE_RADIANCE) {
-                // LightUtils::GetRadiance (Utils.h:355-369) at hit.origin
-                float s = 0.f;
-                bool any = true;
-                if (ltype == RTX_LIGHT_POINT) {
-                    const float ex = L0.x - hx, ey = L0.y - hy, ez = L0.z - hz;
-                    s = L1.w / (ex * ex + ey * ey + ez * ez);
-                } else if (ltype == RTX_LIGHT_DIRECTIONAL) {
-                    s = L1.w;
-                } else {
-                    any = false;
-                }
-                const float rr = any ? L1.x * s : 0.f, rg = any ? L1.y * s : 0.f, rb = any ? L1.z * s : 0.f;
-                if (mode == RTX_MODE_RADIANCE) {
-                    fr += rr; fg += rg; fb += rb;
-                } else {
-                    const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
-                    const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
-                    fr += (rr * oa) * br.r; fg += (rg * oa) * br.g; fb += (rb * oa) * br.b;
-                }
-            } else if (mode == RTX_MODE_OBSERVED_AREA) {
-                const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
-                fr += oa; fg += oa; fb += oa;
-            } else if (mode == RTX_MODE_BRDF) {
-                const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
-                fr += br.r; fg += br.g; fb += br.b;
-            }
+            RTX_LIGHT_TERM(mode, 0, false)
         }
         if (did) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
     }
-    // ColorRGB::MaxToOne (ColorRGB.h:12-17)
-    const float mv = smax(fr, smax(fg, fb));
-    if (mv > 1.f) { fr /= mv; fg /= mv; fb /= mv; }
+    RTX_MAX_TO_ONE()
+}
+
+}  // namespace
+
+// ====================================================================== ray queries
+// Scene::GetClosestHit (ANY = false) and Scene::DoesHit (ANY = true) on caller-supplied rays
+// (rtx_trace_rays*, rtx_occluded*, rtx.h): rays 64w .. 64w + 63 are wave w, ray i lane i & 63, tail
+// lanes inactive; one wave is one workgroup.  Closest hit is the hit pass (PHASE 7 of render_tile) with
+// the ray read from memory and a linear output index (closest_hit, hit_record); occlusion is any_hit on
+// the lane's own ray over the wave's active mask.  DEEP / HSTK: the DFS stacks, as in the render kernel.
+template <bool ANY, bool DEEP, bool HSTK>
+__global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_WAVES_PER_EU)
+    rtx_query_kernel(const DevScene S, const QueryArgs Q) {
+    constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
+    __shared__ uint4 stkE[kBlockThreads / 64][kDepth];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t widx = blockIdx.x * kWavesPerBlock + wave;
+    if (widx * 64u >= Q.n) return;
+    uint4* stk = stkE[wave];
+    if constexpr (HSTK) stk = S.hstk + static_cast<size_t>(widx) * S.hstk_depth;
+    const uint32_t i = widx * 64u + lane;
+    const bool valid = i < Q.n;
+    unsigned long long slow;
+    const Ray r = load_ray(Q.rays, i, valid, slow);
+    const unsigned long long active = ballot(valid);
+    const WaveWalk w = wave_walk(S, r, slow, active);
+    Counts cnt;   // (never counted: the walks' COUNT is off)
+
+    if constexpr (ANY) {
+        const unsigned long long live = any_hit(S, r, w, active, lane, stk, cnt);
+        if (valid) Q.occ[i] = static_cast<uint8_t>(((live >> lane) & 1ull) ? 0u : 1u);
+    } else {
+        const Closest c = closest_hit(S, r, w, active, valid, lane, stk, cnt);
+        const HitRec h = hit_record<false>(S, r, c);
+        if (valid) {
+            const size_t o = i;
+            const uint32_t m = uni(Q.mask);
+            if (m & RTX_AOV_DEPTH) Q.depth[o] = c.t;   // (a miss: the empty HitRecord's FLT_MAX)
+            if (m & RTX_AOV_NORMAL) {
+                Q.normal[3 * o] = h.nx; Q.normal[3 * o + 1] = h.ny; Q.normal[3 * o + 2] = h.nz;
+            }
+            if (m & RTX_AOV_MATERIAL) Q.material[o] = h.mat;
+            // c.idx is the record's byte offset: 16 B per sphere, 32 per plane, 64 per triangle
+            if (m & RTX_AOV_PRIMITIVE) Q.primitive[o] = c.kind != 0 ? (c.kind << 30) | (c.idx >> (c.kind + 3u)) : 0u;
+        }
+    }
+}
+
+// ====================================================================== shaded rays
+// Renderer::RenderPixel from GetClosestHit on (Renderer.cpp:116-181) for caller-supplied rays
+// (rtx_shade_rays*, rtx.h): the ray is the caller's eight floats as rtx_query_kernel reads them, in its
+// layout (ray i = lane i & 63 of wave i / 64, tail lanes inactive and storing nothing), and viewDirection
+// is the ray's direction as given, so Material::Shade receives -direction whatever its length.
+// The body is the ray kernels' shared one: closest_hit, hit_record with hit.origin, light_loop.
+// Occupancy target: the generic kernel's (65 VGPRs, 7 waves per SIMD).  Asked for 8 waves the default
+// kernel fits 64 VGPRs without scratch and measured 2-3 % slower on W4_Bunny and W3 at 1080p
+// (profiles/shade/ab_waves8.txt), and the HBM-stack one spilled.
+template <bool DEEP, bool HSTK>
+__global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_WAVES_PER_EU)
+    rtx_shade_kernel(const DevScene S, const ShadeArgs Q) {
+    constexpr int kDepth = HSTK ? 1 : (DEEP ? kStackDepthDeep : kStackDepth);
+    __shared__ uint4 stkE[kBlockThreads / 64][kDepth];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t widx = blockIdx.x * kWavesPerBlock + wave;
+    if (widx * 64u >= Q.n) return;
+    uint4* stk = stkE[wave];
+    if constexpr (HSTK) stk = S.hstk + static_cast<size_t>(widx) * S.hstk_depth;
+    const uint32_t i = widx * 64u + lane;
+    const bool valid = i < Q.n;
+    unsigned long long slow;
+    const Ray r = load_ray(Q.rays, i, valid, slow);
+    const unsigned long long active = ballot(valid);
+    const WaveWalk w = wave_walk(S, r, slow, active);
+    Counts cnt;   // (never counted: the walks' COUNT is off)
+
+    const Closest c = closest_hit(S, r, w, active, valid, lane, stk, cnt);
+    const HitRec h = hit_record<true>(S, r, c);
+    float fr, fg, fb;
+    light_loop(S, r, h, c.kind != 0, Q.mode, Q.shadows, lane, stk, cnt, fr, fg, fb);
     if (valid) {
         const size_t o = i;
         if (Q.out_px) Q.out_px[o] = (q8(fr) << Q.rshift) | (q8(fg) << Q.gshift) | (q8(fb) << Q.bshift) | Q.amask;
@@ -2133,9 +2030,9 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
 // Lanes: a wave holds 64 / k^2 listed pixels; lane bits 0 .. n-1 are sx, the next n bits sy (n = log2 k),
 // the rest the pixel's slot, so a pixel's lanes are valid together.  Tail lanes carry the shade kernel's
 // harmless ray and are in no mask.
-// The lane's ray is render_tile's primary ray of sample (k x + sx, k y + sy) of the k W x k H frame,
-// statement for statement; from there on the body is rtx_shade_kernel's (the generic walks chosen per
-// wave, SPEC 0, no exact cull, no room planes), restated like it and for its reason.
+// The lane's ray is render_tile's primary ray of sample (k x + sx, k y + sy) of the k W x k H frame, in
+// the macro it expands; from there on the body is rtx_shade_kernel's, the ray kernels' shared one (the
+// generic walks chosen per wave, SPEC 0, no exact cull, no room planes).
 // The resolve is the butterfly ss_add_xor3<1>, <2>, <4>, <8>, <16>, <32> cut after 2 n levels: with this
 // layout the first n levels are the contract's adjacent-pair tree over sx and the next n the tree over
 // sy.  <4> (row_half_mirror) equals lane ^ 4 only once a quad's four lanes hold one value: it is level 3
@@ -2170,212 +2067,20 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
         const int py = static_cast<int>(((xy >> 16) << n) | sy);
 
         // ---- primary ray (Renderer.cpp:104-114), as render_tile makes it for the sample frame
-        const int W = static_cast<int>(A.width), H = static_cast<int>(A.height);
-        const float fW = static_cast<float>(W), fH = static_cast<float>(H);
-        const float cx = (2.f * div_rn(px + 0.5f, fW, A.inv_width) - 1) * A.aspect * A.fov;
-        const float cy = (1.f - div_rn(2.f * (py + 0.5f), fH, A.inv_height)) * A.fov;
-        float dx = A.right[0] * cx + A.up[0] * cy + A.forward[0] * 1.f;
-        float dy = A.right[1] * cx + A.up[1] * cy + A.forward[1] * 1.f;
-        float dz = A.right[2] * cx + A.up[2] * cy + A.forward[2] * 1.f;
-        const float dm = sqrtf(dx * dx + dy * dy + dz * dz);
-        div3_exact(dx, dy, dz, dm);   // dx /= dm; ... (Vector3::Normalize)
+        RTX_PRIMARY_DIR(A, A);
         unsigned long long slow;
         // (a tail lane keeps the shade kernel's harmless ray; it is in no mask)
         const Ray r = make_ray(valid ? A.origin[0] : 0.f, valid ? A.origin[1] : 0.f, valid ? A.origin[2] : 0.f,
                                valid ? dx : 1.f, valid ? dy : 1.f, valid ? dz : 1.f, valid ? 0.0001f : 1.f,
                                valid ? FLT_MAX : 0.f, slow);
         const unsigned long long active = ballot(valid);
-        slow |= ballot(!finite3(r.ox, r.oy, r.oz));
-        const bool slab_fast = (active & slow) == 0;
-        const bool tri_dom = fmaxf(fmaxf(fabsf(r.dx), fabsf(r.dy)), fabsf(r.dz)) <= 1.f &&
-                             fmaxf(fmaxf(fabsf(r.ox), fabsf(r.oy)), fabsf(r.oz)) <= 0x1p40f;
-        const bool fast = slab_fast && S.tri_fast && (active & ~ballot(tri_dom)) == 0;
-        const int oct = (fast && S.oct_bytes) ? batch_octant(r, active) : -1;
+        const WaveWalk w = wave_walk(S, r, slow, active);
         Counts cnt;   // (never counted: the walks' COUNT is off)
 
-        // ---- Scene::GetClosestHit (Scene.cpp:29-66), as rtx_shade_kernel
-        float best_t = FLT_MAX, sc_t = FLT_MAX;
-        uint32_t best_kind = 0, best_idx = 0;   // kind: 0 none, 1 sphere, 2 plane, 3 triangle; idx: BYTE offset
-        for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
-            const float4 s = ldcb16(S.spheres, opaque(k));
-            const SphereProj p = sphere_perp(s, r);
-            const unsigned long long near = ballot(!(s.w < p.perp)) & active;
-            if (!near) continue;
-            const float t = sphere_t(s, p);
-            const bool h = ((near >> lane) & 1ull) & !(t < r.tmin) & !(t > r.tmax);
-            sc_t = h ? t : sc_t;
-            const bool b = h & (t < best_t);
-            best_t = b ? t : best_t;
-            best_kind = b ? 1u : best_kind;
-            best_idx = b ? k : best_idx;
-        }
-        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
-            float4 p0, p1;
-            ldcb32(S.planes, opaque(k), p0, p1);
-            const float t = plane_num(p0, p1, r) / plane_den(p1, r);
-            const bool h = valid & (t >= r.tmin) & (t < r.tmax);
-            sc_t = h ? t : sc_t;
-            const bool b = h & (t < best_t);
-            best_t = b ? t : best_t;
-            best_kind = b ? 2u : best_kind;
-            best_idx = b ? k : best_idx;
-        }
-        for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
-            const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
-            uint32_t sc_tri = 0;
-            unsigned long long unused = 0;
-            if (oct >= 0)
-                mesh_traverse<false, kSlabOct, false>(S, M, r, oct, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
-            else if (fast)
-                mesh_traverse<false, kSlabFast, false>(S, M, r, 0, active, lane, stk, nullptr, sc_t, sc_tri, unused, cnt);
-            else if (slab_fast)
-                mesh_traverse<false, kSlabFast, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
-                                                                           sc_tri, unused, cnt);
-            else
-                mesh_traverse<false, kSlabExact, false, false, false, true>(S, M, r, 0, active, lane, stk, nullptr, sc_t,
-                                                                            sc_tri, unused, cnt);
-            if (sc_t < best_t) { best_t = sc_t; best_kind = 3; best_idx = sc_tri; }
-        }
-
-        // ---- hit record (rebuilt from t: ray.origin + t * ray.direction, Utils.h:62-64), as render_tile
-        const bool did = best_kind != 0;
-        float hx = 0.f, hy = 0.f, hz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
-        uint32_t mat = 0;
-        if (did) {
-            hx = r.ox + r.dx * best_t; hy = r.oy + r.dy * best_t; hz = r.oz + r.dz * best_t;
-            if (best_kind == 1) {
-                const float4 s = ldcb16(S.spheres, best_idx);
-                nx = hx - s.x; ny = hy - s.y; nz = hz - s.z;
-                const float m = sqrtf(nx * nx + ny * ny + nz * nz);   // closestHit.normal.Normalize()
-                div3_exact(nx, ny, nz, m);   // nx /= m; ny /= m; nz /= m
-                mat = ldc(S.sphere_mat, best_idx >> 4);
-            } else if (best_kind == 2) {
-                float4 p0, p1;
-                ldcb32(S.planes, best_idx, p0, p1);
-                nx = p1.x; ny = p1.y; nz = p1.z;
-                mat = __float_as_uint(p0.w);
-            } else {
-                Tri T;
-                ldcb64(S.tris, best_idx, T.a, T.b, T.c, T.d);   // best_idx: byte offset
-                nx = T.a.w; ny = T.b.w; nz = T.c.w;
-                mat = __float_as_uint(T.d.x);
-            }
-        }
-
-        // ---- the reference's light loop (Renderer.cpp:128-176), as rtx_shade_kernel's
-        float shadowFactor = 1.f;
-        float fr = 0.f, fg = 0.f, fb = 0.f;
-        const unsigned long long hitmask = ballot(did);
-        const int mode = A.mode;
-        if (hitmask) {
-            // originOffset = hit.origin + hit.normal * 0.0001f (Renderer.cpp:126)
-            const float oox = hx + nx * 0.0001f, ooy = hy + ny * 0.0001f, ooz = hz + nz * 0.0001f;
-            const float vx = -r.dx, vy = -r.dy, vz = -r.dz;
-            for (uint32_t li = 0; li < S.n_lights; ++li) {
-                float4 L0, L1;
-                ldcb32(S.lights, opaque(li * 32u), L0, L1);
-                const int ltype = __float_as_int(L0.w);
-                const bool known = (ltype == RTX_LIGHT_POINT || ltype == RTX_LIGHT_DIRECTIONAL);
-                float lx = known ? L0.x - oox : 0.f, ly = known ? L0.y - ooy : 0.f, lz = known ? L0.z - ooz : 0.f;
-                const float mag = sqrtf(lx * lx + ly * ly + lz * lz);
-                div3_exact(lx, ly, lz, mag);
-                bool occ = false;
-                if (A.shadows) {
-                    // Scene::DoesHit (Scene.cpp:68-96) on Ray{originOffset, l, 1e-4, |l|} with `hitmask` for
-                    // `active`; `live` = lanes still without an occluder
-                    unsigned long long sslow;
-                    const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, 0.0001f, mag, sslow);
-                    sslow |= ballot(!finite3(sr.ox, sr.oy, sr.oz));
-                    const bool s_slab_fast = (hitmask & sslow) == 0;
-                    const bool s_tri_dom = fmaxf(fmaxf(fabsf(sr.dx), fabsf(sr.dy)), fabsf(sr.dz)) <= 1.f &&
-                                           fmaxf(fmaxf(fabsf(sr.ox), fabsf(sr.oy)), fabsf(sr.oz)) <= 0x1p40f;
-                    const bool sfast = s_slab_fast && S.tri_fast && (hitmask & ~ballot(s_tri_dom)) == 0;
-                    const int soct = (sfast && S.oct_bytes) ? batch_octant(sr, hitmask) : -1;
-                    unsigned long long live = hitmask;
-                    for (uint32_t k = 0; k < S.n_spheres * 16u; k += 16u) {
-                        const float4 s = ldcb16(S.spheres, opaque(k));
-                        const SphereProj p = sphere_perp(s, sr);
-                        const unsigned long long near = ballot(!(s.w < p.perp)) & live;
-                        if (!near) continue;
-                        const float t = sphere_t(s, p);
-                        live &= ~(near & ballot(!(t < sr.tmin)) & ballot(!(t > sr.tmax)));
-                    }
-                    // (tmin = 1e-4 > 0: plane_cand's domain is a finite tmax = |l| in every hit lane)
-                    const bool pl_dom = (hitmask & ~ballot(sr.tmin > 0.f && fabsf(sr.tmax) < INFINITY)) == 0;
-                    if (pl_dom) {
-                        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
-                            float4 p0, p1;
-                            ldcb32(S.planes, opaque(k), p0, p1);
-                            const float num = plane_num(p0, p1, sr), den = plane_den(p1, sr);
-                            const unsigned long long cand = plane_cand(num, den, sr.tmax) & live;
-                            if (!cand) continue;   // also taken once no lane is live
-                            const float t = num / den;
-                            live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax) & cand);
-                        }
-                    } else {
-                        for (uint32_t k = 0; k < S.n_planes * 32u; k += 32u) {
-                            float4 p0, p1;
-                            ldcb32(S.planes, opaque(k), p0, p1);
-                            const float t = plane_num(p0, p1, sr) / plane_den(p1, sr);
-                            live &= ~(ballot(t >= sr.tmin) & ballot(t < sr.tmax));
-                        }
-                    }
-                    for (uint32_t mi = 0; mi < S.n_meshes; ++mi) {
-                        if (!live) break;
-                        float st = 0.f;
-                        uint32_t stri = 0;
-                        const int4 M = ldcb16i(S.meshes, opaque(mi * 16u));
-                        if (soct >= 0)
-                            mesh_traverse<true, kSlabOct, false>(S, M, sr, soct, live, lane, stk, nullptr, st, stri, live, cnt);
-                        else if (sfast)
-                            mesh_traverse<true, kSlabFast, false>(S, M, sr, 0, live, lane, stk, nullptr, st, stri, live, cnt);
-                        else if (s_slab_fast)
-                            mesh_traverse<true, kSlabFast, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
-                                                                                      st, stri, live, cnt);
-                        else
-                            mesh_traverse<true, kSlabExact, false, false, false, true>(S, M, sr, 0, live, lane, stk, nullptr,
-                                                                                       st, stri, live, cnt);
-                    }
-                    occ = did & !((live >> lane) & 1ull);
-                }
-                if (!did) continue;
-                if (occ) {
-                    shadowFactor *= 0.95f;
-                    continue;
-                }
-                if (mode == RTX_MODE_COMBINED || mode == RTX_MODE_RADIANCE) {
-                    // LightUtils::GetRadiance (Utils.h:355-369) at hit.origin
-                    float s = 0.f;
-                    bool any = true;
-                    if (ltype == RTX_LIGHT_POINT) {
-                        const float ex = L0.x - hx, ey = L0.y - hy, ez = L0.z - hz;
-                        s = L1.w / (ex * ex + ey * ey + ez * ez);
-                    } else if (ltype == RTX_LIGHT_DIRECTIONAL) {
-                        s = L1.w;
-                    } else {
-                        any = false;
-                    }
-                    const float rr = any ? L1.x * s : 0.f, rg = any ? L1.y * s : 0.f, rb = any ? L1.z * s : 0.f;
-                    if (mode == RTX_MODE_RADIANCE) {
-                        fr += rr; fg += rg; fb += rb;
-                    } else {
-                        const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
-                        const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
-                        fr += (rr * oa) * br.r; fg += (rg * oa) * br.g; fb += (rb * oa) * br.b;
-                    }
-                } else if (mode == RTX_MODE_OBSERVED_AREA) {
-                    const float oa = smax(nx * lx + ny * ly + nz * lz, 0.f);
-                    fr += oa; fg += oa; fb += oa;
-                } else if (mode == RTX_MODE_BRDF) {
-                    const RGB br = shade<0>(S, mat, nx, ny, nz, lx, ly, lz, vx, vy, vz, cnt, false);
-                    fr += br.r; fg += br.g; fb += br.b;
-                }
-            }
-            if (did) { fr *= shadowFactor; fg *= shadowFactor; fb *= shadowFactor; }
-        }
-        // ColorRGB::MaxToOne (ColorRGB.h:12-17)
-        const float mv = smax(fr, smax(fg, fb));
-        if (mv > 1.f) { fr /= mv; fg /= mv; fb /= mv; }
+        const Closest c = closest_hit(S, r, w, active, valid, lane, stk, cnt);
+        const HitRec h = hit_record<true>(S, r, c);
+        float fr, fg, fb;
+        light_loop(S, r, h, c.kind != 0, A.mode, A.shadows, lane, stk, cnt, fr, fg, fb);
 
         // ---- the box filter: the sx tree, then the sy tree, times the exact 1 / (k * k)
         ss_add_xor3<1>(fr, fg, fb);
@@ -2388,8 +2093,8 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
             ss_add_xor3<16>(fr, fg, fb);
             ss_add_xor3<32>(fr, fg, fb);
         }
-        const float w = __uint_as_float((127u - 2u * n) << 23);   // 2^(-2 log2 k)
-        fr *= w; fg *= w; fb *= w;
+        const float wgt = __uint_as_float((127u - 2u * n) << 23);   // 2^(-2 log2 k)
+        fr *= wgt; fg *= wgt; fb *= wgt;
         // the pixel's sample 0 stores; its list entry is read again from an opaque copy of the lane index,
         // so that neither it nor the sample coordinates stay in registers through the body above
         uint32_t l2 = lane;

@@ -45,11 +45,13 @@ uint32_t launch_rays(const rtx_ctx* c) {
     return chunk;
 }
 
-// Queue the launches of one query on the context stream, behind the last frame's split chain like the
-// hit pass; nothing of the frames' state is read or written.  A large n is cut into launches of at most
-// kQueryChunkRays rays, and with HBM stacks into launches whose stacks stay below kQueryStackBytes.
-int query_launch(rtx_ctx* c, bool any, QueryArgs Q) {
-    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+// Queue the launches of one call over the rays of `Q` (QueryArgs or ShadeArgs) on the context stream,
+// behind the last frame's split chain like the hit pass; nothing of the frames' state is read or written.
+// A large n is cut into launches of at most kQueryChunkRays rays, and with HBM stacks into launches whose
+// stacks stay below kQueryStackBytes: launch(deep, hstk, grid, Q) queues one of Q.n rays, and
+// advance(Q, n) moves Q's output pointers n rays on (the rays move here).
+template <class Args, class Launch, class Advance>
+int chunk_launch(rtx_ctx* c, Args Q, Launch launch, Advance advance) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = join_split(c); rc != RTX_OK) return rc;
     const uint32_t chunk = launch_rays(c);
@@ -62,39 +64,38 @@ int query_launch(rtx_ctx* c, bool any, QueryArgs Q) {
             if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
         }
         Q.n = n;
-        launch_query(any, c->facts.deep_stack || c->facts.hbm_stack, c->facts.hbm_stack, grid, c->stream, c->dev, Q);
+        launch(c->facts.deep_stack || c->facts.hbm_stack, c->facts.hbm_stack, grid, Q);
         HIP_TRY(c, hipGetLastError());
         Q.rays += static_cast<size_t>(n) * 8u;
-        if (Q.depth) Q.depth += n;
-        if (Q.normal) Q.normal += static_cast<size_t>(n) * 3u;
-        if (Q.material) Q.material += n;
-        if (Q.primitive) Q.primitive += n;
-        if (Q.occ) Q.occ += n;
+        advance(Q, n);
     }
     return RTX_OK;
 }
 
-// The same for a shade call (rtx_shade_kernel): the two output pointers advance by n and 3n.
-int shade_launch(rtx_ctx* c, ShadeArgs Q) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (const int rc = join_split(c); rc != RTX_OK) return rc;
-    const uint32_t chunk = launch_rays(c);
-    const uint32_t total = Q.n;
-    for (uint32_t first = 0; first < total; first += chunk) {
-        const uint32_t n = std::min(chunk, total - first);
-        const uint32_t waves = (n + 63u) / 64u;
-        const dim3 grid((waves + kWavesPerBlock - 1u) / kWavesPerBlock);
-        if (c->facts.hbm_stack) {
-            if (const int rc = ensure_hbm_stacks(c, grid.x); rc != RTX_OK) return rc;
-        }
-        Q.n = n;
-        launch_shade(c->facts.deep_stack || c->facts.hbm_stack, c->facts.hbm_stack, grid, c->stream, c->dev, Q);
-        HIP_TRY(c, hipGetLastError());
-        Q.rays += static_cast<size_t>(n) * 8u;
-        if (Q.out_px) Q.out_px += n;
-        if (Q.out_rgb) Q.out_rgb += static_cast<size_t>(n) * 3u;
-    }
-    return RTX_OK;
+int query_launch(rtx_ctx* c, bool any, const QueryArgs& Q) {
+    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
+    return chunk_launch(
+        c, Q,
+        [&](bool deep, bool hstk, dim3 grid, const QueryArgs& q) {
+            launch_query(any, deep, hstk, grid, c->stream, c->dev, q);
+        },
+        [](QueryArgs& q, uint32_t n) {
+            if (q.depth) q.depth += n;
+            if (q.normal) q.normal += static_cast<size_t>(n) * 3u;
+            if (q.material) q.material += n;
+            if (q.primitive) q.primitive += n;
+            if (q.occ) q.occ += n;
+        });
+}
+
+int shade_launch(rtx_ctx* c, const ShadeArgs& Q) {
+    return chunk_launch(
+        c, Q,
+        [&](bool deep, bool hstk, dim3 grid, const ShadeArgs& q) { launch_shade(deep, hstk, grid, c->stream, c->dev, q); },
+        [](ShadeArgs& q, uint32_t n) {
+            if (q.out_px) q.out_px += n;
+            if (q.out_rgb) q.out_rgb += static_cast<size_t>(n) * 3u;
+        });
 }
 
 // A shade call's checks, in the order of the error table (rtx.h); the lighting mode and the pixel
