@@ -189,7 +189,9 @@ extern "C" int rtx_anim_create(rtx_anim** out, rtx_ctx* c, const rtx_scene* s, c
     a->dev = rebase(c->dev, base, nullptr);
     // every animated triangle keeps |e1| |e2| within a rounding of its registration value
     // (a rotation): FAST Moller-Trumbore only with a factor-2 margin below its 2^56 bound
-    a->dev.tri_fast = P.max_ee <= 0x1p55 ? 1u : 0u;
+    // (max_se: the static meshes' share of the bound on the cross-product terms; an animated mesh's v0 and
+    // edges are bounded per update through `e` in rtx_anim_update, far below it: the factor 4 is to spare)
+    a->dev.tri_fast = (P.max_ee <= 0x1p55 && P.max_se <= 0x1p124) ? 1u : 0u;
     a->reg_fast = a->dev.tri_fast != 0;
     a->facts = c->facts;   // (deep_stack and hbm_stack false: refused above)
     for (uint32_t i = 0; i < n; ++i) {

@@ -720,8 +720,11 @@ __device__ void mesh_traverse(const DevScene& S, const int4 M, const Ray& r, int
         }
     }
     if (m == 0) return;
+    // The exact walk is where every ray outside the reduced cross products' domain ends up (a slow lane, a
+    // scene that is not tri_fast), a frame's as well as a query's: it takes Vector3::Cross as written.
+    constexpr bool XCE = XC || (SLAB == kSlabExact && !COUNT && !RTX_STAMPS_WALK);
     if ((!COUNT || CULL) && !RTX_STAMPS_WALK)
-        bvh_walk_lean<ANY, OCT ? kSlabOct : (FAST ? kSlabFast : kSlabExact), CB, CULL, COUNT, XC>(
+        bvh_walk_lean<ANY, OCT ? kSlabOct : (FAST ? kSlabFast : kSlabExact), CB, CULL, COUNT, XCE>(
             S, nb, cull_sign(M.z, ANY), r, __float_as_uint(b1.z), __float_as_uint(b1.w), m, mask, lane, stk, sc_t,
             sc_tri, live, nullptr, 0u, cq, &cnt);
     else
@@ -782,8 +785,9 @@ __device__ unsigned long long part_traverse(const DevScene& S, const int4 E, con
     // (read unconditionally: a `timed` test here made the compiler version the walk loop)
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
     if (!RTX_STAMPS_WALK)
-        bvh_walk_lean<ANY, SLAB, CB, CULL>(S, nb, cull_sign(M.z, ANY), r, link, ntri, m, mask, lane, stk, sc_t,
-                                           sc_tri, live, occ_word, occ_bit, cq);
+        bvh_walk_lean<ANY, SLAB, CB, CULL, false, SLAB == kSlabExact>(S, nb, cull_sign(M.z, ANY), r, link, ntri, m, mask,
+                                                                      lane, stk, sc_t, sc_tri, live, occ_word, occ_bit,
+                                                                      cq);   // (the exact walk: cross products as written)
     else
         bvh_walk<ANY, FAST, false>(S, cull_sign(M.z, ANY), r, link, ntri, m, mask, lane, stk, nullptr, sc_t, sc_tri,
                                    live, cnt, occ_word, occ_bit);

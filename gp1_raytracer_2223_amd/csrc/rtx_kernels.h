@@ -144,7 +144,8 @@ struct DevScene {
     const int4* __restrict__ parts;
     uint32_t n_spheres, n_planes, n_meshes, n_lights, n_materials, n_tris, n_nodes, n_parts;
     // every triangle has |e1| * |e2| <= 2^56: with |d| < 2, Moller-Trumbore's determinant
-    // stays inside the exact fast-reciprocal domain (rtx_fastdiv.h)
+    // stays inside the exact fast-reciprocal domain (rtx_fastdiv.h); and (|v0|_1 + 2^40) (|e1|_1 + |e2|_1)
+    // <= 2^126, so that no term of the ray kernels' reduced cross products overflows (rtx_pack.cpp)
     uint32_t tri_fast;
     // Byte stride between the 8 octant copies of the node array (0: no copies, the octant
     // slab path is off).  Copy k swaps the axes whose bit is set in k (the axes a ray of

@@ -189,6 +189,7 @@ int pack_prims(const rtx_scene* s, const PackOptions& opt, PackedScene& P, Work&
 int pack_tris(const rtx_mesh& m, uint32_t ntri, PackedScene& P, Work& W, std::string& err) {
     std::vector<float4>& tri = P.tri;
     double max_ee = P.max_ee, max_ee2_lo = W.max_ee2_lo;   // (locals: the loop's stores cannot alias them)
+    double max_se = P.max_se;
     double bmin[3] = {P.bmin[0], P.bmin[1], P.bmin[2]}, bmax[3] = {P.bmax[0], P.bmax[1], P.bmax[2]};
     const bool boxes = W.cull_want && !W.reuse_worth;
     for (uint32_t k = 0; k < ntri; ++k) {
@@ -216,6 +217,12 @@ int pack_tris(const rtx_mesh& m, uint32_t ntri, PackedScene& P, Work& W, std::st
             max_ee = (ee > max_ee || ee != ee) ? ee : max_ee;   // NaN sticks
             max_ee2_lo = max_ee * max_ee * (1.0 - 0x1p-40);
         }
+        // (|v0|_1 + 2^40) (|e1|_1 + |e2|_1) bounds every product of the cross products (o - v0) x e1
+        // and d x e2 for |o_k| <= 2^40, |d_k| <= 1; sums, not maxima: a NaN or inf coordinate sticks
+        const double se = (std::fabs(double(v0[0])) + std::fabs(double(v0[1])) + std::fabs(double(v0[2])) + 0x1p40) *
+                          (std::fabs(double(e1.x)) + std::fabs(double(e1.y)) + std::fabs(double(e1.z)) +
+                           std::fabs(double(e2.x)) + std::fabs(double(e2.y)) + std::fabs(double(e2.z)));
+        max_se = (se > max_se || se != se) ? se : max_se;
         tri.push_back(f4(bits(m.material), 0.f, 0.f, 0.f));
         for (int a = 0; a < 3; ++a) {
             const float lo = std::fmin(v0[a], std::fmin(v1[a], v2[a])), hi = std::fmax(v0[a], std::fmax(v1[a], v2[a]));
@@ -225,6 +232,7 @@ int pack_tris(const rtx_mesh& m, uint32_t ntri, PackedScene& P, Work& W, std::st
         }
     }
     P.max_ee = max_ee;
+    P.max_se = max_se;
     W.max_ee2_lo = max_ee2_lo;
     for (int a = 0; a < 3; ++a) { P.bmin[a] = bmin[a]; P.bmax[a] = bmax[a]; }
     return RTX_OK;
@@ -515,7 +523,7 @@ void layout(const rtx_scene* s, const PackOptions& opt, PackedScene& P) {
     P.n_spheres = s->n_spheres; P.n_planes = s->n_planes; P.n_meshes = s->n_meshes;
     P.n_lights = s->n_lights; P.n_materials = s->n_materials;
     P.n_tris = static_cast<uint32_t>(P.tri.size() / 4); P.n_nodes = static_cast<uint32_t>(P.nodes.size() / 2);
-    P.tri_fast = P.max_ee <= 0x1p56 ? 1u : 0u;
+    P.tri_fast = (P.max_ee <= 0x1p56 && P.max_se <= 0x1p126) ? 1u : 0u;
     P.oct_bytes = (P.oct_ok && !opt.no_octant) ? static_cast<uint32_t>(P.node_bytes) : 0u;
     P.cull_stride = P.node_bytes;
     if (P.cull_on && (P.cull_stride >= (1ull << 32) || 2 * P.tri.size() >= (1ull << 32))) P.cull_on = false;

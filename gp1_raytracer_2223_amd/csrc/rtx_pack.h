@@ -93,6 +93,7 @@ struct PackedScene {
     struct MeshLayout { uint32_t tri0 = 0, root = 0, part0 = 0, part_cap = 0; int depth = 0; };
     std::vector<MeshLayout> mesh_layout;
     double max_ee = 0.0;           // max |e1| * |e2| over the triangles (DevScene::tri_fast)
+    double max_se = 0.0;           // max (|v0|_1 + 2^40) (|e1|_1 + |e2|_1): bounds every |o - v0| x e term (tri_fast)
 };
 
 // Pack `s`.  RTX_OK, or the refusal's code with its reason in `err` (`out` is then unspecified).

@@ -22,6 +22,7 @@
 //   bench  <name> <t|-1> <W> <H> <threads> <frames> [mode shadows]   -> one JSON line
 //   obj    <path> <out>                             Utils::ParseOBJ result
 //   prims  <seed> <n> <out>                         primitive known-answer vectors
+//   primrows <in> <out>                             the same for caller-supplied rows
 // Scenes are constructed with cwd = the directory holding Resources/*.obj.
 
 #include <algorithm>
@@ -586,6 +587,64 @@ static void dump_prims(uint32_t seed, int n, const char* out) {
     w.i32("shade_kind", shade_kind); w.f32("shade_in", shade_in); w.f32("shade_out", shade_out);
 }
 
+// The same tests for rows the caller supplies (tests/walk_domains.py: operands at the edges of the
+// kernels' fast-path domains).  <in> is raw binary32, 34 floats a row: ray (origin, direction, min,
+// max), triangle v0 v1 v2, cull mode (0, 1 or 2), box min max, plane origin normal, sphere origin
+// radius.  The output has dump_prims' arrays but for the shading vectors; the triangle's normal is the
+// one the reference's constructor computes.
+static void dump_prim_rows(const char* in, const char* out) {
+    std::vector<float> rows;
+    {
+        FILE* f = std::fopen(in, "rb");
+        if (!f) { std::perror(in); std::exit(2); }
+        float buf[34];
+        while (std::fread(buf, sizeof(float), 34, f) == 34) rows.insert(rows.end(), buf, buf + 34);
+        std::fclose(f);
+    }
+    Writer w(out);
+    std::vector<float> rays, sph, pl, tri, aabb, res_s, res_p, res_t;
+    std::vector<int32_t> cull;
+    std::vector<uint8_t> any_s, any_p, any_t, slab;
+    auto v3 = [](const float* p) { return Vector3{p[0], p[1], p[2]}; };
+    for (size_t i = 0; i + 34 <= rows.size(); i += 34) {
+        const float* r = rows.data() + i;
+        Ray ray{v3(r), v3(r + 3), r[6], r[7]};
+        rays.insert(rays.end(), r, r + 8);
+
+        Triangle t{v3(r + 8), v3(r + 11), v3(r + 14)};
+        t.cullMode = static_cast<TriangleCullMode>(static_cast<int>(r[17]));
+        t.materialIndex = 5;
+        push3(tri, t.v0); push3(tri, t.v1); push3(tri, t.v2); push3(tri, t.normal);
+        cull.push_back(static_cast<int>(r[17]));
+        HitRecord ht{};
+        bool hit = GeometryUtils::HitTest_Triangle(t, ray, ht);
+        res_t.push_back(hit ? 1.f : 0.f); res_t.push_back(ht.t); push3(res_t, ht.origin); push3(res_t, ht.normal);
+        any_t.push_back(GeometryUtils::HitTest_Triangle(t, ray) ? 1 : 0);
+
+        aabb.insert(aabb.end(), r + 18, r + 24);
+        slab.push_back(GeometryUtils::SlabTest_BVH(v3(r + 18), v3(r + 21), ray) ? 1 : 0);
+
+        Plane p; p.origin = v3(r + 24); p.normal = v3(r + 27); p.materialIndex = 3;
+        pl.insert(pl.end(), r + 24, r + 30);
+        HitRecord hp{};
+        hit = GeometryUtils::HitTest_Plane(p, ray, hp);
+        res_p.push_back(hit ? 1.f : 0.f); res_p.push_back(hp.t); push3(res_p, hp.origin); push3(res_p, hp.normal);
+        any_p.push_back(GeometryUtils::HitTest_Plane(p, ray) ? 1 : 0);
+
+        Sphere s; s.origin = v3(r + 30); s.radius = r[33]; s.materialIndex = 7;
+        sph.insert(sph.end(), r + 30, r + 34);
+        HitRecord hs{};
+        hit = GeometryUtils::HitTest_Sphere(s, ray, hs);
+        res_s.push_back(hit ? 1.f : 0.f); res_s.push_back(hs.t); push3(res_s, hs.origin); push3(res_s, hs.normal);
+        any_s.push_back(GeometryUtils::HitTest_Sphere(s, ray) ? 1 : 0);
+    }
+    w.f32("rays", rays); w.f32("spheres", sph); w.f32("planes", pl); w.f32("triangles", tri);
+    w.i32("tri_cull", cull);
+    w.f32("sphere_hit", res_s); w.f32("plane_hit", res_p); w.f32("tri_hit", res_t);
+    w.u8("sphere_any", any_s); w.u8("plane_any", any_p); w.u8("tri_any", any_t);
+    w.f32("aabbs", aabb); w.u8("slab", slab);
+}
+
 static void dump_obj(const char* path, const char* out) {
     std::vector<Vector3> positions, normals;
     std::vector<int> indices;
@@ -600,7 +659,7 @@ static void dump_obj(const char* path, const char* out) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: ref_harness scene|render|bench|obj|prims ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: ref_harness scene|render|bench|obj|prims|primrows ...\n"); return 2; }
     const std::string cmd = argv[1];
     if (cmd == "scene" && argc == 5) {
         auto s = make_scene(argv[2]);
@@ -652,6 +711,7 @@ int main(int argc, char** argv) {
     }
     if (cmd == "obj" && argc == 4) { dump_obj(argv[2], argv[3]); return 0; }
     if (cmd == "prims" && argc == 5) { dump_prims(static_cast<uint32_t>(std::atoi(argv[2])), std::atoi(argv[3]), argv[4]); return 0; }
+    if (cmd == "primrows" && argc == 4) { dump_prim_rows(argv[2], argv[3]); return 0; }
     std::fprintf(stderr, "bad arguments\n");
     return 2;
 }

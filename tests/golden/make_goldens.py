@@ -14,6 +14,8 @@ the reference's own functions:
   config_<name>_<W>x<H>.npz   full-resolution BASELINE configs: SHA-256 of the uint32
                         frame and of the float RGB plane + 4096 seeded sample pixels (index, uint32, rgb)
   prims.npz             primitive / BRDF known-answer vectors (GeometryUtils, Material::Shade)
+  prims_domains.npz     the same primitives on the rows of tests/walk_domains.py (prim_rows): operands at the
+                        edges of the ray kernels' fast-path domains
   scene_file_<stem>[_t].npz, frame_file_<stem>_128x72_m<mode>s<sh>[_t].npz
                         the same for the scene files in scenes/*.rtxscene, built by the
                         harness with the reference's own classes
@@ -24,7 +26,7 @@ the reference's own functions:
                         of the case's Update list, shape facts of the reference's trees (nodes, largest
                         leaf, depth, inf and -0 words) and its 44x28 frames, modes (3,1), (0,1)
 
-Usage:  python tests/golden/make_goldens.py [--scene-files-only | --configs-only | --fuzz-only]
+Usage:  python tests/golden/make_goldens.py [--scene-files-only | --configs-only | --fuzz-only | --prims-domains-only]
 
 """
 from __future__ import annotations
@@ -114,11 +116,25 @@ def fuzz() -> None:
         print("fuzz", fs.name, flush=True)
 
 
+def prims_domains() -> None:
+    """tests/walk_domains.py's rows through the reference's own HitTest_* and SlabTest_BVH."""
+    sys.path.insert(0, str(HERE.parent))
+    import walk_domains
+    with tempfile.TemporaryDirectory() as td:
+        rows = Path(td) / "rows.f32"
+        walk_domains.prim_rows().tofile(rows)
+        d = run("primrows", rows)
+    np.savez_compressed(HERE / "prims_domains.npz", **d)
+
+
 def main() -> None:
     if "--fuzz-only" in sys.argv:
         fuzz()
         return
     assert HARNESS.exists(), "build oracle/_ref first (python -m gp1_raytracer_2223_amd.build)"
+    if "--prims-domains-only" in sys.argv:
+        prims_domains()
+        return
     if "--scene-files-only" in sys.argv:
         scene_files()
         return
@@ -150,6 +166,7 @@ def main() -> None:
 
     d = run("prims", 1234, 1500)
     np.savez_compressed(HERE / "prims.npz", **d)
+    prims_domains()
 
 
 def configs() -> None:

@@ -1,5 +1,8 @@
 """Known-answer vectors of the reference's primitive functions (GeometryUtils::HitTest_*,
-SlabTest_BVH, Material::Shade), captured from the reference build, against the oracle."""
+SlabTest_BVH, Material::Shade), captured from the reference build, against the oracle: seeded ordinary
+operands (prims.npz: origins in +-3, unit directions) and the rows of tests/walk_domains.py at the edges
+of the ray kernels' fast-path domains (prims_domains.npz: directions of 2^+-60, origins of 2^40 to 2^120,
+triangles with |e1||e2| = 2^56, where Vector3::Cross's `0 *` terms turn an infinity into NaN)."""
 from pathlib import Path
 
 import ctypes as C
@@ -21,7 +24,16 @@ def _eq(a, b):
     return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-def test_sphere_plane_triangle_slab():
+def _eq_nan(a, b):
+    """Bit for bit, a NaN equal to any NaN (x86 and the reference build may differ in NaN payloads)."""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def _hold(G, _eq):
+    """The oracle's four primitive tests, closest and any, against the vectors of G under _eq."""
+    def _rows(name, w):
+        return G[name].reshape(-1, w).astype(np.float32)
     L = oracle_bind.lib()
     rays, sph, pl, tri = _rows("rays", 8), _rows("spheres", 4), _rows("planes", 6), _rows("triangles", 12)
     cull, aabb = G["tri_cull"], _rows("aabbs", 6)
@@ -49,6 +61,29 @@ def test_sphere_plane_triangle_slab():
     # the vectors exercise both outcomes of every test
     for k in ("sphere_any", "plane_any", "tri_any", "slab"):
         assert 0 < G[k].sum() < len(G[k]), k
+
+
+def test_sphere_plane_triangle_slab():
+    _hold(G, _eq)
+
+
+def test_the_same_at_the_edges_of_the_fast_path_domains():
+    """prims_domains.npz is what the reference answers on walk_domains.prim_rows(): the rows are the
+    committed ones, some triangle hits carry the NaN t that Vector3::Cross's `0 *` terms make, and the
+    oracle answers the same everywhere, bit for bit with a NaN equal to any NaN."""
+    import walk_domains
+    D = np.load(Path(__file__).resolve().parent / "golden" / "prims_domains.npz")
+    rows = walk_domains.prim_rows()
+    assert 200 <= rows.shape[0] <= 600
+    assert _eq(D["rays"].reshape(-1, 8), rows[:, 0:8]) and _eq(D["triangles"].reshape(-1, 12)[:, 0:9], rows[:, 8:17])
+    assert np.array_equal(D["tri_cull"], rows[:, 17].astype(np.int32)) and set(D["tri_cull"].tolist()) == {0, 1, 2}
+    assert _eq(D["aabbs"].reshape(-1, 6), rows[:, 18:24]) and _eq(D["planes"].reshape(-1, 6), rows[:, 24:30])
+    assert _eq(D["spheres"].reshape(-1, 4), rows[:, 30:34])
+    th = D["tri_hit"].reshape(-1, 8)
+    nan_hits = (th[:, 0] == 1) & np.isnan(th[:, 1])
+    assert nan_hits.sum() >= 8 and np.isnan(th[nan_hits, 2:5]).all()
+    assert ((th[:, 0] == 1) & np.isfinite(th[:, 1])).sum() >= 50
+    _hold(D, _eq_nan)
 
 
 def test_shade_materials():

@@ -1,0 +1,289 @@
+"""The conditions that keep tests/test_gpu_walk_domains.py honest, on the CPU: the scenes of
+tests/walk_domains.py are what they claim (the packer's tri_fast and octant copies), every ray class
+hits triangles and is neither always nor never occluded in the checker, the NaN-occluder class really is
+one, the committed sets take each of the four walks and both plane forms by the model, both sides of
+every threshold are present, and in every mixed wave the single lane changes the walk."""
+from collections import Counter
+
+import numpy as np
+import pytest
+
+import aov_ref
+import pack_cases as PC
+import rayq_ref
+import walk_domains as WD
+from test_pack_cpu import build_harness, parse, run_harness
+
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    return rayq_ref.build(tmp_path_factory.mktemp("rayq_ref"))
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    return build_harness(tmp_path_factory.mktemp("pack"))
+
+
+@pytest.fixture(scope="module")
+def folder(tmp_path_factory):
+    return tmp_path_factory.mktemp("wd_scenes")
+
+
+_scenes = {}
+
+
+def _scene(folder, name, cull):
+    if (name, cull) not in _scenes:
+        _scenes[(name, cull)] = WD.host_scene(WD.GEO[name], cull, folder)
+    return _scenes[(name, cull)][1:]
+
+
+def test_pack_facts(folder, harness):
+    """tri_fast is 1 for unit, giant (|e1||e2| = 2^56 exactly) and sliver and 0 for over, one float
+    above; every scene gets its octant copies."""
+    exe = harness
+    script, want = [], {}
+    for name, cull in WD.SCENES:
+        path = WD.write_scene(WD.GEO[name], cull, folder)
+        script.append(f"scene {name}_{cull} file:{path} {path.parent}")
+        want[f"{name}_{cull}"] = WD.GEO[name]
+    got = {d["label"]: d for d in map(parse, run_harness(exe, script))}
+    assert sorted(got) == sorted(want)
+    for label, geo in want.items():
+        assert int(got[label]["tri_fast"]) == int(geo.tri_fast) == int(geo.name != "over"), label
+        assert int(got[label]["oct_bytes"]) > 0, label
+        assert got[label]["sig"].split("/")[3] == str(WD.N_TRI), label
+        assert WD.facts(geo) == {"tri_fast": bool(int(got[label]["tri_fast"])), "oct": True}
+    s, _ = _scene(folder, "giant", "none")
+    assert PC.max_edge_product(s) == 2.0 ** 56
+    s, _ = _scene(folder, "over", "none")
+    assert PC.max_edge_product(s) == 2.0 ** 56 * (1 + 2.0 ** -23)
+    s, _ = _scene(folder, "sliver", "back")
+    assert PC.max_edge_product(s) == 2.0 ** 56
+
+
+@pytest.mark.parametrize("cls", sorted(WD.CLASSES))
+def test_every_class_hits_and_is_sometimes_occluded(checker, folder, cls):
+    """On its intended scenes, none-culled and back-culled, a class has a triangle-hit share (closest hit
+    finds a triangle) of at least 0.2 and an occlusion share in [0.1, 0.9].  Beyond that, the same holds
+    for its outside rays alone, where for `far` a triangle's hit is also the NaN t that DoesHit alone
+    accepts (occluded while closest hit finds nothing: the plane cannot occlude those rays)."""
+    for name in WD.INTENDED[cls]:
+        geo = WD.GEO[name]
+        w_out, t_out = WD.outside_of(cls)
+        rays = np.concatenate([WD.waves(geo, cls), WD.tail(geo, cls)])
+        out = np.concatenate([w_out, 320 + t_out])
+        assert rays.shape[0] <= 2048
+        for cull in WD.CULLS:
+            s, _ = _scene(folder, name, cull)
+            kind = aov_ref.kind(rayq_ref.trace(checker, s, rays)["primitive"])
+            occ = rayq_ref.occluded(checker, s, rays) != 0
+            tri = kind == 3
+            assert tri.mean() >= 0.2, (name, cull, tri.mean())
+            assert 0.1 <= occ.mean() <= 0.9, (name, cull, occ.mean())
+            if cls == "far":
+                tri = tri | (occ & (kind == 0))
+            assert tri[out].mean() >= 0.2, (name, cull, "outside", tri[out].mean())
+            assert 0.1 <= occ[out].mean() <= 0.9, (name, cull, "outside", occ[out].mean())
+
+
+@pytest.mark.parametrize("name", ["giant", "over"])
+def test_the_nan_occluder_class_is_one(checker, folder, name):
+    """At least 0.25 of the far rays are occluded while closest hit finds no primitive: a NaN t that no
+    comparison rejects, DoesHit's answer and not GetClosestHit's."""
+    geo = WD.GEO[name]
+    s, _ = _scene(folder, name, "none")
+    w_out, t_out = WD.outside_of("far")
+    rays = np.concatenate([WD.waves(geo, "far")[w_out], WD.tail(geo, "far")[t_out]])
+    assert np.abs(rays[:, 0:3]).max(axis=1).min() >= 2.0 ** 70 and np.isfinite(rays[:, 7]).all()
+    kind = aov_ref.kind(rayq_ref.trace(checker, s, rays)["primitive"])
+    occ = rayq_ref.occluded(checker, s, rays)
+    share = ((occ == 1) & (kind == 0)).mean()
+    assert share >= 0.25, share
+
+
+def _walks(geo, rays):
+    return WD.walk_of(WD.facts(geo), rays)
+
+
+def test_every_walk_and_both_plane_forms_are_taken():
+    """By the model, over the whole sets and their prefixes 63 and 65."""
+    walks, forms = Counter(), Counter()
+    for name, geo in WD.GEO.items():
+        for key, rays in WD.all_sets(geo).items():
+            for n in (rays.shape[0], 63, 65):
+                for w, f in _walks(geo, rays[:n]):
+                    walks[w] += 1
+                    forms[f] += 1
+    assert sorted(walks) == sorted(WD.WALKS) and min(walks.values()) >= 4, walks
+    assert sorted(forms) == ["cand", "divide"] and min(forms.values()) >= 4, forms
+    # per scene: a tri_fast scene takes all four, `over` never the two that need tri_fast
+    for name, geo in WD.GEO.items():
+        seen = {w for rays in WD.all_sets(geo).values() for w, _ in _walks(geo, rays)}
+        assert seen == (set(WD.WALKS) if geo.tri_fast else {"xc", "exact"}), (name, seen)
+
+
+def test_both_sides_of_every_threshold_are_present():
+    two60, lo60, two40 = F32(2.0 ** 60), F32(2.0 ** -60), F32(2.0 ** 40)
+    for name, geo in WD.GEO.items():
+        def sides(cls):
+            w_out, _ = WD.outside_of(cls)
+            r = WD.waves(geo, cls)
+            return r[:64], r[w_out]
+        i, o = sides("dmax")
+        assert (np.abs(i[:, 3:6]).max(axis=1) == 1).all() and (np.abs(o[:, 3:6]).max(axis=1) == WD.up(1.0)).all()
+        i, o = sides("dsum")
+        s_in = (np.abs(i[:, 3]) + np.abs(i[:, 4])).astype(np.float32) + np.abs(i[:, 5])
+        s_out = (np.abs(o[:, 3]) + np.abs(o[:, 4])).astype(np.float32) + np.abs(o[:, 5])
+        assert (s_in == two60).all() and (s_out == WD.up(two60)).all() and (np.abs(o[:, 3:6]).max(axis=1) < two60).all()
+        i, o = sides("dsingle")
+        s_in = (np.abs(i[:, 3]) + np.abs(i[:, 4])).astype(np.float32) + np.abs(i[:, 5])
+        s_out = (np.abs(o[:, 3]) + np.abs(o[:, 4])).astype(np.float32) + np.abs(o[:, 5])
+        assert (s_in == two60).all() and (s_out > two60).all()
+        assert (np.abs(i[:, 5]) == two60).all() and (np.abs(o[:, 3:6]).max(axis=1) == two60).all()
+        i, o = sides("dmin")
+        assert (np.abs(i[:, 3:6]).min(axis=1) == lo60).all() and (np.abs(o[:, 3:6]).min(axis=1) == lo60 / 2).all()
+        i, o = sides("omax")
+        assert (np.abs(i[:, 0:3]).max(axis=1) == two40).all() and (np.abs(o[:, 0:3]).max(axis=1) == WD.up(two40)).all()
+        assert (np.abs(i[:, 3:6]).max(axis=1) <= 1).all() and (np.abs(o[:, 3:6]).max(axis=1) <= 1).all()
+        _, o = sides("far")
+        assert {int(np.log2(x)) for x in np.abs(o[:, 0:3]).max(axis=1)} == {70, 100, 120}
+        _, o = sides("big_a")
+        with np.errstate(over="ignore"):
+            a = np.abs(o[:, 5]) * F32(geo.a) * F32(geo.b)     # |a| = |d_z| a b for these triangles
+        assert (o[:, 6] == 0).any() and (o[:, 6] < 0).any() and (o[:, 6] <= 0).all()
+        if name != "unit":
+            assert ((a > two60) & (a <= F32(2.0 ** 126))).any() and ((a > F32(2.0 ** 126)) & np.isfinite(a)).any()
+            assert np.isinf(a).any()
+        i, o = sides("plane")
+        assert ((i[:, 6] > 0) & np.isfinite(i[:, 7])).all()
+        assert {(float(F32(t)), bool(f)) for t, f in zip(o[:, 6], np.isfinite(o[:, 7]))} == \
+            {(float(F32(t)), f) for t, f in WD.PLANE_FORMS if (t, f) != (1e-4, True)}
+        # the plane x = const lies in front of some of these rays and behind others
+        assert (o[:, 3] < 0).any() and (o[:, 3] > 0).any()
+
+
+@pytest.mark.parametrize("cls", sorted(WD.CLASSES))
+def test_the_single_lane_changes_the_walk(cls):
+    """In every mixed wave of a class on its intended scenes, the model's answer with the odd lane
+    active differs from its answer without it; and the tail set's rays 63 and 64 do the same for their
+    waves, while as inactive tail lanes they change nothing."""
+    for name in WD.INTENDED[cls]:
+        geo = WD.GEO[name]
+        rays = WD.waves(geo, cls)
+        for j, lane in enumerate(WD.MIXED_LANES):
+            wave = rays[128 + 64 * j:192 + 64 * j]
+            without = np.ones(64, bool)
+            without[lane] = False
+            assert _walks(geo, wave) != WD.walk_of(WD.facts(geo), wave, without), (name, cls, lane)
+        t = WD.tail(geo, cls)
+        assert _walks(geo, t[:64]) != _walks(geo, t[:63]), (name, cls)
+        assert _walks(geo, t[:65])[1] != _walks(geo, t[65:129])[0], (name, cls)
+
+
+FRAMES = [("giant", "none"), ("giant", "back"), ("over", "none"), ("sliver", "none"), ("needle", "none"),
+          ("needle", "back")]
+
+
+@pytest.fixture(scope="module")
+def relight_checker(tmp_path_factory):
+    import relight_ref
+    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
+
+
+@pytest.mark.parametrize("name,cull", FRAMES)
+def test_the_frames_are_not_flat(relight_checker, folder, name, cull):
+    """The 64 x 48 frame of a scene's camera hits triangles and misses them, has at least 3 distinct
+    colour words in both modes, and its point light is occluded in some hit pixels and not in others.
+    `needle`'s frame shows a plane, and the occluder of its far light is the triangle whose t is NaN: with
+    the reduced cross products (a copy of the oracle, by hand) the share is 0."""
+    import oracle_bind
+    import relight_ref
+    from gp1_raytracer_2223_amd import abi
+    lib = relight_checker
+    if name == "needle":
+        hs, s, cam = WD.needle_scene(cull, folder, True)
+        kind = aov_ref.kind(aov_ref.planes(lib, s, cam, 64, 48)["primitive"])
+        assert (kind == 2).all()
+    else:
+        s, cam = _scene(folder, name, cull)
+        kind = aov_ref.kind(aov_ref.planes(lib, s, cam, 64, 48)["primitive"])
+        assert (kind == 3).mean() >= 0.5 and (kind != 3).mean() >= 0.05
+    for mode in (abi.RTX_MODE_OBSERVED_AREA, abi.RTX_MODE_COMBINED):
+        px, _ = oracle_bind.render(s, cam, abi.make_params(64, 48, mode, 1))
+        assert len(np.unique(px)) >= 3, (name, mode)
+    bits, hit = relight_ref.plane(lib, s, cam, 64, 48)
+    assert 0.1 <= (bits[hit] & 1).mean() <= 0.9, (bits[hit] & 1).mean()
+
+
+@pytest.mark.parametrize("cull", WD.CULLS)
+def test_the_shaded_rays_straddle_the_origin_bound(checker, folder, cull):
+    """On `giant`, the rays onto the far plane all hit it; by the model some light's shadow wave takes the
+    reduced triangle test (octant or fast) and some the cross products as written, and the mixed waves
+    flip; the point light beyond the mesh is occluded for some hit points and not for others."""
+    geo = WD.GEO["giant"]
+    s, _ = _scene(folder, "giant", cull)
+    rays = WD.waves(geo, "onto_plane")
+    planes = rayq_ref.trace(checker, s, rays)
+    assert (aov_ref.kind(planes["primitive"]) == 2).all()
+    seen = set()
+    for light in range(s.n_lights):
+        sr, hit = WD.shadow_rays(s, rays, planes, light)
+        walks = [w for w, _ in WD.walk_of(WD.facts(geo), sr, hit)]
+        assert walks[0] in ("octant", "fast") and walks[1:] == ["xc"] * 4, (light, walks)
+        for j, lane in enumerate(WD.MIXED_LANES):
+            without = hit[128 + 64 * j:192 + 64 * j].copy()
+            without[lane] = False
+            assert WD.walk_of(WD.facts(geo), sr[128 + 64 * j:192 + 64 * j], without)[0][0] in ("octant", "fast")
+        seen |= set(walks)
+        if light == 0:
+            occ = rayq_ref.occluded(checker, s, sr)[hit]
+            assert 0.1 <= occ.mean() <= 0.9, occ.mean()
+    assert "xc" in seen and seen & {"octant", "fast"}
+
+
+def test_the_needle_scene_is_refused_tri_fast(checker, folder, harness):
+    """|e1||e2| is 2^56 exactly on `needle`, yet `(o - v0) x e1` overflows for every origin: the packer
+    says tri_fast = 0 (its bound on (|v0|_1 + 2^40) (|e1|_1 + |e2|_1)), so the model sends its rays, all
+    inside the ray domains, through the cross products as written; and the checker shows why: at least
+    0.25 of them are occluded by a triangle that closest hit cannot keep."""
+    exe = harness
+    script = []
+    for cull in WD.CULLS:
+        path = WD.write_needle(cull, folder)
+        script.append(f"scene needle_{cull} file:{path} {path.parent}")
+    for d in map(parse, run_harness(exe, script)):
+        assert int(d["tri_fast"]) == 0 and int(d["oct_bytes"]) > 0, d["label"]
+    rays = WD.needle_rays()
+    f = WD.lane_facts(rays)
+    assert f["tri_dom"].mean() >= 0.99 and (np.abs(rays[:, 0:3]) <= 2.0 ** 39).all()
+    assert {w for w, _ in WD.walk_of({"tri_fast": True, "oct": True}, rays)} >= {"octant", "fast"}   # but for the bound
+    assert {w for w, _ in WD.walk_of(WD.NEEDLE_FACTS, rays)} <= {"xc", "exact"}
+    for cull in WD.CULLS:
+        hs, s, _ = WD.needle_scene(cull, folder)
+        assert PC.max_edge_product(s) == 2.0 ** 56
+        kind = aov_ref.kind(rayq_ref.trace(checker, s, rays)["primitive"])
+        occ = rayq_ref.occluded(checker, s, rays)
+        assert ((occ == 1) & (kind == 0)).mean() >= 0.25 and 0.1 <= occ.mean() <= 0.9
+        del hs
+
+
+F32HEX = lambda x: f"{int(np.float32(x).view(np.uint32)):08x}"    # noqa: E731
+
+
+@pytest.mark.parametrize("what,a,b,want", [
+    ("at_bound", 2.0 ** 86, 2.0 ** -40, 1),                     # (0 + 2^40) (2^86 + 2^-40) = 2^126 in double
+    ("one_float_above", float(WD.up(2.0 ** 86)), 2.0 ** -40, 0),
+    ("well_below", 2.0 ** 60, 2.0 ** -10, 1),
+    ("inf_edge", float("inf"), 2.0 ** -40, 0),
+    ("nan_edge", float("nan"), 2.0 ** -40, 0)])
+def test_tri_fast_at_the_bound_on_the_cross_product_terms(harness, what, a, b, want):
+    """Triangles (0, 0, 0), (a, 0, 0), (0, b, 0) with |e1||e2| far below 2^56: tri_fast is decided by
+    (|v0|_1 + 2^40)(|e1|_1 + |e2|_1) <= 2^126 alone, at the bound, one binary32 of a above it, and with
+    an infinite or NaN coordinate (which either rule refuses)."""
+    assert not np.isfinite(a) or float(np.float32(a)) * float(np.float32(b)) <= 2.0 ** 56
+    (line,) = run_harness(harness, [f"scene {what} tris:{F32HEX(a)}.{F32HEX(b)} {PC.ASSETS}"])
+    assert int(parse(line)["tri_fast"]) == want
