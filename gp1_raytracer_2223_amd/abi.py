@@ -191,7 +191,9 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_render_shadows_async", "rtx_download_shadows", "rtx_gather_shadows_async",
                "rtx_device_shadow_buffer", "rtx_relight_async", "rtx_relight", "rtx_time_shadows", "rtx_time_relight",
                "rtx_update_shadows_async", "rtx_refresh_shadows_async", "rtx_time_shadows_update",
-               "rtx_relight_resolve_async", "rtx_relight_resolve", "rtx_time_relight_resolve"]
+               "rtx_relight_resolve_async", "rtx_relight_resolve", "rtx_time_relight_resolve",
+               "rtx_edit_lights", "rtx_edit_materials", "rtx_edit_light_values_device",
+               "rtx_edit_material_values_device"]
 
 
 def load_hip() -> C.CDLL:
@@ -390,6 +392,15 @@ def load_hip() -> C.CDLL:
             lib.rtx_refresh_shadows_async.argtypes = [VP, C.POINTER(C.c_uint32)]
             lib.rtx_time_shadows_update.argtypes = [VP, C.c_uint32, C.c_int, C.POINTER(C.c_float)]
             for n in ("rtx_update_shadows_async", "rtx_refresh_shadows_async", "rtx_time_shadows_update"):
+                getattr(lib, n).restype = C.c_int
+        if hasattr(lib, "rtx_edit_lights"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            # (the device forms take integer device addresses: void pointers)
+            lib.rtx_edit_lights.argtypes = [VP, C.c_uint32, C.c_uint32, C.POINTER(Light)]
+            lib.rtx_edit_materials.argtypes = [VP, C.c_uint32, C.c_uint32, C.POINTER(Material)]
+            lib.rtx_edit_light_values_device.argtypes = [VP, C.c_uint32, C.c_uint32, VP]
+            lib.rtx_edit_material_values_device.argtypes = [VP, C.c_uint32, C.c_uint32, VP]
+            for n in ("rtx_edit_lights", "rtx_edit_materials", "rtx_edit_light_values_device",
+                      "rtx_edit_material_values_device"):
                 getattr(lib, n).restype = C.c_int
         if hasattr(lib, "rtx_scene_image"):
             lib.rtx_scene_image.argtypes = [VP, VP, C.c_size_t, C.POINTER(C.c_size_t)]

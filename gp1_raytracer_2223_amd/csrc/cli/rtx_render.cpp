@@ -5,7 +5,7 @@
 //   rtx_render <scene> [width height] [--time T] [--mode 0..3] [--no-shadows]
 //              [--frames N] [--out file.bmp] [--assets dir] [--benchmark [windows]] [--inflight F]
 //              [--device-update] [--ss K] [--aov PREFIX] [--rays FILE] [--adaptive K,T] [--deferred] [--relight]
-//              [--resolve K] [--move-light L,X,Y,Z]...
+//              [--resolve K] [--move-light L,X,Y,Z]... [--in-place]
 //
 // --benchmark runs the reference's frame loop (main.cpp:86-100: Scene::Update with the
 // timer's total time, Render into the host pixel buffer, Timer::Update) under its F6
@@ -38,6 +38,8 @@
 // With --relight the hit pass and the full shadow pass run with the scene's ORIGINAL lights; then the moved scene is
 // uploaded, rtx_refresh_shadows_async re-traces only the moved lights, and the relight makes the image: the same
 // BMP as the plain run with the same moves, and with --aov the refreshed PREFIX_shadow.u32.
+// --in-place (only with --relight and --move-light) makes the move an edit of the uploaded scene (rtx_edit_lights)
+// instead of a second upload; the refresh and the image are the same.
 #include <algorithm>
 #include <array>
 #include <cfloat>
@@ -336,7 +338,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: %s <scene> [width height] [--time T] [--mode M] [--no-shadows] [--frames N] "
                              "[--out f.bmp] [--assets dir] [--benchmark [windows]] [--inflight F] [--device-update] [--ss K] "
                              "[--aov prefix] [--rays file] [--adaptive K,T] [--deferred] [--relight] [--resolve K] "
-                             "[--move-light L,X,Y,Z]...\n",
+                             "[--move-light L,X,Y,Z]... [--in-place]\n",
                      argv[0]);
         return 2;
     }
@@ -346,7 +348,7 @@ int main(int argc, char** argv) {
     int resolve = 0;          // --resolve K (0: not asked for)
     std::vector<float> seq;
     float t = -1.f;
-    bool shadows = true, device_update = false, deferred = false, relight = false;
+    bool shadows = true, device_update = false, deferred = false, relight = false, in_place = false;
     std::vector<std::pair<uint32_t, std::array<float, 3>>> moves;   // --move-light, in the order given
     int pos = 0;
     for (int i = 2; i < argc; ++i) {
@@ -367,6 +369,7 @@ int main(int argc, char** argv) {
         else if (a == "--device-update") device_update = true;
         else if (a == "--deferred") deferred = true;
         else if (a == "--relight") relight = true;
+        else if (a == "--in-place") in_place = true;
         else if (a == "--ss") {   // checked here: a bad factor ends the program before any device work
             ss = i + 1 < argc ? std::atoi(argv[++i]) : 0;
             if (ss != 1 && ss != 2 && ss != 4 && ss != 8) {
@@ -417,6 +420,10 @@ int main(int argc, char** argv) {
     if (relight && (deferred || bench || !seq.empty() || !rays_file.empty() || ad_k || ss > 1)) {   // before any device work
         std::fprintf(stderr, "--relight shades a single frame's hit pass and shadow pass: not with --deferred, --benchmark, "
                              "--sequence, --rays, --adaptive or --ss above 1\n");
+        return 2;
+    }
+    if (in_place && (!relight || moves.empty())) {   // before any device work
+        std::fprintf(stderr, "--in-place makes --relight's --move-light an edit of the uploaded scene: only with both\n");
         return 2;
     }
     if (resolve && (!relight || !aov.empty())) {   // before any device work
@@ -500,6 +507,12 @@ int main(int argc, char** argv) {
         }
         return v;
     };
+    // --relight's moved scene `s` onto the device: an upload, or with --in-place an edit of each moved light
+    auto move_lights = [&](rtx::Renderer& r, const rtx_scene& s) {
+        if (!in_place) return r.Upload(s);
+        for (const auto& m : moves) r.EditLights(m.first, {s.lights[m.first]});
+        std::printf("moved %zu light(s) in place\n", moves.size());
+    };
     int rc = 0;
     try {
         rtx::Renderer r(W, H);
@@ -546,7 +559,7 @@ int main(int argc, char** argv) {
                 rtx_scene s;
                 rtx_camera cam;
                 if (rtx_host_scene_view(hs, &s, &cam) != RTX_OK) throw std::runtime_error("rtx_host_scene_view failed");
-                r.Upload(s);
+                move_lights(r, s);
                 uint32_t traced = 0;
                 if (rtx_refresh_shadows_async(r.Context(), &traced) != RTX_OK)
                     throw std::runtime_error(std::string("rtx_refresh_shadows_async: ") + rtx_last_error(r.Context()));
@@ -564,7 +577,7 @@ int main(int argc, char** argv) {
                 rtx_scene s;
                 rtx_camera cam;
                 if (rtx_host_scene_view(hs, &s, &cam) != RTX_OK) throw std::runtime_error("rtx_host_scene_view failed");
-                r.Upload(s);
+                move_lights(r, s);
                 uint32_t traced = 0;
                 bits = r.RefreshShadows(&traced);
                 std::printf("refreshed the shadow plane: light mask 0x%x re-traced\n", traced);

@@ -326,6 +326,7 @@ extern "C" int rtx_anim_update(rtx_anim* a, rtx_ctx* c, const float* transforms)
     }
     c->dev.tri_fast = fast ? 1u : 0u;
     c->facts = a->facts;
+    c->edit_ok = false;   // (the Update's images are its registration's template: not edited in place)
     c->has_scene = true;
     ++c->scene_gen;
     return RTX_OK;

@@ -4,7 +4,7 @@
 // calls: the split tuner, the throughput / in-flight choice, the frontier refinement and the
 // deferred join of the split chain), the context's device buffers (DevBuf), the upload
 // (rtx_upload.hip, committing what the HIP-free rtx_pack.h packs), the cull records
-// (rtx_cull_records.hip), the tile schedule (rtx_sched.hip) and the frame (rtx_frame.hip).  The render
+// (rtx_cull_records.hip), the in-place edits (rtx_edit.hip), the tile schedule (rtx_sched.hip) and the frame (rtx_frame.hip).  The render
 // kernel's launches are rtx_launch.h's.  Internal to librtx_hip.so.
 #pragma once
 
@@ -97,6 +97,11 @@ struct rtx_ctx {
     int sb_cur = -1;
     size_t scene_bytes = 0;
     rtxh::SceneFacts facts;  // of the uploaded scene (rtx_pack.h)
+    // In-place edits (rtx_edit_*, rtx_edit.hip): what the values derived from lights and materials need of
+    // the uploaded scene, kept in step by every edit; edit_ok: the current image is a host upload's (a
+    // device Update's registration and its images are not edited)
+    rtxh::EditInputs edit;
+    bool edit_ok = false;
     DevScene dev{};
     bool has_scene = false;
     // frame buffer in HBM
@@ -226,6 +231,7 @@ struct rtx_ctx {
     float cull_anchor[kMaxViews + kMaxCullLights][5] = {};   // per record copy: anchor xyz, w, bt (rtx_cull_dump)
     std::vector<std::array<float, 4>> cull_lights;   // the uploaded lights' anchors {origin, T}
     bool cull_boxes_pending = false;      // an upload's boxes and light records wait for its first frame
+    uint32_t cull_lights_dirty = 0;       // bit l: an edit moved light l, whose records alone wait (rtx_edit.hip)
     rtx_render_params last{};
     int last_views = 1;
     bool last_valid = false, last_rgb = false;
@@ -298,6 +304,8 @@ int adopt_image(rtx_ctx* c, int k, size_t total);
 // an uploaded node array (`n2` node records per copy, copies `stride` float4 apart).
 void cull_records(rtx_ctx* c, const std::vector<float>& T, const rtx_light* lights, uint32_t n_lights);
 int cull_views(rtx_ctx* c, const FrameArgs& F);
+// whether record launches that need no view wait (an upload's, or an edit's moved lights)
+inline bool cull_lights_due(const rtx_ctx* c) { return c->cull_boxes_pending || c->cull_lights_dirty != 0; }
 void octant_expand(float4* nodes, uint32_t n2, uint32_t stride, hipStream_t s);
 
 // rtx_sched.hip: queue the next frames' dispatch order and heavy set from measured frame F's tile costs.

@@ -366,14 +366,18 @@ void cull_records(rtx_ctx* c, const std::vector<float>& T, const rtx_light* ligh
 int cull_views(rtx_ctx* c, const FrameArgs& F) {
     CullAnchors A{};
     const bool boxes = c->cull_boxes_pending;
-    if (boxes) {
+    // after an upload every light's anchor; after an edit (rtx_edit.hip) the moved lights' alone
+    const uint32_t lights = boxes ? ~0u : c->cull_lights_dirty;
+    if (lights) {
         for (size_t l = 0; l < c->cull_lights.size(); ++l) {
+            if (!((lights >> l) & 1u)) continue;
             for (int k = 0; k < 4; ++k) A.p[A.n][k] = c->cull_lights[l][k];
             A.bt[A.n] = A.p[A.n][3];
             A.idx[A.n] = static_cast<uint32_t>(kMaxViews + l);
             ++A.n;
         }
     }
+    const uint32_t light_anchors = A.n;
     uint32_t valid = c->cull_view_valid;
     for (uint32_t v = 0; v < F.n_views && v < static_cast<uint32_t>(kMaxViews); ++v) {
         const float* o = F.cam[v].origin;
@@ -391,16 +395,18 @@ int cull_views(rtx_ctx* c, const FrameArgs& F) {
         c->dev.cull_T = nullptr;
         c->dev.cull_stride = 0;
         c->cull_boxes_pending = false;
+        c->cull_lights_dirty = 0;
         c->cull_view_valid = 0;
         ++c->cull_failures;
         (void)hipGetLastError();
         return RTX_OK;
     }
-    if (A.n > (boxes ? c->cull_lights.size() : 0u)) ++c->cull_updates;
+    if (A.n > light_anchors) ++c->cull_updates;
     for (uint32_t j = 0; j < A.n; ++j)
         if (A.idx[j] < static_cast<uint32_t>(kMaxViews)) std::memcpy(c->cull_view[A.idx[j]], A.p[j], 12);
     c->cull_view_valid = valid;
     c->cull_boxes_pending = false;
+    c->cull_lights_dirty = 0;
     return RTX_OK;
 }
 

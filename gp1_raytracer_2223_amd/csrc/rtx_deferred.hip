@@ -60,7 +60,7 @@ int deferred_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, Fram
     // The shadow rays' cull records are the light anchors', which an upload leaves to its first frame
     // or pass.  After a relight upload that is this call: the boxes and the lights' records, no
     // camera's (the shade casts no primary ray), and the camera records' state stays as it was.
-    if (!c->facts.deep_stack && !c->facts.hbm_stack && c->dev.cull_stride && c->cull_boxes_pending) {
+    if (!c->facts.deep_stack && !c->facts.hbm_stack && c->dev.cull_stride && cull_lights_due(c)) {
         FrameArgs L = F;
         L.n_views = 0;
         if (const int rc = cull_views(c, L); rc != RTX_OK) return rc;

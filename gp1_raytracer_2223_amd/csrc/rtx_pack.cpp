@@ -47,6 +47,14 @@ bool room_planes(const rtx_scene* s) {
     return room;
 }
 
+// plane k's origin and normal on its axis kRoomAxes[k] (zeros when the planes are not the room's)
+void room_axes(const rtx_scene* s, bool room, float* p0, float* nrm) {
+    for (int k = 0; k < 5; ++k) {
+        p0[k] = room ? s->planes[k].origin[kRoomAxes[k]] : 0.f;
+        nrm[k] = room ? s->planes[k].normal[kRoomAxes[k]] : 0.f;
+    }
+}
+
 // The room skip's host fact (render_tile's room_clear).  The five planes bound a convex
 // room; when every light lies strictly inside it, a shadow ray that starts strictly inside cannot meet
 // a room plane before its light.  The kernel may skip the reference's plane tests only where the
@@ -66,16 +74,17 @@ struct RoomSkip {
     float M = 0.f;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
 };
-RoomSkip room_skip(const rtx_scene* s, bool room, bool off) {
+// (the planes as EditInputs keeps them: plane k's origin p0[k] and normal nrm[k] on axis kRoomAxes[k])
+RoomSkip room_skip(const float* p0s, const float* nrm, const rtx_light* lights, uint32_t n_lights, bool room, bool off) {
     RoomSkip r;
-    if (!room || off || s->n_lights == 0) return r;
+    if (!room || off || n_lights == 0) return r;
     double mmin = INFINITY, mmax = 0.0;
-    for (uint32_t i = 0; i < s->n_lights; ++i) {
-        if (s->lights[i].type != RTX_LIGHT_POINT) return r;
+    for (uint32_t i = 0; i < n_lights; ++i) {
+        if (lights[i].type != RTX_LIGHT_POINT) return r;
         for (int k = 0; k < 5; ++k) {
             const int A = kRoomAxes[k];
-            const double m = static_cast<double>(s->planes[k].normal[A]) *
-                             (static_cast<double>(s->lights[i].origin[A]) - static_cast<double>(s->planes[k].origin[A]));
+            const double m = static_cast<double>(nrm[k]) *
+                             (static_cast<double>(lights[i].origin[A]) - static_cast<double>(p0s[k]));
             if (!(std::isfinite(m) && m > 0.0)) return r;
             mmin = std::fmin(mmin, m);
             mmax = std::fmax(mmax, m);
@@ -89,8 +98,8 @@ RoomSkip room_skip(const rtx_scene* s, bool room, bool off) {
     float lo[3] = {-INFINITY, -INFINITY, -INFINITY}, hi[3] = {INFINITY, INFINITY, INFINITY};
     for (int k = 0; k < 5; ++k) {
         const int A = kRoomAxes[k];
-        const float p0 = s->planes[k].origin[A];
-        const bool up = s->planes[k].normal[A] == 1.f;   // inside: o > p0 (else o < p0)
+        const float p0 = p0s[k];
+        const bool up = nrm[k] == 1.f;   // inside: o > p0 (else o < p0)
         // |a_k| <= M as the kernel's binary32 difference would have it
         auto near = [&](float o) {
             const volatile float a = up ? o - p0 : p0 - o;
@@ -177,7 +186,9 @@ int pack_prims(const rtx_scene* s, const PackOptions& opt, PackedScene& P, Work&
     // the room skip's record behind the room's five planes (inside the section's padding, so no
     // offset moves): {lo, M}, {hi, 0}
     W.room = room_planes(s);
-    W.rs = room_skip(s, W.room, opt.room_skip_off);
+    float p0[5] = {}, nrm[5] = {};
+    room_axes(s, W.room, p0, nrm);
+    W.rs = room_skip(p0, nrm, s->lights, s->n_lights, W.room, opt.room_skip_off);
     if (W.room) {
         P.pl.push_back(f4(W.rs.lo[0], W.rs.lo[1], W.rs.lo[2], W.rs.M));
         P.pl.push_back(f4(W.rs.hi[0], W.rs.hi[1], W.rs.hi[2], 0.f));
@@ -434,19 +445,15 @@ bool cull_worth(const PackedScene& P, const Work& W, double cull_min_sa) {
 
 // Per light the tmax up to which its shadow rays are culled: 4x the farthest mesh-box corner + 1
 // (longer rays pass).
-void cull_tmax(const rtx_scene* s, PackedScene& P) {
-    for (uint32_t i = 0; i < s->n_lights; ++i) {
-        double R = 0.0;
-        for (int k = 0; k < 8; ++k) {
-            const double cx = (k & 1) ? P.bmax[0] : P.bmin[0], cy = (k & 2) ? P.bmax[1] : P.bmin[1],
-                         cz = (k & 4) ? P.bmax[2] : P.bmin[2];
-            const double dx = s->lights[i].origin[0] - cx, dy = s->lights[i].origin[1] - cy,
-                         dz = s->lights[i].origin[2] - cz;
-            R = std::fmax(R, std::sqrt(dx * dx + dy * dy + dz * dz));
-        }
-        const double T = 4.0 * R + 1.0;
-        P.cull_T.push_back(std::isfinite(T) && T < 0x1p60 ? static_cast<float>(T) : 0.f);   // 0: never culled
+float cull_tmax(const float* origin, const double* bmin, const double* bmax) {
+    double R = 0.0;
+    for (int k = 0; k < 8; ++k) {
+        const double cx = (k & 1) ? bmax[0] : bmin[0], cy = (k & 2) ? bmax[1] : bmin[1], cz = (k & 4) ? bmax[2] : bmin[2];
+        const double dx = origin[0] - cx, dy = origin[1] - cy, dz = origin[2] - cz;
+        R = std::fmax(R, std::sqrt(dx * dx + dy * dy + dz * dz));
     }
+    const double T = 4.0 * R + 1.0;
+    return std::isfinite(T) && T < 0x1p60 ? static_cast<float>(T) : 0.f;   // 0: never culled
 }
 
 // Cull records' inputs: per node slot the range of device triangles under it (leaf order is
@@ -460,7 +467,7 @@ void cull_inputs(const rtx_scene* s, const PackOptions& opt, PackedScene& P, Wor
     P.worth_from = W.reuse_worth ? PackedScene::kWorthReused : PackedScene::kWorthComputed;
     P.worth = W.reuse_worth ? opt.worth : cull_worth(P, W, opt.cull_min_sa);
     P.cull_on = W.ordered_all && P.worth;   // the ordered walk needs left-then-right = increasing index
-    cull_tmax(s, P);
+    for (uint32_t i = 0; i < s->n_lights; ++i) P.cull_T.push_back(cull_tmax(s->lights[i].origin, P.bmin, P.bmax));
 }
 
 // Device links are byte offsets (s_load with an SGPR offset, no address arithmetic):
@@ -490,19 +497,28 @@ void octant_decision(PackedScene& P) {
     P.oct_ok = ok;
 }
 
+// The two record encoders (an upload's and an edit's): a light's 2 records, a material's 3.
+void light_records(const rtx_light& l, float4* out) {
+    out[0] = f4(l.origin[0], l.origin[1], l.origin[2], bitsi(l.type));
+    out[1] = f4(l.color[0], l.color[1], l.color[2], l.intensity);
+}
+void material_records(const rtx_material& m, float4* out) {
+    // BRDF::Lambert(kd, cd) = (cd * kd) / PI (BRDFs.h:14-17), exact binary32 on host
+    const float lr = (m.color[0] * m.kd) / RTX_PI, lg = (m.color[1] * m.kd) / RTX_PI, lb = (m.color[2] * m.kd) / RTX_PI;
+    out[0] = f4(bitsi(m.kind), m.color[0], m.color[1], m.color[2]);
+    out[1] = f4(m.kd, m.ks, m.exponent, m.metalness);
+    out[2] = f4(m.roughness, lr, lg, lb);
+}
+
 void pack_lights_materials(const rtx_scene* s, PackedScene& P) {
+    float4 r[3];
     for (uint32_t i = 0; i < s->n_lights; ++i) {
-        const rtx_light& l = s->lights[i];
-        P.lights.push_back(f4(l.origin[0], l.origin[1], l.origin[2], bitsi(l.type)));
-        P.lights.push_back(f4(l.color[0], l.color[1], l.color[2], l.intensity));
+        light_records(s->lights[i], r);
+        P.lights.insert(P.lights.end(), r, r + 2);
     }
     for (uint32_t i = 0; i < s->n_materials; ++i) {
-        const rtx_material& m = s->materials[i];
-        // BRDF::Lambert(kd, cd) = (cd * kd) / PI (BRDFs.h:14-17), exact binary32 on host
-        const float lr = (m.color[0] * m.kd) / RTX_PI, lg = (m.color[1] * m.kd) / RTX_PI, lb = (m.color[2] * m.kd) / RTX_PI;
-        P.mats.push_back(f4(bitsi(m.kind), m.color[0], m.color[1], m.color[2]));
-        P.mats.push_back(f4(m.kd, m.ks, m.exponent, m.metalness));
-        P.mats.push_back(f4(m.roughness, lr, lg, lb));
+        material_records(s->materials[i], r);
+        P.mats.insert(P.mats.end(), r, r + 3);
     }
 }
 
@@ -608,6 +624,113 @@ void emit(const PackedScene& P, char* dst, int host_octant_copies) {
         }
         std::memset(dst + x.off + x.n, 0, end - x.off - x.n);
     }
+}
+
+// ---- in-place edits ---------------------------------------------------------------------------------
+void edit_inputs(const rtx_scene* s, const PackOptions& opt, const PackedScene& P, EditInputs& E) {
+    // (every field is set: an animated loop's upload per frame reuses the vectors' storage)
+    E.room = (P.facts.spec & kSpecRoomPlanes) != 0;
+    E.room_skip_off = opt.room_skip_off;
+    room_axes(s, E.room, E.room_p0, E.room_n);
+    E.has_cull_T = !P.cull_T.empty();
+    for (int a = 0; a < 3; ++a) { E.bmin[a] = P.bmin[a]; E.bmax[a] = P.bmax[a]; }
+    E.off_planes = P.sec[kSecPlanes].off; E.off_lights = P.sec[kSecLights].off;
+    E.off_mats = P.sec[kSecMaterials].off; E.off_cull_T = P.sec[kSecCullT].off;
+    E.lights.assign(s->lights, s->lights + s->n_lights);
+    E.kinds.resize(s->n_materials);
+    for (uint32_t i = 0; i < s->n_materials; ++i) E.kinds[i] = s->materials[i].kind;
+    E.facts = P.facts;
+}
+
+namespace {
+void push_records(EditRange& r, const float4* rec, int n) {
+    const size_t at = r.words.size();
+    r.words.resize(at + 4 * static_cast<size_t>(n));
+    std::memcpy(r.words.data() + at, rec, 16 * static_cast<size_t>(n));
+}
+}  // namespace
+
+int pack_light_edit(const EditInputs& E, uint32_t first, uint32_t n, const rtx_light* lights, LightPatch& out,
+                    std::string& err) {
+    out = LightPatch{};
+    const size_t count = E.lights.size();
+    if ((n && !lights) || first > count || n > count - first) return refuse(err, "light range beyond the uploaded lights");
+    for (uint32_t i = 0; i < n; ++i)
+        if (lights[i].type != E.lights[first + i].type) {
+            err = "light " + std::to_string(first + i) + " changes its type: that is an upload";
+            return RTX_E_UNSUPPORTED;
+        }
+    out.lights = E.lights;
+    out.moved_l.assign(count, 0);
+    out.room_fact = E.facts.room_fact;
+    out.room_M = E.facts.room_M;
+    EditRange rec;
+    rec.off = E.off_lights + 32 * static_cast<size_t>(first);
+    for (uint32_t i = 0; i < n; ++i) {
+        rtx_light& l = out.lights[first + i];
+        if (std::memcmp(l.origin, lights[i].origin, 12) != 0) { out.moved_l[first + i] = 1; ++out.moved; }
+        std::memcpy(l.origin, lights[i].origin, 12);
+        std::memcpy(l.color, lights[i].color, 12);
+        l.intensity = lights[i].intensity;
+        float4 r[2];
+        light_records(l, r);
+        push_records(rec, r, 2);
+    }
+    if (n) out.ranges.push_back(std::move(rec));
+    if (!out.moved) return RTX_OK;
+    // what pack_scene derives from the lights' origins: the room-skip record and facts, the lights' cull_T
+    if (E.room) {
+        const RoomSkip rs = room_skip(E.room_p0, E.room_n, out.lights.data(), static_cast<uint32_t>(count), true, E.room_skip_off);
+        const float4 r[2] = {f4(rs.lo[0], rs.lo[1], rs.lo[2], rs.M), f4(rs.hi[0], rs.hi[1], rs.hi[2], 0.f)};
+        EditRange room;
+        room.off = E.off_planes + 5 * 32;
+        push_records(room, r, 2);
+        out.ranges.push_back(std::move(room));
+        out.room_fact = rs.fact;
+        out.room_M = rs.M;
+    }
+    if (E.has_cull_T) {
+        EditRange t;
+        t.off = E.off_cull_T + 4 * static_cast<size_t>(first);
+        for (uint32_t i = 0; i < n; ++i) {
+            out.cull_T.push_back(cull_tmax(out.lights[first + i].origin, E.bmin, E.bmax));
+            t.words.push_back(ubits(out.cull_T.back()));
+        }
+        out.ranges.push_back(std::move(t));
+    }
+    return RTX_OK;
+}
+
+void commit_light_edit(EditInputs& E, LightPatch& patch) {
+    E.lights.swap(patch.lights);
+    E.facts.room_fact = patch.room_fact;
+    E.facts.room_M = patch.room_M;
+}
+
+int pack_material_edit(const EditInputs& E, uint32_t first, uint32_t n, const rtx_material* materials,
+                       MaterialPatch& out, std::string& err) {
+    out = MaterialPatch{};
+    const size_t count = E.kinds.size();
+    if ((n && !materials) || first > count || n > count - first)
+        return refuse(err, "material range beyond the uploaded materials");
+    for (uint32_t i = 0; i < n; ++i)
+        if (materials[i].kind != E.kinds[first + i]) {
+            err = "material " + std::to_string(first + i) + " changes its kind: that is an upload";
+            return RTX_E_UNSUPPORTED;
+        }
+    EditRange rec;
+    rec.off = E.off_mats + 48 * static_cast<size_t>(first);
+    for (uint32_t i = 0; i < n; ++i) {
+        float4 r[3];
+        material_records(materials[i], r);
+        push_records(rec, r, 3);
+    }
+    if (n) out.ranges.push_back(std::move(rec));
+    return RTX_OK;
+}
+
+void apply_ranges(const std::vector<EditRange>& ranges, char* image) {
+    for (const EditRange& r : ranges) std::memcpy(image + r.off, r.words.data(), 4 * r.words.size());
 }
 
 }  // namespace rtxh

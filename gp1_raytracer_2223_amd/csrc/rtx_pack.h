@@ -105,4 +105,49 @@ int pack_scene(const rtx_scene* s, const PackOptions& opt, PackedScene& out, std
 // intermediate node image).
 void emit(const PackedScene& P, char* dst, int host_octant_copies);
 
+// ---- in-place edits of the light and material records (rtx_edit.hip) --------------------------------
+// What the values derived from the lights and materials need of the packed scene besides the edited
+// records themselves: a context retains it at upload, so an edit never needs the caller's scene again.
+struct EditInputs {
+    bool room = false;             // the five planes are the room's (kSpecRoomPlanes)
+    bool room_skip_off = false;    // PackOptions::room_skip_off
+    float room_p0[5] = {}, room_n[5] = {};   // plane k's origin and normal on axis kRoomAxes[k]
+    bool has_cull_T = false;       // the image holds a kSecCullT entry per light
+    double bmin[3] = {}, bmax[3] = {};       // the meshes' box (cull_tmax)
+    size_t off_planes = 0, off_lights = 0, off_mats = 0, off_cull_T = 0;   // the sections' offsets in the image
+    std::vector<rtx_light> lights;           // as uploaded, then as edited (direction unused)
+    std::vector<int32_t> kinds;              // per material
+    SceneFacts facts;              // room_fact and room_M follow the edits
+};
+void edit_inputs(const rtx_scene* s, const PackOptions& opt, const PackedScene& P, EditInputs& E);
+
+// The bytes an edit replaces: 32-bit words at byte offset `off` of the image, in the packer's own encoding.
+struct EditRange {
+    size_t off = 0;
+    std::vector<uint32_t> words;
+};
+struct LightPatch {
+    std::vector<EditRange> ranges;   // the light records; with a moved light, the room-skip record and cull_T too
+    uint32_t moved = 0;              // lights whose origin bits changed, counted
+    std::vector<uint8_t> moved_l;    // per light of the scene: its origin changed
+    std::vector<rtx_light> lights;   // every light of the edited scene (EditInputs::lights after the edit)
+    std::vector<float> cull_T;       // per edited light (first + i), when the image holds them
+    bool room_fact = false;          // the edited scene's facts
+    float room_M = 0.f;
+};
+struct MaterialPatch {
+    std::vector<EditRange> ranges;
+};
+// The patch that turns the image of E's scene into the image of the scene with lights [first, first + n)
+// (materials, for the second) replaced.  RTX_OK; RTX_E_INVALID for a range beyond the uploaded count;
+// RTX_E_UNSUPPORTED for a changed light type or material kind, the first one named in `err`.  E is not
+// changed: commit_light_edit makes it the edited scene's once the bytes are on their way.
+int pack_light_edit(const EditInputs& E, uint32_t first, uint32_t n, const rtx_light* lights, LightPatch& out,
+                    std::string& err);
+int pack_material_edit(const EditInputs& E, uint32_t first, uint32_t n, const rtx_material* materials,
+                       MaterialPatch& out, std::string& err);
+void commit_light_edit(EditInputs& E, LightPatch& patch);
+// Apply a patch's ranges to an image in host memory.
+void apply_ranges(const std::vector<EditRange>& ranges, char* image);
+
 }  // namespace rtxh

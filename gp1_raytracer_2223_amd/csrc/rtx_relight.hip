@@ -82,7 +82,7 @@ int shadows_build(rtx_ctx* c, FrameArgs& F, dim3& grid, uint32_t trace, uint32_t
     F.lm_lights = trace & all_lights(c);   // (PHASE 9 reads these two as its masks: rtx_kernels.h)
     F.heavy_n = keep & all_lights(c);
     // the light anchors' cull records, when this is the first launch after an upload (as deferred_prepare)
-    if (!c->facts.deep_stack && !c->facts.hbm_stack && c->dev.cull_stride && c->cull_boxes_pending) {
+    if (!c->facts.deep_stack && !c->facts.hbm_stack && c->dev.cull_stride && cull_lights_due(c)) {
         FrameArgs L = F;
         L.n_views = 0;
         if (const int rc = cull_views(c, L); rc != RTX_OK) return rc;

@@ -132,6 +132,7 @@ void set_scene_state(rtx_ctx* c, const PackedScene& P, const rtx_ctx::SceneBuf& 
     c->cull_view_valid = 0;
     c->dev = dev_scene(P, B);
     c->cull_boxes_pending = false;
+    c->cull_lights_dirty = 0;
     c->facts = P.facts;
     c->last_facts = c->facts.spec;   // (rtx_spec_info before the first frame)
     c->last_variant = -1;
@@ -155,7 +156,8 @@ void set_scene_state(rtx_ctx* c, const PackedScene& P, const rtx_ctx::SceneBuf& 
 int upload_scene(rtx_ctx* c, const rtx_scene* s, const std::vector<uint8_t>& reserve, PackedScene& P) {
     if (!c || !s) return RTX_E_INVALID;
     std::string err;
-    if (const int rc = pack_scene(s, pack_options(c, s, reserve), P, err); rc != RTX_OK) return fail(c, rc, err);
+    const PackOptions opt = pack_options(c, s, reserve);
+    if (const int rc = pack_scene(s, opt, P, err); rc != RTX_OK) return fail(c, rc, err);
     HIP_TRY(c, hipSetDevice(c->device));
     int k = 0;
     if (const int rc = next_image(c, P.total, k); rc != RTX_OK) return rc;
@@ -169,6 +171,8 @@ int upload_scene(rtx_ctx* c, const rtx_scene* s, const std::vector<uint8_t>& res
     if (const int rc = queue_copies(c, P, B, oct_dev); rc != RTX_OK) return rc;
     if (const int rc = adopt_image(c, k, P.total); rc != RTX_OK) return rc;
     set_scene_state(c, P, B);
+    edit_inputs(s, opt, P, c->edit);   // (what rtx_edit_* needs of this scene)
+    c->edit_ok = reserve.empty();
     if (P.cull_on) cull_records(c, P.cull_T, s->lights, s->n_lights);   // (built before the first frame)
     return RTX_OK;
 }

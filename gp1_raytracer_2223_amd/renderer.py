@@ -336,6 +336,41 @@ class DeviceContext:
         abi.check(self.lib.rtx_device_shadow_buffer(self.h, C.byref(d)), "rtx_device_shadow_buffer", self.h)
         return C.cast(d, C.c_void_p).value or 0
 
+    # ---- scene edits (rtx_edit_*): light and material records of the current image replaced in place
+    @staticmethod
+    def _records(records, kind):
+        """`records` as a ctypes array of `kind` (a ctypes array of it passes through; else a sequence of them)."""
+        if isinstance(records, C.Array) and records._type_ is kind:
+            return records
+        recs = list(records)
+        return (kind * len(recs))(*recs)
+
+    def edit_lights(self, first: int, lights) -> None:
+        """Lights first .. first+len-1 of the uploaded scene take the given origin, color and intensity, in
+        place and queued (rtx_edit_lights); the types must be the uploaded ones.  After a light moved, relight()
+        with shadows needs update_shadows_async or refresh_shadows_async first, as after an upload."""
+        arr = self._records(lights, abi.Light)
+        abi.check(self.lib.rtx_edit_lights(self.h, int(first), len(arr), arr), "rtx_edit_lights", self.h)
+
+    def edit_materials(self, first: int, materials) -> None:
+        """Materials first .. first+len-1 take the given values in place (rtx_edit_materials); kinds as uploaded."""
+        arr = self._records(materials, abi.Material)
+        abi.check(self.lib.rtx_edit_materials(self.h, int(first), len(arr), arr), "rtx_edit_materials", self.h)
+
+    def edit_light_values_device(self, first: int, n: int, d_ptr: int) -> None:
+        """The colour and intensity of lights first .. first+n-1 from device memory: 4 floats a light, {color[3],
+        intensity}, at device address `d_ptr` (rtx_edit_light_values_device).  Queued: the memory stays valid
+        until the context's stream has passed the edit."""
+        abi.check(self.lib.rtx_edit_light_values_device(self.h, int(first), int(n), int(d_ptr) or None),
+                  "rtx_edit_light_values_device", self.h)
+
+    def edit_material_values_device(self, first: int, n: int, d_ptr: int) -> None:
+        """The values of materials first .. first+n-1 from device memory: 8 floats a material, {color[3], kd, ks,
+        exponent, metalness, roughness} (rtx_edit_material_values_device); the Lambert term is computed on the
+        device, bit for bit the host form's."""
+        abi.check(self.lib.rtx_edit_material_values_device(self.h, int(first), int(n), int(d_ptr) or None),
+                  "rtx_edit_material_values_device", self.h)
+
     def relight_async(self, params: abi.RenderParams, want_rgb: bool = False) -> None:
         """Queue the relight of the last hit pass into the colour frame buffer (rtx_relight_async): `params`
         supplies the lighting mode, shadows and pixel format; with shadows the shadow plane answers DoesHit."""
@@ -632,6 +667,43 @@ class Renderer:
             self._scene_ref = weakref.ref(scene)
             self._scene_gen = scene.generation
         return s, cam
+
+    def _edit(self, scene: HostScene, first: int, records, which: str) -> None:
+        """Write `records` over the host scene's own from `first` on (type and kind stay the scene's), and
+        bring the device in step: in place when `scene` in this state is the uploaded one, else by an upload."""
+        s, _ = scene.view()
+        own, count = (s.lights, s.n_lights) if which == "lights" else (s.materials, s.n_materials)
+        records = list(records)
+        if first < 0 or first + len(records) > count:
+            raise ValueError(f"Edit: {which} {first} .. {first + len(records) - 1} of {count}")
+        same = self._scene_ref is not None and self._scene_ref() is scene and self._scene_gen == scene.generation
+        for i, r in enumerate(records):
+            if which == "lights":
+                own[first + i].origin[:] = list(r.origin)
+                own[first + i].color[:] = list(r.color)
+                own[first + i].intensity = r.intensity
+            else:
+                kind = own[first + i].kind
+                C.memmove(C.byref(own[first + i]), C.byref(r), C.sizeof(abi.Material))
+                own[first + i].kind = kind
+        if not same:
+            self._view(scene, True)
+        elif which == "lights":
+            self.ctx.edit_lights(first, [own[first + i] for i in range(len(records))])
+        else:
+            self.ctx.edit_materials(first, [own[first + i] for i in range(len(records))])
+
+    def EditLights(self, scene: HostScene, first: int, lights) -> None:
+        """Lights first .. of `scene` take the origin, color and intensity of `lights` (abi.Light records), in
+        the host scene and, without an upload, in the uploaded one (rtx_edit_lights; not in the reference's
+        Renderer): a later call with upload=False sees the edit, one with upload=True uploads the same scene.
+        After a moved light, RefreshShadows before Relight, as after an upload."""
+        self._edit(scene, int(first), lights, "lights")
+
+    def EditMaterials(self, scene: HostScene, first: int, materials) -> None:
+        """Materials first .. of `scene` take the values of `materials` (abi.Material records; kinds stay), as
+        EditLights does for lights (rtx_edit_materials)."""
+        self._edit(scene, int(first), materials, "materials")
 
     def RenderAOV(self, scene: HostScene, mask: int = AOV_ALL, upload: bool = True) -> dict:
         """The hit pass of the frame Render would render (same size, stripes and upload bookkeeping):

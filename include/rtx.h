@@ -30,7 +30,7 @@
  * and the scheduler's / exact cull's internals are in rtx_diag.h; the environment knobs the library
  * reads are listed in INTEGRATION.md (none of them changes a pixel).  In csrc/ the entry points
  * live by topic: rtx_context.hip, rtx_upload.hip, rtx_frame.hip, rtx_aov.hip (the hit pass),
- * rtx_deferred.hip (deferred shading), rtx_relight.hip (the shadow pass and the relight), rtx_query.hip (ray queries and shaded rays), rtx_adaptive.hip (adaptive supersampling), rtx_group.cpp and
+ * rtx_deferred.hip (deferred shading), rtx_relight.hip (the shadow pass and the relight), rtx_edit.hip (scene edits in place), rtx_query.hip (ray queries and shaded rays), rtx_adaptive.hip (adaptive supersampling), rtx_group.cpp and
  * rtx_anim_host.hip; the render kernel is rtx_hip.hip.
  */
 #ifndef RTX_H_
@@ -495,6 +495,42 @@ int rtx_relight_resolve_async(rtx_ctx* ctx, const rtx_render_params* params, uin
  * NULL; out_pixels == NULL: RTX_E_INVALID). */
 int rtx_relight_resolve(rtx_ctx* ctx, const rtx_render_params* params, uint32_t k, uint32_t* out_pixels,
                         float* out_rgb);
+
+/* ---- scene edits: lights and materials changed in place ---------------------------------------
+ * The relighting loop changes 32 bytes of a light or 48 of a material; rtx_upload_scene packs and copies
+ * the whole scene for that.  An edit replaces records of the CURRENT scene image in place, on the context
+ * stream, behind a pending split chain and ordered with every frame, pass, query and Update queued before
+ * and after it, without waiting on the host.  After any sequence of edits every entry point behaves word
+ * for word as if the scene with those records replaced had been given to rtx_upload_scene.
+ *
+ * rtx_edit_lights: lights first .. first+n-1 take the given origin, color and intensity (`direction` is
+ * ignored: the device record never carried it).  `type` must be the uploaded light's.  A light whose
+ * origin bits did not change is a value edit of its own two records.  A moved light also renews what the
+ * upload derives from light origins: the room-skip record and fact (rtx_room_info; it can flip either
+ * way), the light's cull bound and its exact-cull anchor records (the camera anchors stay valid), and the
+ * light's key for the shadow plane: rtx_relight* with shadows on then refuses until
+ * rtx_update_shadows_async or rtx_refresh_shadows_async has run, and the refresh traces exactly the
+ * moved lights.
+ * rtx_edit_materials: materials first .. first+n-1 take the given values; `kind` must be the uploaded one.
+ *
+ * The _device forms read VALUES from device memory of the context's device (queued, returning at once;
+ * the memory must stay valid until the stream reaches the edit): per light 4 floats {color[3],
+ * intensity}, per material 8 floats {color[3], kd, ks, exponent, metalness, roughness}.  They cannot move
+ * a light or change a kind, so no host state changes; the image is the host form's bit for bit for every
+ * finite value.
+ *
+ * An edit is no upload for any policy: the tile schedule and costs, the split tuner, the refinement, motion
+ * mode and the cull worth cache stay as they were.
+ * Errors, in this order (the context keeps working after each, and a refused edit changes nothing): NULL
+ * ctx, NULL records with n > 0, first + n above the uploaded count: RTX_E_INVALID; no scene uploaded:
+ * RTX_E_STATE; a changed type or kind (the first is named in rtx_last_error), or a context whose current
+ * image belongs to a device Update's registration (rtx_anim_create): RTX_E_UNSUPPORTED.  n == 0 returns
+ * RTX_OK and launches nothing.  Adding or removing records, type and kind changes, and sphere, plane or
+ * mesh edits are uploads. */
+int rtx_edit_lights(rtx_ctx* ctx, uint32_t first, uint32_t n, const rtx_light* lights);
+int rtx_edit_materials(rtx_ctx* ctx, uint32_t first, uint32_t n, const rtx_material* materials);
+int rtx_edit_light_values_device(rtx_ctx* ctx, uint32_t first, uint32_t n, const float* d_values);
+int rtx_edit_material_values_device(rtx_ctx* ctx, uint32_t first, uint32_t n, const float* d_values);
 
 /* ---- ray queries: closest hit and occlusion for caller-supplied rays ---------------
  * The traversal behind a frame's rays, for rays the caller makes: a line-of-sight test, a pick ray,

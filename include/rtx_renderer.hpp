@@ -144,6 +144,18 @@ public:
         const rtx_render_params p = Params();
         Check(rtx_relight(m_Ctx, &p, m_Pixels.data(), nullptr), "rtx_relight");
     }
+    // Scene edits (rtx_edit_lights, rtx_edit_materials; not in the reference): records first .. of the scene
+    // uploaded last replaced in place, without packing or copying anything else; types and kinds stay the
+    // uploaded ones.  The caller keeps its host scene in step (rtx_host_light_set_origin, or the same values
+    // through the scene's view), so that a later call with upload = true uploads the same scene.  After a
+    // moved light, RefreshShadows or UpdateShadows before Relight, as after an upload.
+    void EditLights(uint32_t first, const std::vector<rtx_light>& lights) {
+        Check(rtx_edit_lights(m_Ctx, first, static_cast<uint32_t>(lights.size()), lights.data()), "rtx_edit_lights");
+    }
+    void EditMaterials(uint32_t first, const std::vector<rtx_material>& materials) {
+        Check(rtx_edit_materials(m_Ctx, first, static_cast<uint32_t>(materials.size()), materials.data()),
+              "rtx_edit_materials");
+    }
     // Resolved relighting (rtx_relight_resolve; not in the reference): the anti-aliased form of the loop above.
     // RenderSamplePasses stores the hit pass (all four planes) of the k*width x k*height sample frame of the
     // frame Render would render, k = 2, 4 or 8, and its shadow pass; RelightResolved then fills Pixels() with the
