@@ -60,7 +60,7 @@ def build_host(force: bool = False) -> Path:
 # code object is the first of the library's fat binary (tests/test_isa.py reads that one).
 HIP_KERNEL_UNIT = CSRC / "rtx_hip.hip"
 HIP_SOURCES = [HIP_KERNEL_UNIT, CSRC / "rtx_cull_records.hip", CSRC / "rtx_sched.hip", CSRC / "rtx_context.hip",
-               CSRC / "rtx_pack.cpp", CSRC / "rtx_upload.hip", CSRC / "rtx_frame.hip", CSRC / "rtx_aov.hip", CSRC / "rtx_deferred.hip", CSRC / "rtx_relight.hip", CSRC / "rtx_edit.hip", CSRC / "rtx_query.hip",
+               CSRC / "rtx_pack.cpp", CSRC / "rtx_upload.hip", CSRC / "rtx_frame.hip", CSRC / "rtx_pass.hip", CSRC / "rtx_aov.hip", CSRC / "rtx_deferred.hip", CSRC / "rtx_relight.hip", CSRC / "rtx_edit.hip", CSRC / "rtx_query.hip",
                CSRC / "rtx_adaptive.hip", CSRC / "rtx_diag.hip",
                CSRC / "rtx_policy.hip", CSRC / "rtx_anim.hip", CSRC / "rtx_anim_host.hip", CSRC / "rtx_group.cpp"]
 # Every unit gets every flag (the host units compute floats that reach the pixels too).

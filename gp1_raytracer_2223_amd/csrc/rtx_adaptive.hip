@@ -159,15 +159,7 @@ extern "C" int rtx_adaptive_refined(rtx_ctx* c, uint32_t* n_refined) {
 extern "C" int rtx_time_adaptive_frames(rtx_ctx* c, const rtx_camera* cam, const rtx_render_params* p, uint32_t k,
                                         uint32_t threshold, int iters, float* mean_ms) {
     if (!mean_ms || iters <= 0) return RTX_E_INVALID;
-    // (checks, buffer growth, a new shape's schedule: outside the timing)
+    // one full call first: its checks, buffer growth and a new shape's schedule stay outside the timing
     if (const int rc = rtx_render_adaptive_async(c, cam, p, 0, k, threshold); rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i)
-        if (const int rc = rtx_render_adaptive_async(c, cam, p, 0, k, threshold); rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
-    return RTX_OK;
+    return timed_loop(c, iters, mean_ms, [&](int) { return rtx_render_adaptive_async(c, cam, p, 0, k, threshold); });
 }

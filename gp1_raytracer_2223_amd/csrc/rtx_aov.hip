@@ -34,8 +34,7 @@ int aov_prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rende
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npx = static_cast<size_t>(p->width) * p->height * static_cast<size_t>(n_views);
     // the planes of every mask seen so far, each allocated when first asked for
-    uint32_t need = mask | (c->d_aov_depth ? RTX_AOV_DEPTH : 0u) | (c->d_aov_normal ? RTX_AOV_NORMAL : 0u) |
-                    (c->d_aov_material ? RTX_AOV_MATERIAL : 0u) | (c->d_aov_primitive ? RTX_AOV_PRIMITIVE : 0u);
+    const uint32_t need = mask | planes_mask(device_planes(c));
     if (npx > c->aov_cap) {   // larger planes: all of them again, at the new size
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->d_aov_depth.free(); c->d_aov_normal.free();
@@ -51,11 +50,7 @@ int aov_prepare(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_rende
     if (rc == RTX_OK && (need & RTX_AOV_PRIMITIVE)) rc = aov_alloc(c, c->d_aov_primitive, c->aov_cap, 4);
     if (rc != RTX_OK) return rc;
     frame_shape(c, cams, n_views, p, *p, 0u, F, grid);
-    F.aov_mask = mask;
-    F.aov_depth = c->d_aov_depth;
-    F.aov_normal = c->d_aov_normal;
-    F.aov_material = c->d_aov_material;
-    F.aov_primitive = c->d_aov_primitive;
+    bind_planes(c, F, mask);
     return RTX_OK;
 }
 
@@ -98,8 +93,7 @@ void aov_remember(rtx_ctx* c, const rtx_camera* cams, int n_views, const rtx_ren
 int queue_aov_copy(rtx_ctx* c, const rtx_aov_planes* out) {
     if (!c || !out) return RTX_E_INVALID;
     if (!c->aov_last_mask) return fail(c, RTX_E_STATE, "no hit pass rendered yet");
-    const uint32_t want = (out->depth ? RTX_AOV_DEPTH : 0u) | (out->normal ? RTX_AOV_NORMAL : 0u) |
-                          (out->material ? RTX_AOV_MATERIAL : 0u) | (out->primitive ? RTX_AOV_PRIMITIVE : 0u);
+    const uint32_t want = planes_mask(*out);
     if (want & ~c->aov_last_mask)
         return fail(c, RTX_E_STATE, "the last hit pass (mask " + std::to_string(c->aov_last_mask) +
                                         ") did not write every plane asked for (mask " + std::to_string(want) + ")");
@@ -145,10 +139,7 @@ extern "C" int rtx_render_aov(rtx_ctx* c, const rtx_camera* cam, const rtx_rende
 
 extern "C" int rtx_device_aov_buffers(rtx_ctx* c, rtx_aov_planes* out) {
     if (!c || !out) return RTX_E_INVALID;
-    out->depth = c->d_aov_depth;
-    out->normal = c->d_aov_normal;
-    out->material = c->d_aov_material;
-    out->primitive = c->d_aov_primitive;
+    *out = device_planes(c);
     return RTX_OK;
 }
 
@@ -159,17 +150,10 @@ extern "C" int rtx_time_aov_frames(rtx_ctx* c, const rtx_camera* cam, const rtx_
     dim3 grid;
     int rc = aov_prepare(c, cam, 1, p, mask, F, grid);
     if (rc != RTX_OK) return rc;
-    if (const int rc2 = join_split(c); rc2 != RTX_OK) return rc2;   // (a colour frame's chain: outside the timing)
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        rc = aov_launch(c, F, grid);
-        if (rc != RTX_OK) return rc;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
+    // joined before ev0: aov_launch joins a colour frame's pending chain, which is not the pass's time
+    if (const int rc2 = join_split(c); rc2 != RTX_OK) return rc2;
+    rc = timed_loop(c, iters, mean_ms, [&](int) { return aov_launch(c, F, grid); });
+    if (rc != RTX_OK) return rc;
     aov_remember(c, cam, 1, p, mask);
     return RTX_OK;
 }

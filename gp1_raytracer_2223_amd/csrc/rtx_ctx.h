@@ -4,7 +4,7 @@
 // calls: the split tuner, the throughput / in-flight choice, the frontier refinement and the
 // deferred join of the split chain), the context's device buffers (DevBuf), the upload
 // (rtx_upload.hip, committing what the HIP-free rtx_pack.h packs), the cull records
-// (rtx_cull_records.hip), the in-place edits (rtx_edit.hip), the tile schedule (rtx_sched.hip) and the frame (rtx_frame.hip).  The render
+// (rtx_cull_records.hip), the in-place edits (rtx_edit.hip), the tile schedule (rtx_sched.hip), the frame (rtx_frame.hip) and what the stored hit pass's consumers share (rtx_pass.hip).  The render
 // kernel's launches are rtx_launch.h's.  Internal to librtx_hip.so.
 #pragma once
 
@@ -334,6 +334,27 @@ void remember(rtx_ctx* c, const rtx_render_params* p, int n_views, bool rgb);
 struct CopyPlane { char* dst; const char* src; size_t elem; };
 int queue_rows(rtx_ctx* c, const rtx_render_params& p, int n_views, const CopyPlane* planes, int n_planes);
 
+// rtx_pass.hip: what a consumer of the stored hit pass (rtx_ctx::aov_last*) starts from.  Its checks, which
+// change nothing; each entry point calls them in its contract's order (rtx.h's error tables):
+// a shade's lighting mode and pixel format, as rtx_render checks them;
+int shade_param_checks(rtx_ctx* c, const rtx_render_params* p);
+// a scene, no supersampling, and a last hit pass with all four planes (`what` names the consumer);
+int pass_checks(rtx_ctx* c, const char* what);
+// and a scene with at least the materials the pass was traced with, and one at all.
+int material_checks(rtx_ctx* c);
+// The pass's shape with the call's mode, shadows and format: what the frame would be rendered with.
+rtx_render_params pass_shape(const rtx_ctx* c, const rtx_render_params* p);
+// The launch record of a kernel over the pass in `shape`, after the checks, join_split and any growth: the
+// pass's cameras and tiles (frame_shape), the last colour frames' dispatch order when they had this tile
+// set, the four planes, and the light anchors' cull records when they are due.  Nothing of the colour
+// frames' state is written; the outputs are the caller's.
+int pass_frame(rtx_ctx* c, const rtx_render_params& shape, FrameArgs& F, dim3& grid);
+// The context's four device planes (NULL: not allocated yet), and the same bound into a launch record.
+rtx_aov_planes device_planes(const rtx_ctx* c);
+void bind_planes(const rtx_ctx* c, FrameArgs& F, uint32_t mask);
+// The RTX_AOV_* bits of the planes of `o` that are not NULL.
+uint32_t planes_mask(const rtx_aov_planes& o);
+
 // Join the last frame's deferred split chain into the frame stream (rtx_ctx::join).
 int join_split(rtx_ctx* c);
 // One round of the frontier refinement once its measured frame has completed (rtx_ctx::refine).
@@ -342,6 +363,22 @@ int refine_round(rtx_ctx* c);
 float inflight_ratio(const rtx_ctx* c);
 // Whether a frame in flight, with k frames of this device's contexts at once, renders one piece.
 bool inflight_onepiece(rtx_ctx* c, uint32_t k);
+
+// The timed loop of every rtx_time_* entry point, after its checks and whatever it keeps outside the timing:
+// once(i) for i = 0 .. iters-1 between ev0 and ev1 on the context stream, and their mean in *mean_ms.  The
+// first code that is not RTX_OK is returned unchanged, *mean_ms untouched.
+template <class Once>
+int timed_loop(rtx_ctx* c, int iters, float* mean_ms, Once once) {
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < iters; ++i)
+        if (const int rc = once(i); rc != RTX_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *mean_ms = ms / static_cast<float>(iters);
+    return RTX_OK;
+}
 
 }  // namespace rtxh
 

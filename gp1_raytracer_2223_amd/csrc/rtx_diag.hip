@@ -18,22 +18,16 @@ extern "C" int rtx_time_views(rtx_ctx* c, const rtx_camera* cams, int n_views, c
     // and every kSchedPeriod-th frame measures again
     int rc = prepare(c, cams, n_views, p, false, F, grid);
     if (rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i) {
+    // the first frame's prepare stays outside the timing, the later ones' and the last frame's chain inside it
+    rc = timed_loop(c, iters, mean_ms, [&](int i) {
         if (i > 0) {
             remember(c, p, n_views, false);
-            rc = prepare(c, cams, n_views, p, false, F, grid);
-            if (rc != RTX_OK) return rc;
+            if (const int rc2 = prepare(c, cams, n_views, p, false, F, grid); rc2 != RTX_OK) return rc2;
         }
-        rc = launch(c, F, grid, false);
-        if (rc != RTX_OK) return rc;
-    }
-    if (const int rc2 = join_split(c); rc2 != RTX_OK) return rc2;   // (the last chain inside the timing)
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
+        if (const int rc2 = launch(c, F, grid, false); rc2 != RTX_OK) return rc2;
+        return i + 1 < iters ? RTX_OK : join_split(c);
+    });
+    if (rc != RTX_OK) return rc;
     remember(c, p, n_views, false);
     return RTX_OK;
 }

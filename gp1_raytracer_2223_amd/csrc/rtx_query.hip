@@ -26,8 +26,7 @@ int mask_check(rtx_ctx* c, uint32_t mask, const rtx_aov_planes* out) {
         return fail(c, RTX_E_INVALID, "a ray query's mask must be a non-empty set of RTX_AOV_* bits (got " +
                                           std::to_string(mask) + ")");
     if (!out) return RTX_OK;   // (n == 0)
-    const uint32_t given = (out->depth ? RTX_AOV_DEPTH : 0u) | (out->normal ? RTX_AOV_NORMAL : 0u) |
-                           (out->material ? RTX_AOV_MATERIAL : 0u) | (out->primitive ? RTX_AOV_PRIMITIVE : 0u);
+    const uint32_t given = planes_mask(*out);
     if (given & ~mask)
         return fail(c, RTX_E_INVALID, "a ray query's planes (mask " + std::to_string(given) +
                                           ") must be planes of its mask (" + std::to_string(mask) + ")");
@@ -105,10 +104,7 @@ int shade_check(rtx_ctx* c, const void* rays, uint32_t n, const rtx_render_param
     if (!p) return fail(c, RTX_E_INVALID, "a shade call needs render parameters");
     if (n > 0 && !rays) return fail(c, RTX_E_INVALID, "a shade call needs rays");
     if (n > 0 && !px && !rgb) return fail(c, RTX_E_INVALID, "a shade call needs an output: pixels, rgb or both");
-    if (p->lighting_mode < 0 || p->lighting_mode >= RTX_MODE_COUNT) return fail(c, RTX_E_INVALID, "bad lighting mode");
-    if (p->format.rshift > 24 || p->format.gshift > 24 || p->format.bshift > 24)
-        return fail(c, RTX_E_INVALID, "bad pixel format");
-    return RTX_OK;
+    return shade_param_checks(c, p);
 }
 
 QueryArgs trace_args(const rtx_ray* d_rays, uint32_t n, uint32_t mask, const rtx_aov_planes& d) {
@@ -147,8 +143,7 @@ extern "C" int rtx_trace_rays_device(rtx_ctx* c, const rtx_ray* d_rays, uint32_t
     if (n == 0) return RTX_OK;
     if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
     // (a plane of the mask the caller left NULL is not asked for)
-    const uint32_t given = (d_out->depth ? RTX_AOV_DEPTH : 0u) | (d_out->normal ? RTX_AOV_NORMAL : 0u) |
-                           (d_out->material ? RTX_AOV_MATERIAL : 0u) | (d_out->primitive ? RTX_AOV_PRIMITIVE : 0u);
+    const uint32_t given = planes_mask(*d_out);
     if (given == 0) return RTX_OK;
     return query_launch(c, false, trace_args(d_rays, n, given, *d_out));
 }
@@ -176,16 +171,9 @@ extern "C" int rtx_time_ray_queries(rtx_ctx* c, const rtx_ray* d_rays, uint32_t 
                                   c->stream));
         return RTX_OK;
     };
-    if (const int rc = once(); rc != RTX_OK) return rc;   // (checks, a pending chain's join: outside the timing)
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i)
-        if (const int rc = once(); rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
-    return RTX_OK;
+    // one full call first: its checks and a pending chain's join stay outside the timing of the public entry point
+    if (const int rc = once(); rc != RTX_OK) return rc;
+    return timed_loop(c, iters, mean_ms, [&](int) { return once(); });
 }
 
 extern "C" int rtx_trace_rays(rtx_ctx* c, const rtx_ray* rays, uint32_t n, uint32_t mask, const rtx_aov_planes* out) {
@@ -262,15 +250,7 @@ extern "C" int rtx_shade_rays(rtx_ctx* c, const rtx_ray* rays, uint32_t n, const
 extern "C" int rtx_time_shade_rays(rtx_ctx* c, const rtx_ray* d_rays, uint32_t n, const rtx_render_params* p,
                                    uint32_t* d_pixels, float* d_rgb, int iters, float* mean_ms) {
     if (!c || !d_rays || !p || !mean_ms || iters <= 0 || n == 0) return RTX_E_INVALID;
-    // (checks, a pending chain's join: outside the timing)
+    // one full call first: its checks and a pending chain's join stay outside the timing of the public entry point
     if (const int rc = rtx_shade_rays_device(c, d_rays, n, p, d_pixels, d_rgb); rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i)
-        if (const int rc = rtx_shade_rays_device(c, d_rays, n, p, d_pixels, d_rgb); rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
-    return RTX_OK;
+    return timed_loop(c, iters, mean_ms, [&](int) { return rtx_shade_rays_device(c, d_rays, n, p, d_pixels, d_rgb); });
 }

@@ -1,7 +1,8 @@
 // rtx_relight.hip — relighting behind the C-ABI: the shadow pass (PHASE 9: rtx_render_shadows_async, its
 // plane and its copies; rtx_update_shadows_async and rtx_refresh_shadows_async, the same pass over a subset
 // of the lights, merged into the plane), the relight that shades the last hit pass plus that plane without a ray
-// (rtx_relight*, rtx_relight_kernel), and their timing entry points.
+// (rtx_relight*, rtx_relight_kernel), and their timing entry points.  The checks of the hit pass and the
+// preamble of its launch record are rtx_pass.hip's.
 #include <cstring>
 
 #include "rtx_ctx.h"
@@ -11,39 +12,9 @@ using namespace rtxh;
 
 namespace {
 
-// What both passes ask of the context before anything else: a scene, no supersampling, and a last hit
-// pass with all four planes (the checks of deferred shading, rtx_deferred.hip, in its order).
-int pass_checks(rtx_ctx* c, const char* what) {
-    if (!c->has_scene) return fail(c, RTX_E_STATE, "no scene uploaded");
-    if (c->ss_log2)
-        return fail(c, RTX_E_UNSUPPORTED, std::string("no ") + what + " on a supersampled context (factor " +
-                                              std::to_string(1u << c->ss_log2) + "): the hit pass has one record per pixel");
-    if (!c->aov_last_mask) return fail(c, RTX_E_STATE, "no hit pass rendered yet");
-    if (c->aov_last_mask != static_cast<uint32_t>(RTX_AOV_ALL))
-        return fail(c, RTX_E_STATE, std::string(what) + " needs all four planes: the last hit pass wrote mask " +
-                                        std::to_string(c->aov_last_mask));
-    return RTX_OK;
-}
-
-// The dispatch order of the context's last colour frames when they had the pass's tile set: read, never
-// written, as deferred shading reads it (rtx_deferred.hip).
-const uint32_t* frames_order(rtx_ctx* c, const rtx_render_params& shape, int n_views) {
-    const std::string tk = tiles_key(shape.width, shape.height, n_views, shape.stripe_rows, shape.stripe_first,
-                                     shape.stripe_step);
-    if (c->sched_enabled && c->sched_ready && c->sched_key.compare(0, tk.size(), tk) == 0)
-        return (c->xcd_order ? c->d_order_xcd : c->d_order).get();
-    return nullptr;
-}
-
 // ---- the shadow pass (PHASE 9) ------------------------------------------------------------------
 
-// Checks, the plane and the launch record of a shadow pass over the last hit pass.  The pass gives the
-// shape and the cameras; the kernel runs as the Combined frame with shadows would (that decides the
-// specialised variant, and with it the walk).  Nothing of the colour frames' state is written, and the
-// hit planes and their record are only read.
-// (its two halves: what every shadow pass checks first, and everything after; an update's own checks go
-// between them.  `trace` names the lights whose shadow rays are cast and `keep` the bits of the stored
-// word that are carried over, new = (old & keep) | traced: the full pass is every light and 0.)
+// What every shadow pass checks first; an update's own checks follow them.
 int shadows_checks(rtx_ctx* c) {
     if (!c) return RTX_E_INVALID;
     if (const int rc = pass_checks(c, "shadow pass"); rc != RTX_OK) return rc;
@@ -58,41 +29,29 @@ uint32_t all_lights(const rtx_ctx* c) {
     return c->dev.n_lights >= 32u ? ~0u : (1u << c->dev.n_lights) - 1u;
 }
 
+// The plane and the launch record of a shadow pass over the last hit pass, after its checks.  The pass gives
+// the shape and the cameras; the kernel runs as the Combined frame with shadows would (that decides the
+// specialised variant, and with it the walk).  Nothing of the colour frames' state is written, and the
+// hit planes and their record are only read.  `trace` names the lights whose shadow rays are cast and
+// `keep` the bits of the stored word that are carried over, new = (old & keep) | traced: the full pass is
+// every light and 0.
 int shadows_build(rtx_ctx* c, FrameArgs& F, dim3& grid, uint32_t trace, uint32_t keep) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = join_split(c); rc != RTX_OK) return rc;   // (on the context stream, like the hit pass)
     rtx_render_params shape = c->aov_last;
     shape.lighting_mode = RTX_MODE_COMBINED;
     shape.shadows_enabled = 1;
-    const int n_views = c->aov_last_views;
-    const size_t npx = static_cast<size_t>(shape.width) * shape.height * static_cast<size_t>(n_views);
+    const size_t npx = static_cast<size_t>(shape.width) * shape.height * static_cast<size_t>(c->aov_last_views);
     if (npx > c->d_shadow.cap) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->shadow_serial = 0;   // (its contents are gone)
         if (const int rc = c->d_shadow.grow(c, npx); rc != RTX_OK) return rc;
     }
-    frame_shape(c, c->aov_last_cams, n_views, &shape, shape, 0u, F, grid);
-    F.order = frames_order(c, shape, n_views);
-    F.aov_mask = RTX_AOV_ALL;   // the planes the kernel reads
-    F.aov_depth = c->d_aov_depth;
-    F.aov_normal = c->d_aov_normal;
-    F.aov_material = c->d_aov_material;
-    F.aov_primitive = c->d_aov_primitive;
+    if (const int rc = pass_frame(c, shape, F, grid); rc != RTX_OK) return rc;
     F.occ_bits = c->d_shadow;   // the word the kernel writes, in the frame's layout
     F.lm_lights = trace & all_lights(c);   // (PHASE 9 reads these two as its masks: rtx_kernels.h)
     F.heavy_n = keep & all_lights(c);
-    // the light anchors' cull records, when this is the first launch after an upload (as deferred_prepare)
-    if (!c->facts.deep_stack && !c->facts.hbm_stack && c->dev.cull_stride && cull_lights_due(c)) {
-        FrameArgs L = F;
-        L.n_views = 0;
-        if (const int rc = cull_views(c, L); rc != RTX_OK) return rc;
-    }
     return RTX_OK;
-}
-
-int shadows_prepare(rtx_ctx* c, FrameArgs& F, dim3& grid) {
-    if (const int rc = shadows_checks(c); rc != RTX_OK) return rc;
-    return shadows_build(c, F, grid, all_lights(c), 0u);
 }
 
 int shadows_launch(rtx_ctx* c, const FrameArgs& F, dim3 grid) {
@@ -106,10 +65,21 @@ int shadows_launch(rtx_ctx* c, const FrameArgs& F, dim3 grid) {
     return RTX_OK;
 }
 
-// The plane's validity record: the hit pass it belongs to and the lights it was traced for.
-void shadows_remember(rtx_ctx* c) {
+// What every shadow entry point does once its checks have passed: the record, the launch, and the plane's
+// validity record (the hit pass it belongs to and the lights it was traced for).  With `mean_ms` the
+// timing entry points' form: the record is made once and `iters` launches of it are timed.
+int shadows_pass(rtx_ctx* c, uint32_t trace, uint32_t keep, int iters = 1, float* mean_ms = nullptr) {
+    FrameArgs F;
+    dim3 grid;
+    int rc = shadows_build(c, F, grid, trace, keep);
+    if (rc != RTX_OK) return rc;
+    // (the join and the plane's growth are shadows_build's: outside the timing)
+    rc = mean_ms ? timed_loop(c, iters, mean_ms, [&](int) { return shadows_launch(c, F, grid); })
+                 : shadows_launch(c, F, grid);
+    if (rc != RTX_OK) return rc;
     c->shadow_serial = c->aov_serial;
     c->shadow_lights = c->light_keys;
+    return RTX_OK;
 }
 
 // The plane is the last hit pass's: a pass since then may have another shape, and its rows are what a
@@ -123,7 +93,7 @@ int shadows_current(rtx_ctx* c) {
 
 // ---- the incremental shadow pass ----------------------------------------------------------------
 
-// rtx_update_shadows_async's checks after the pass's own: a current plane, the recorded light count, a mask
+// rtx_update_shadows_async's checks: the pass's own, then a current plane, the recorded light count, a mask
 // inside it, and every light outside the mask where the plane recorded it.  Nothing is changed.
 int update_checks(rtx_ctx* c, uint32_t lights) {
     if (const int rc = shadows_checks(c); rc != RTX_OK) return rc;
@@ -166,92 +136,19 @@ int queue_shadow_copy(rtx_ctx* c, uint32_t* out) {
 
 // ---- the relight --------------------------------------------------------------------------------
 
-// A relight's checks of the last hit pass: deferred shading's (rtx_deferred.hip), plus the shadow plane's
+// A relight's checks of the last hit pass: deferred shading's, in its order, then the shadow plane's
 // validity with shadows on.  Nothing is changed.
 int relight_checks(rtx_ctx* c, const rtx_render_params* p) {
     if (!c || !p) return RTX_E_INVALID;
-    if (p->lighting_mode < 0 || p->lighting_mode >= RTX_MODE_COUNT) return fail(c, RTX_E_INVALID, "bad lighting mode");
-    if (p->format.rshift > 24 || p->format.gshift > 24 || p->format.bshift > 24)
-        return fail(c, RTX_E_INVALID, "bad pixel format");
+    if (const int rc = shade_param_checks(c, p); rc != RTX_OK) return rc;
     if (const int rc = pass_checks(c, "relight"); rc != RTX_OK) return rc;
-    if (c->dev.n_materials < c->aov_last_materials)
-        return fail(c, RTX_E_STATE, "the scene has " + std::to_string(c->dev.n_materials) +
-                                        " materials, the hit pass was traced with " +
-                                        std::to_string(c->aov_last_materials));
-    if (c->dev.n_materials == 0) return fail(c, RTX_E_STATE, "the scene has no material");
+    if (const int rc = material_checks(c); rc != RTX_OK) return rc;
     if (p->shadows_enabled != 0) {
         if (const int rc = shadows_current(c); rc != RTX_OK) return rc;
         if (c->light_keys != c->shadow_lights)
             return fail(c, RTX_E_STATE, "the uploaded lights' count, origins or types are not those the shadow pass was "
                                         "traced for: render the shadow pass again");
     }
-    return RTX_OK;
-}
-
-// The frame buffer and the launch record of a relight of the last hit pass, after relight_checks.  With
-// ss > 0 (rtx_relight_resolve*, after resolve_checks) the pass is the sample frame of the frame `shape`, whose
-// sides and stripes are the pass's divided by k = 1 << ss: A describes the sample frame, its rows and stripes
-// count output rows (one wave walks an output row's k sample rows), and the frame buffer holds the output.
-int relight_build(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, uint32_t ss, RelightArgs& A, dim3& grid,
-                  rtx_render_params& shape) {
-    const bool shadows = p->shadows_enabled != 0;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // behind a pending split chain, which writes the frame buffer this call sizes and writes
-    if (const int rc = join_split(c); rc != RTX_OK) return rc;
-    shape = c->aov_last;
-    shape.lighting_mode = p->lighting_mode;
-    shape.shadows_enabled = p->shadows_enabled;
-    shape.format = p->format;
-    const int n_views = c->aov_last_views;
-    const size_t npx = static_cast<size_t>(shape.width >> ss) * (shape.height >> ss) * static_cast<size_t>(n_views);
-    if (const int rc = frame_buffers(c, npx, want_rgb); rc != RTX_OK) return rc;
-    // the frame's own launch record: its cameras, aspect and reciprocals are the relight's, value for value
-    FrameArgs F;
-    dim3 tiles;
-    frame_shape(c, c->aov_last_cams, n_views, &shape, shape, 0u, F, tiles);
-    std::memset(&A, 0, sizeof A);
-    for (int v = 0; v < n_views; ++v) A.cam[v] = F.cam[v];
-    A.n_views = F.n_views;
-    A.aspect = F.aspect; A.inv_width = F.inv_width; A.inv_height = F.inv_height;
-    A.width = F.width; A.height = F.height;
-    A.mode = F.mode; A.shadows = F.shadows;
-    A.rshift = F.rshift; A.gshift = F.gshift; A.bshift = F.bshift; A.amask = F.amask;
-    A.segs = (F.width + 63u) / 64u;
-    A.rows = F.height;
-    if (F.groups_per_stripe) {   // the largest owner's stripes, row for row (a stripe taller than the frame: its rows)
-        A.stripe_rows = F.groups_per_stripe * kWaveTile;
-        A.stripe_first = F.stripe_first; A.stripe_step = F.stripe_step;
-        if (A.stripe_rows < F.height) A.rows = F.tiles_y * kWaveTile;
-    }
-    A.depth = c->d_aov_depth;
-    A.normal = c->d_aov_normal;
-    A.material = c->d_aov_material;
-    A.primitive = c->d_aov_primitive;
-    A.shadow = shadows ? c->d_shadow.get() : nullptr;
-    A.out_px = c->d_px;
-    A.out_rgb = want_rgb ? c->d_rgb.get() : nullptr;
-    // (the resolve's divisions are exact: the sides by resolve_checks, a striped pass's stripe and owned rows as
-    // multiples of 16 k.  An unstriped pass's stripe_rows means nothing and may be anything: the output's record is 0.)
-    A.rows >>= ss; A.stripe_rows >>= ss;
-    shape.width >>= ss; shape.height >>= ss;
-    if (ss) shape.stripe_rows = F.groups_per_stripe ? shape.stripe_rows >> ss : 0u;
-    const uint32_t waves = A.segs * A.rows * A.n_views, per = kRelightThreads / 64u;
-    grid = dim3((waves + per - 1) / per, 1, 1);
-    return RTX_OK;
-}
-
-int relight_prepare(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, RelightArgs& A, dim3& grid,
-                    rtx_render_params& shape) {
-    if (const int rc = relight_checks(c, p); rc != RTX_OK) return rc;
-    return relight_build(c, p, want_rgb, 0u, A, grid, shape);
-}
-
-// ss = 0: the relight; else the resolved relight of factor 1 << ss.
-int relight_launch(rtx_ctx* c, const RelightArgs& A, dim3 grid, uint32_t ss = 0u) {
-    if (grid.x == 0) return RTX_OK;
-    if (ss) launch_relight_resolve(ss, grid, c->stream, c->dev, A);
-    else launch_relight(grid, c->stream, c->dev, A);
-    HIP_TRY(c, hipGetLastError());
     return RTX_OK;
 }
 
@@ -274,30 +171,89 @@ int resolve_checks(rtx_ctx* c, const rtx_render_params* p, uint32_t k, uint32_t&
     return RTX_OK;
 }
 
+// The frame buffer and the launch record of a relight of the last hit pass, after relight_checks.  With
+// ss > 0 (rtx_relight_resolve*, after resolve_checks) the pass is the sample frame of the frame `shape`, whose
+// sides and stripes are the pass's divided by k = 1 << ss: A describes the sample frame, its rows and stripes
+// count output rows (one wave walks an output row's k sample rows), and the frame buffer holds the output.
+int relight_build(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, uint32_t ss, RelightArgs& A, dim3& grid,
+                  rtx_render_params& shape) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    // behind a pending split chain, which writes the frame buffer this call sizes and writes
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    shape = pass_shape(c, p);
+    const int n_views = c->aov_last_views;
+    const size_t npx = static_cast<size_t>(shape.width >> ss) * (shape.height >> ss) * static_cast<size_t>(n_views);
+    if (const int rc = frame_buffers(c, npx, want_rgb); rc != RTX_OK) return rc;
+    // the frame's own launch record: its cameras, aspect and reciprocals are the relight's, value for value
+    FrameArgs F;
+    dim3 tiles;
+    frame_shape(c, c->aov_last_cams, n_views, &shape, shape, 0u, F, tiles);
+    std::memset(&A, 0, sizeof A);
+    for (int v = 0; v < n_views; ++v) A.cam[v] = F.cam[v];
+    A.n_views = F.n_views;
+    A.aspect = F.aspect; A.inv_width = F.inv_width; A.inv_height = F.inv_height;
+    A.width = F.width; A.height = F.height;
+    A.mode = F.mode; A.shadows = F.shadows;
+    A.rshift = F.rshift; A.gshift = F.gshift; A.bshift = F.bshift; A.amask = F.amask;
+    A.segs = (F.width + 63u) / 64u;
+    A.rows = F.height;
+    if (F.groups_per_stripe) {   // the largest owner's stripes, row for row (a stripe taller than the frame: its rows)
+        A.stripe_rows = F.groups_per_stripe * kWaveTile;
+        A.stripe_first = F.stripe_first; A.stripe_step = F.stripe_step;
+        if (A.stripe_rows < F.height) A.rows = F.tiles_y * kWaveTile;
+    }
+    const rtx_aov_planes d = device_planes(c);
+    A.depth = d.depth; A.normal = d.normal; A.material = d.material; A.primitive = d.primitive;
+    A.shadow = p->shadows_enabled != 0 ? c->d_shadow.get() : nullptr;
+    A.out_px = c->d_px;
+    A.out_rgb = want_rgb ? c->d_rgb.get() : nullptr;
+    // (the resolve's divisions are exact: the sides by resolve_checks, a striped pass's stripe and owned rows as
+    // multiples of 16 k.  An unstriped pass's stripe_rows means nothing and may be anything: the output's record is 0.)
+    A.rows >>= ss; A.stripe_rows >>= ss;
+    shape.width >>= ss; shape.height >>= ss;
+    if (ss) shape.stripe_rows = F.groups_per_stripe ? shape.stripe_rows >> ss : 0u;
+    const uint32_t waves = A.segs * A.rows * A.n_views, per = kRelightThreads / 64u;
+    grid = dim3((waves + per - 1) / per, 1, 1);
+    return RTX_OK;
+}
+
+// ss = 0: the relight; else the resolved relight of factor 1 << ss.
+int relight_launch(rtx_ctx* c, const RelightArgs& A, dim3 grid, uint32_t ss) {
+    if (grid.x == 0) return RTX_OK;
+    if (ss) launch_relight_resolve(ss, grid, c->stream, c->dev, A);
+    else launch_relight(grid, c->stream, c->dev, A);
+    HIP_TRY(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// What the relight and its resolve (ss > 0) do once their checks have passed: the record, the launch and the
+// record of the frame now in the frame buffer.  With `mean_ms` the timing entry points' form, as shadows_pass.
+int relight_pass(rtx_ctx* c, const rtx_render_params* p, bool want_rgb, uint32_t ss, int iters = 1,
+                 float* mean_ms = nullptr) {
+    RelightArgs A;
+    dim3 grid;
+    rtx_render_params shape;
+    int rc = relight_build(c, p, want_rgb, ss, A, grid, shape);
+    if (rc != RTX_OK) return rc;
+    // (the join and the frame buffer's growth are relight_build's: outside the timing)
+    rc = mean_ms ? timed_loop(c, iters, mean_ms, [&](int) { return relight_launch(c, A, grid, ss); })
+                 : relight_launch(c, A, grid, ss);
+    if (rc != RTX_OK) return rc;
+    remember(c, &shape, c->aov_last_views, want_rgb);
+    return RTX_OK;
+}
+
 }  // namespace
 
 extern "C" int rtx_render_shadows_async(rtx_ctx* c) {
-    FrameArgs F;
-    dim3 grid;
-    int rc = shadows_prepare(c, F, grid);
-    if (rc != RTX_OK) return rc;
-    rc = shadows_launch(c, F, grid);
-    if (rc != RTX_OK) return rc;
-    shadows_remember(c);
-    return RTX_OK;
+    if (const int rc = shadows_checks(c); rc != RTX_OK) return rc;
+    return shadows_pass(c, all_lights(c), 0u);
 }
 
 extern "C" int rtx_update_shadows_async(rtx_ctx* c, uint32_t lights) {
     if (const int rc = update_checks(c, lights); rc != RTX_OK) return rc;
     if (!lights) return RTX_OK;   // (nothing named and, by the checks, nothing changed)
-    FrameArgs F;
-    dim3 grid;
-    int rc = shadows_build(c, F, grid, lights, ~lights);
-    if (rc != RTX_OK) return rc;
-    rc = shadows_launch(c, F, grid);
-    if (rc != RTX_OK) return rc;
-    shadows_remember(c);
-    return RTX_OK;
+    return shadows_pass(c, lights, ~lights);
 }
 
 extern "C" int rtx_refresh_shadows_async(rtx_ctx* c, uint32_t* traced) {
@@ -308,38 +264,23 @@ extern "C" int rtx_refresh_shadows_async(rtx_ctx* c, uint32_t* traced) {
         if (traced) *traced = 0u;
         return RTX_OK;
     }
-    FrameArgs F;
-    dim3 grid;
-    int rc = shadows_build(c, F, grid, trace, merge ? ~trace : 0u);
-    if (rc != RTX_OK) return rc;
-    rc = shadows_launch(c, F, grid);
-    if (rc != RTX_OK) return rc;
-    shadows_remember(c);
+    if (const int rc = shadows_pass(c, trace, merge ? ~trace : 0u); rc != RTX_OK) return rc;
     if (traced) *traced = trace;
     return RTX_OK;
+}
+
+extern "C" int rtx_time_shadows(rtx_ctx* c, int iters, float* mean_ms) {
+    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
+    if (const int rc = shadows_checks(c); rc != RTX_OK) return rc;
+    return shadows_pass(c, all_lights(c), 0u, iters, mean_ms);
 }
 
 extern "C" int rtx_time_shadows_update(rtx_ctx* c, uint32_t lights, int iters, float* mean_ms) {
     if (!mean_ms || iters <= 0) return RTX_E_INVALID;
     if (const int rc = update_checks(c, lights); rc != RTX_OK) return rc;
     *mean_ms = 0.f;
-    if (!lights) return RTX_OK;
-    FrameArgs F;
-    dim3 grid;
-    int rc = shadows_build(c, F, grid, lights, ~lights);
-    if (rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        rc = shadows_launch(c, F, grid);
-        if (rc != RTX_OK) return rc;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
-    shadows_remember(c);
-    return RTX_OK;
+    if (!lights) return RTX_OK;   // an empty mask launches nothing, as the update: exactly 0 ms
+    return shadows_pass(c, lights, ~lights, iters, mean_ms);
 }
 
 extern "C" int rtx_gather_shadows_async(rtx_ctx* c, uint32_t* out) { return queue_shadow_copy(c, out); }
@@ -357,36 +298,9 @@ extern "C" int rtx_device_shadow_buffer(rtx_ctx* c, uint32_t** d) {
     return RTX_OK;
 }
 
-extern "C" int rtx_time_shadows(rtx_ctx* c, int iters, float* mean_ms) {
-    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
-    FrameArgs F;
-    dim3 grid;
-    int rc = shadows_prepare(c, F, grid);
-    if (rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        rc = shadows_launch(c, F, grid);
-        if (rc != RTX_OK) return rc;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
-    shadows_remember(c);
-    return RTX_OK;
-}
-
 extern "C" int rtx_relight_async(rtx_ctx* c, const rtx_render_params* p, int want_rgb) {
-    RelightArgs A;
-    dim3 grid;
-    rtx_render_params shape;
-    int rc = relight_prepare(c, p, want_rgb != 0, A, grid, shape);
-    if (rc != RTX_OK) return rc;
-    rc = relight_launch(c, A, grid);
-    if (rc != RTX_OK) return rc;
-    remember(c, &shape, c->aov_last_views, want_rgb != 0);
-    return RTX_OK;
+    if (const int rc = relight_checks(c, p); rc != RTX_OK) return rc;
+    return relight_pass(c, p, want_rgb != 0, 0u);
 }
 
 extern "C" int rtx_relight(rtx_ctx* c, const rtx_render_params* p, uint32_t* out_px, float* out_rgb) {
@@ -396,18 +310,16 @@ extern "C" int rtx_relight(rtx_ctx* c, const rtx_render_params* p, uint32_t* out
     return rtx_download(c, out_px, out_rgb);
 }
 
+extern "C" int rtx_time_relight(rtx_ctx* c, const rtx_render_params* p, int want_rgb, int iters, float* mean_ms) {
+    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
+    if (const int rc = relight_checks(c, p); rc != RTX_OK) return rc;
+    return relight_pass(c, p, want_rgb != 0, 0u, iters, mean_ms);
+}
+
 extern "C" int rtx_relight_resolve_async(rtx_ctx* c, const rtx_render_params* p, uint32_t k, int want_rgb) {
     uint32_t ss = 0;
     if (const int rc = resolve_checks(c, p, k, ss); rc != RTX_OK) return rc;
-    RelightArgs A;
-    dim3 grid;
-    rtx_render_params shape;
-    int rc = relight_build(c, p, want_rgb != 0, ss, A, grid, shape);
-    if (rc != RTX_OK) return rc;
-    rc = relight_launch(c, A, grid, ss);
-    if (rc != RTX_OK) return rc;
-    remember(c, &shape, c->aov_last_views, want_rgb != 0);
-    return RTX_OK;
+    return relight_pass(c, p, want_rgb != 0, ss);
 }
 
 extern "C" int rtx_relight_resolve(rtx_ctx* c, const rtx_render_params* p, uint32_t k, uint32_t* out_px, float* out_rgb) {
@@ -422,42 +334,5 @@ extern "C" int rtx_time_relight_resolve(rtx_ctx* c, const rtx_render_params* p, 
     if (!mean_ms || iters <= 0) return RTX_E_INVALID;
     uint32_t ss = 0;
     if (const int rc = resolve_checks(c, p, k, ss); rc != RTX_OK) return rc;
-    RelightArgs A;
-    dim3 grid;
-    rtx_render_params shape;
-    int rc = relight_build(c, p, want_rgb != 0, ss, A, grid, shape);
-    if (rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        rc = relight_launch(c, A, grid, ss);
-        if (rc != RTX_OK) return rc;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
-    remember(c, &shape, c->aov_last_views, want_rgb != 0);
-    return RTX_OK;
-}
-
-extern "C" int rtx_time_relight(rtx_ctx* c, const rtx_render_params* p, int want_rgb, int iters, float* mean_ms) {
-    if (!mean_ms || iters <= 0) return RTX_E_INVALID;
-    RelightArgs A;
-    dim3 grid;
-    rtx_render_params shape;
-    int rc = relight_prepare(c, p, want_rgb != 0, A, grid, shape);
-    if (rc != RTX_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        rc = relight_launch(c, A, grid);
-        if (rc != RTX_OK) return rc;
-    }
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *mean_ms = ms / static_cast<float>(iters);
-    remember(c, &shape, c->aov_last_views, want_rgb != 0);
-    return RTX_OK;
+    return relight_pass(c, p, want_rgb != 0, ss, iters, mean_ms);
 }

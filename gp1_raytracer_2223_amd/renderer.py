@@ -47,6 +47,10 @@ def aov_struct(planes: dict) -> abi.AovPlanes:
     return out
 
 
+def _u32p(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
 class LightingMode:
     ObservedArea, Radiance, BRDF, Combined, Count = 0, 1, 2, 3, 4
 
@@ -77,59 +81,66 @@ class DeviceContext:
         except Exception:
             pass
 
+    def _call(self, name: str, *args) -> None:
+        """Entry point `name` on this context; anything but RTX_OK raises with the context's last error."""
+        abi.check(getattr(self.lib, name)(self.h, *args), name, self.h)
+
+    def _timed(self, name: str, iters: int, *args) -> float:
+        """An rtx_time_* entry point, whose last two arguments are `iters` and the mean's address: the mean in ms."""
+        ms = C.c_float()
+        self._call(name, *args, int(iters), C.byref(ms))
+        return ms.value
+
+    @staticmethod
+    def _pixels(n: int, want_rgb: bool, px: np.ndarray | None = None):
+        """The outputs of a frame of n pixels, (px, rgb, their pointers): `px` or a zeroed uint32[n], and a zeroed
+        float32[3n] or, without want_rgb, None and NULL."""
+        if px is None:
+            px = np.zeros(n, np.uint32)
+        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
+        return px, rgb, _u32p(px), rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None
+
+    def _frame(self, name: str, n: int, want_rgb: bool, *args, px: np.ndarray | None = None):
+        """A blocking frame of n pixels by entry point `name`, whose last two arguments are the outputs: (px, rgb)."""
+        px, rgb, pxp, rgbp = self._pixels(n, want_rgb, px)
+        self._call(name, *args, pxp, rgbp)
+        return px, rgb
+
     def upload(self, scene: abi.Scene) -> None:
-        abi.check(self.lib.rtx_upload_scene(self.h, C.byref(scene)), "rtx_upload_scene", self.h)
+        self._call("rtx_upload_scene", C.byref(scene))
 
     def set_supersample(self, k: int) -> None:
         """k x k samples per pixel (1, 2, 4 or 8) for every later frame (rtx_set_supersample)."""
-        abi.check(self.lib.rtx_set_supersample(self.h, int(k)), "rtx_set_supersample", self.h)
+        self._call("rtx_set_supersample", int(k))
 
     def render(self, cam: abi.Camera, params: abi.RenderParams, want_rgb: bool = True):
-        n = params.width * params.height
-        px = np.zeros(n, np.uint32)
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.lib.rtx_render(self.h, C.byref(cam), C.byref(params),
-                                 px.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                 rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_render", self.h)
-        return px, rgb
+        return self._frame("rtx_render", params.width * params.height, want_rgb, C.byref(cam), C.byref(params))
 
     def render_adaptive(self, cam: abi.Camera, params: abi.RenderParams, k: int, threshold: int,
                         want_rgb: bool = True):
         """Adaptive supersampling (rtx_render_adaptive), blocking: the plain frame with k x k samples
         (k = 2, 4, 8) for the pixels that differ from a 4-neighbour by more than `threshold` (0..255) in a
         channel; (pixels, rgb) like render()."""
-        n = params.width * params.height
-        px = np.zeros(n, np.uint32)
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.lib.rtx_render_adaptive(self.h, C.byref(cam), C.byref(params), int(k), int(threshold),
-                                          px.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                          rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_render_adaptive", self.h)
-        return px, rgb
+        return self._frame("rtx_render_adaptive", params.width * params.height, want_rgb, C.byref(cam),
+                           C.byref(params), int(k), int(threshold))
 
     def render_adaptive_async(self, cam, params, k: int, threshold: int, want_rgb: bool = False) -> None:
-        abi.check(self.lib.rtx_render_adaptive_async(self.h, C.byref(cam), C.byref(params), int(want_rgb), int(k),
-                                                     int(threshold)), "rtx_render_adaptive_async", self.h)
+        self._call("rtx_render_adaptive_async", C.byref(cam), C.byref(params), int(want_rgb), int(k), int(threshold))
 
     def adaptive_refined(self) -> int:
         """The pixels the last adaptive frame refined (rtx_adaptive_refined; waits for the stream)."""
         n = C.c_uint32()
-        abi.check(self.lib.rtx_adaptive_refined(self.h, C.byref(n)), "rtx_adaptive_refined", self.h)
+        self._call("rtx_adaptive_refined", C.byref(n))
         return n.value
 
     def time_adaptive_frames(self, cam, params, k: int, threshold: int, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_adaptive_frames(self.h, C.byref(cam), C.byref(params), int(k), int(threshold),
-                                                    int(iters), C.byref(ms)), "rtx_time_adaptive_frames", self.h)
-        return ms.value
+        return self._timed("rtx_time_adaptive_frames", iters, C.byref(cam), C.byref(params), int(k), int(threshold))
 
     def render_async(self, cam, params, want_rgb=False):
-        abi.check(self.lib.rtx_render_async(self.h, C.byref(cam), C.byref(params), int(want_rgb)),
-                  "rtx_render_async", self.h)
+        self._call("rtx_render_async", C.byref(cam), C.byref(params), int(want_rgb))
 
     def synchronize(self):
-        abi.check(self.lib.rtx_synchronize(self.h), "rtx_synchronize", self.h)
+        self._call("rtx_synchronize")
 
     def gather_async(self, out_px: np.ndarray, out_rgb: np.ndarray | None = None) -> None:
         """Queue the D2H copy of the rows the last render owns into full-frame host arrays
@@ -139,16 +150,14 @@ class DeviceContext:
         if out_rgb is not None:
             assert out_rgb.dtype == np.float32 and out_rgb.flags.c_contiguous
             rgbp = out_rgb.ctypes.data_as(C.POINTER(C.c_float))
-        abi.check(self.lib.rtx_gather_async(self.h, out_px.ctypes.data_as(C.POINTER(C.c_uint32)), rgbp),
-                  "rtx_gather_async", self.h)
+        self._call("rtx_gather_async", _u32p(out_px), rgbp)
 
     def render_aov(self, cam: abi.Camera, params: abi.RenderParams, mask: int = AOV_ALL) -> dict:
         """The hit pass (rtx_render_aov), blocking: {"depth", "normal", "material", "primitive"} ->
         flat numpy planes, those of `mask` (include/rtx.h gives their values)."""
         planes = aov_host_planes(params.width, params.height, mask)
         out = aov_struct(planes)
-        abi.check(self.lib.rtx_render_aov(self.h, C.byref(cam), C.byref(params), int(mask), C.byref(out)),
-                  "rtx_render_aov", self.h)
+        self._call("rtx_render_aov", C.byref(cam), C.byref(params), int(mask), C.byref(out))
         self._aov_shape = (params.width, params.height, 1)
         return planes
 
@@ -157,33 +166,32 @@ class DeviceContext:
         if isinstance(cams, abi.Camera):
             cams = [cams]
         arr = (abi.Camera * len(cams))(*cams)
-        abi.check(self.lib.rtx_render_aov_async(self.h, arr, len(cams), C.byref(params), int(mask)),
-                  "rtx_render_aov_async", self.h)
+        self._call("rtx_render_aov_async", arr, len(cams), C.byref(params), int(mask))
         self._aov_shape = (params.width, params.height, len(cams))
 
     def gather_aov_async(self, planes: dict) -> None:
         """Queue the D2H copy of the rows the last hit pass owns into full-frame host planes
         (rtx_gather_aov_async); complete after synchronize()."""
         out = aov_struct(planes)
-        abi.check(self.lib.rtx_gather_aov_async(self.h, C.byref(out)), "rtx_gather_aov_async", self.h)
+        self._call("rtx_gather_aov_async", C.byref(out))
 
     def download_aov(self, planes: dict) -> dict:
         """Copy the last hit pass's owned rows into `planes` and wait (rtx_download_aov)."""
         out = aov_struct(planes)
-        abi.check(self.lib.rtx_download_aov(self.h, C.byref(out)), "rtx_download_aov", self.h)
+        self._call("rtx_download_aov", C.byref(out))
         return planes
 
     def device_aov_buffers(self) -> dict:
         """Device addresses of the HBM planes (0 for a plane no mask has named yet)."""
         out = abi.AovPlanes()
-        abi.check(self.lib.rtx_device_aov_buffers(self.h, C.byref(out)), "rtx_device_aov_buffers", self.h)
+        self._call("rtx_device_aov_buffers", C.byref(out))
         return {k: C.cast(getattr(out, k), C.c_void_p).value or 0 for k in AOV_PLANES}
 
     def device_buffers(self) -> tuple[int, int]:
         """Device addresses (d_px, d_rgb) of the colour frame buffer (rtx_device_buffers; 0 for a plane
         no frame has asked for yet).  A larger frame reallocates them: fetch them afresh."""
         px, rgb = C.c_void_p(), C.c_void_p()
-        abi.check(self.lib.rtx_device_buffers(self.h, C.byref(px), C.byref(rgb)), "rtx_device_buffers", self.h)
+        self._call("rtx_device_buffers", C.byref(px), C.byref(rgb))
         return px.value or 0, rgb.value or 0
 
     @staticmethod
@@ -202,8 +210,7 @@ class DeviceContext:
         n = a.shape[0]
         planes = {k: np.zeros(e * n, dt) for k, (bit, dt, e) in AOV_PLANES.items() if mask & bit}
         out = aov_struct(planes)
-        abi.check(self.lib.rtx_trace_rays(self.h, a.ctypes.data_as(C.POINTER(abi.Ray)), n, int(mask), C.byref(out)),
-                  "rtx_trace_rays", self.h)
+        self._call("rtx_trace_rays", a.ctypes.data_as(C.POINTER(abi.Ray)), n, int(mask), C.byref(out))
         return planes
 
     def occluded(self, rays) -> np.ndarray:
@@ -212,8 +219,7 @@ class DeviceContext:
         a = self._rays(rays)
         n = a.shape[0]
         out = np.zeros(n, np.uint8)
-        abi.check(self.lib.rtx_occluded(self.h, a.ctypes.data_as(C.POINTER(abi.Ray)), n,
-                                        out.ctypes.data_as(C.POINTER(C.c_uint8))), "rtx_occluded", self.h)
+        self._call("rtx_occluded", a.ctypes.data_as(C.POINTER(abi.Ray)), n, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         return out
 
     def trace_rays_device(self, d_rays: int, n: int, mask: int, d_planes: dict) -> None:
@@ -224,13 +230,11 @@ class DeviceContext:
             if d_planes.get(k):
                 setattr(out, k, C.cast(C.c_void_p(int(d_planes[k])),
                                        C.POINTER(C.c_float if dt == np.float32 else C.c_uint32)))
-        abi.check(self.lib.rtx_trace_rays_device(self.h, C.c_void_p(int(d_rays)), int(n), int(mask), C.byref(out)),
-                  "rtx_trace_rays_device", self.h)
+        self._call("rtx_trace_rays_device", C.c_void_p(int(d_rays)), int(n), int(mask), C.byref(out))
 
     def occluded_device(self, d_rays: int, n: int, d_out: int) -> None:
         """rtx_occluded_device: device addresses; queued, complete after synchronize()."""
-        abi.check(self.lib.rtx_occluded_device(self.h, C.c_void_p(int(d_rays)), int(n), C.c_void_p(int(d_out))),
-                  "rtx_occluded_device", self.h)
+        self._call("rtx_occluded_device", C.c_void_p(int(d_rays)), int(n), C.c_void_p(int(d_out)))
 
     def shade_rays(self, rays, params: abi.RenderParams):
         """Renderer::RenderPixel from GetClosestHit on for caller-supplied rays (rtx_shade_rays), blocking:
@@ -239,38 +243,28 @@ class DeviceContext:
         receives -direction as given (include/rtx.h)."""
         a = self._rays(rays)
         n = a.shape[0]
-        px, rgb = np.zeros(n, np.uint32), np.zeros(3 * n, np.float32)
-        abi.check(self.lib.rtx_shade_rays(self.h, a.ctypes.data_as(C.POINTER(abi.Ray)), n, C.byref(params),
-                                          px.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                          rgb.ctypes.data_as(C.POINTER(C.c_float))), "rtx_shade_rays", self.h)
-        return px, rgb
+        return self._frame("rtx_shade_rays", n, True, a.ctypes.data_as(C.POINTER(abi.Ray)), n, C.byref(params))
 
     def shade_rays_device(self, d_rays: int, n: int, params: abi.RenderParams, d_pixels: int = 0, d_rgb: int = 0) -> None:
         """rtx_shade_rays_device: device addresses (0 = that output is not asked for); queued, complete
         after synchronize()."""
-        abi.check(self.lib.rtx_shade_rays_device(self.h, C.c_void_p(int(d_rays)), int(n), C.byref(params),
-                                                 C.c_void_p(int(d_pixels) or None), C.c_void_p(int(d_rgb) or None)),
-                  "rtx_shade_rays_device", self.h)
+        self._call("rtx_shade_rays_device", C.c_void_p(int(d_rays)), int(n), C.byref(params),
+                   C.c_void_p(int(d_pixels) or None), C.c_void_p(int(d_rgb) or None))
 
     def time_shade_rays(self, d_rays: int, n: int, params: abi.RenderParams, d_pixels: int, d_rgb: int,
                         iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_shade_rays(self.h, C.c_void_p(int(d_rays)), int(n), C.byref(params),
-                                               C.c_void_p(int(d_pixels) or None), C.c_void_p(int(d_rgb) or None),
-                                               int(iters), C.byref(ms)), "rtx_time_shade_rays", self.h)
-        return ms.value
+        return self._timed("rtx_time_shade_rays", iters, C.c_void_p(int(d_rays)), int(n), C.byref(params),
+                           C.c_void_p(int(d_pixels) or None), C.c_void_p(int(d_rgb) or None))
 
     def time_aov_frames(self, cam, params, mask: int, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_aov_frames(self.h, C.byref(cam), C.byref(params), int(mask), int(iters),
-                                               C.byref(ms)), "rtx_time_aov_frames", self.h)
+        ms = self._timed("rtx_time_aov_frames", iters, C.byref(cam), C.byref(params), int(mask))
         self._aov_shape = (params.width, params.height, 1)
-        return ms.value
+        return ms
 
     def shade_aov_async(self, params: abi.RenderParams, want_rgb: bool = False) -> None:
         """Queue deferred shading of the last hit pass into the colour frame buffer (rtx_shade_aov_async):
         `params` supplies the lighting mode, shadows and pixel format, the pass everything else."""
-        abi.check(self.lib.rtx_shade_aov_async(self.h, C.byref(params), int(want_rgb)), "rtx_shade_aov_async", self.h)
+        self._call("rtx_shade_aov_async", C.byref(params), int(want_rgb))
 
     def shade_aov(self, params: abi.RenderParams, want_rgb: bool = True):
         """Deferred shading of the last hit pass (rtx_shade_aov), blocking: (pixels, rgb) like render(), of
@@ -278,20 +272,10 @@ class DeviceContext:
         not own stay zero)."""
         if self._aov_shape is None:   # no pass through this object: the library says why
             self.shade_aov_async(params, want_rgb)
-            raise RuntimeError("shade_aov: the last hit pass was not queued through this object, its size is unknown")
-        n = self._aov_shape[0] * self._aov_shape[1] * self._aov_shape[2]
-        px = np.zeros(n, np.uint32)
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.lib.rtx_shade_aov(self.h, C.byref(params), px.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                    rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_shade_aov", self.h)
-        return px, rgb
+        return self._frame("rtx_shade_aov", self._pass_pixels("shade_aov"), want_rgb, C.byref(params))
 
     def time_shade_aov(self, params: abi.RenderParams, want_rgb: bool, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_shade_aov(self.h, C.byref(params), int(want_rgb), int(iters), C.byref(ms)),
-                  "rtx_time_shade_aov", self.h)
-        return ms.value
+        return self._timed("rtx_time_shade_aov", iters, C.byref(params), int(want_rgb))
 
     def _pass_pixels(self, what: str) -> int:
         if self._aov_shape is None:
@@ -301,20 +285,19 @@ class DeviceContext:
     def render_shadows_async(self) -> None:
         """Queue the shadow pass of the last hit pass (rtx_render_shadows_async): per pixel one word whose bit
         l says that light l of the uploaded scene is occluded, kept in HBM for relight()."""
-        abi.check(self.lib.rtx_render_shadows_async(self.h), "rtx_render_shadows_async", self.h)
+        self._call("rtx_render_shadows_async")
 
     def update_shadows_async(self, lights: int) -> None:
         """Queue the shadow pass for the lights named in `lights` only (bit l = light l) and merge their bits
         into the plane (rtx_update_shadows_async); every other light must be where the plane recorded it."""
-        abi.check(self.lib.rtx_update_shadows_async(self.h, int(lights) & 0xFFFFFFFF), "rtx_update_shadows_async",
-                  self.h)
+        self._call("rtx_update_shadows_async", int(lights) & 0xFFFFFFFF)
 
     def refresh_shadows_async(self) -> int:
         """Make the plane valid for the uploaded lights at the least cost (rtx_refresh_shadows_async): the
         full pass without a current plane, else one launch over the lights that changed.  Returns the mask
         of the lights traced (0: nothing was launched, or only removed lights' bits were cleared)."""
         traced = C.c_uint32()
-        abi.check(self.lib.rtx_refresh_shadows_async(self.h, C.byref(traced)), "rtx_refresh_shadows_async", self.h)
+        self._call("rtx_refresh_shadows_async", C.byref(traced))
         return traced.value
 
     def download_shadows(self, out: np.ndarray | None = None) -> np.ndarray:
@@ -322,18 +305,16 @@ class DeviceContext:
         rows the pass does not own keep what `out` held (zero in a new array)."""
         if out is None:
             out = np.zeros(self._pass_pixels("download_shadows"), np.uint32)
-        abi.check(self.lib.rtx_download_shadows(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))),
-                  "rtx_download_shadows", self.h)
+        self._call("rtx_download_shadows", _u32p(out))
         return out
 
     def gather_shadows_async(self, out: np.ndarray) -> None:
-        abi.check(self.lib.rtx_gather_shadows_async(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))),
-                  "rtx_gather_shadows_async", self.h)
+        self._call("rtx_gather_shadows_async", _u32p(out))
 
     def device_shadow_buffer(self) -> int:
         """Device address of the shadow plane (0 before the first shadow pass)."""
         d = C.POINTER(C.c_uint32)()
-        abi.check(self.lib.rtx_device_shadow_buffer(self.h, C.byref(d)), "rtx_device_shadow_buffer", self.h)
+        self._call("rtx_device_shadow_buffer", C.byref(d))
         return C.cast(d, C.c_void_p).value or 0
 
     # ---- scene edits (rtx_edit_*): light and material records of the current image replaced in place
@@ -350,50 +331,41 @@ class DeviceContext:
         place and queued (rtx_edit_lights); the types must be the uploaded ones.  After a light moved, relight()
         with shadows needs update_shadows_async or refresh_shadows_async first, as after an upload."""
         arr = self._records(lights, abi.Light)
-        abi.check(self.lib.rtx_edit_lights(self.h, int(first), len(arr), arr), "rtx_edit_lights", self.h)
+        self._call("rtx_edit_lights", int(first), len(arr), arr)
 
     def edit_materials(self, first: int, materials) -> None:
         """Materials first .. first+len-1 take the given values in place (rtx_edit_materials); kinds as uploaded."""
         arr = self._records(materials, abi.Material)
-        abi.check(self.lib.rtx_edit_materials(self.h, int(first), len(arr), arr), "rtx_edit_materials", self.h)
+        self._call("rtx_edit_materials", int(first), len(arr), arr)
 
     def edit_light_values_device(self, first: int, n: int, d_ptr: int) -> None:
         """The colour and intensity of lights first .. first+n-1 from device memory: 4 floats a light, {color[3],
         intensity}, at device address `d_ptr` (rtx_edit_light_values_device).  Queued: the memory stays valid
         until the context's stream has passed the edit."""
-        abi.check(self.lib.rtx_edit_light_values_device(self.h, int(first), int(n), int(d_ptr) or None),
-                  "rtx_edit_light_values_device", self.h)
+        self._call("rtx_edit_light_values_device", int(first), int(n), int(d_ptr) or None)
 
     def edit_material_values_device(self, first: int, n: int, d_ptr: int) -> None:
         """The values of materials first .. first+n-1 from device memory: 8 floats a material, {color[3], kd, ks,
         exponent, metalness, roughness} (rtx_edit_material_values_device); the Lambert term is computed on the
         device, bit for bit the host form's."""
-        abi.check(self.lib.rtx_edit_material_values_device(self.h, int(first), int(n), int(d_ptr) or None),
-                  "rtx_edit_material_values_device", self.h)
+        self._call("rtx_edit_material_values_device", int(first), int(n), int(d_ptr) or None)
 
     def relight_async(self, params: abi.RenderParams, want_rgb: bool = False) -> None:
         """Queue the relight of the last hit pass into the colour frame buffer (rtx_relight_async): `params`
         supplies the lighting mode, shadows and pixel format; with shadows the shadow plane answers DoesHit."""
-        abi.check(self.lib.rtx_relight_async(self.h, C.byref(params), int(want_rgb)), "rtx_relight_async", self.h)
+        self._call("rtx_relight_async", C.byref(params), int(want_rgb))
 
     def relight(self, params: abi.RenderParams, want_rgb: bool = True):
         """The relight (rtx_relight), blocking: (pixels, rgb) like shade_aov()."""
         if self._aov_shape is None:   # no pass through this object: the library says why
             self.relight_async(params, want_rgb)
-        n = self._pass_pixels("relight")
-        px = np.zeros(n, np.uint32)
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.lib.rtx_relight(self.h, C.byref(params), px.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                  rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_relight", self.h)
-        return px, rgb
+        return self._frame("rtx_relight", self._pass_pixels("relight"), want_rgb, C.byref(params))
 
     def relight_resolve_async(self, params: abi.RenderParams, k: int, want_rgb: bool = False) -> None:
         """Queue the resolved relight (rtx_relight_resolve_async): the last hit pass of k*W x k*H is read as the
         sample frame of a W x H frame, every sample is relit and each pixel's k x k samples are box-filtered as
         rtx_set_supersample(k) defines; the frame buffer then holds the W x H frame."""
-        abi.check(self.lib.rtx_relight_resolve_async(self.h, C.byref(params), int(k), int(want_rgb)),
-                  "rtx_relight_resolve_async", self.h)
+        self._call("rtx_relight_resolve_async", C.byref(params), int(k), int(want_rgb))
 
     def relight_resolve(self, params: abi.RenderParams, k: int, want_rgb: bool = True):
         """The resolved relight (rtx_relight_resolve), blocking: (pixels, rgb) of W*H*views pixels."""
@@ -403,53 +375,33 @@ class DeviceContext:
             raise RuntimeError("relight_resolve: the last hit pass was not queued through this object, its size is "
                                "unknown")
         n = (self._aov_shape[0] // k) * (self._aov_shape[1] // k) * self._aov_shape[2]
-        px = np.zeros(n, np.uint32)
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.lib.rtx_relight_resolve(self.h, C.byref(params), int(k), px.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                          rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_relight_resolve", self.h)
-        return px, rgb
+        return self._frame("rtx_relight_resolve", n, want_rgb, C.byref(params), int(k))
 
     def time_relight_resolve(self, params: abi.RenderParams, k: int, want_rgb: bool, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_relight_resolve(self.h, C.byref(params), int(k), int(want_rgb), int(iters),
-                                                    C.byref(ms)), "rtx_time_relight_resolve", self.h)
-        return ms.value
+        return self._timed("rtx_time_relight_resolve", iters, C.byref(params), int(k), int(want_rgb))
 
     def time_shadows(self, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_shadows(self.h, int(iters), C.byref(ms)), "rtx_time_shadows", self.h)
-        return ms.value
+        return self._timed("rtx_time_shadows", iters)
 
     def time_shadows_update(self, lights: int, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_shadows_update(self.h, int(lights) & 0xFFFFFFFF, int(iters), C.byref(ms)),
-                  "rtx_time_shadows_update", self.h)
-        return ms.value
+        return self._timed("rtx_time_shadows_update", iters, int(lights) & 0xFFFFFFFF)
 
     def time_relight(self, params: abi.RenderParams, want_rgb: bool, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_relight(self.h, C.byref(params), int(want_rgb), int(iters), C.byref(ms)),
-                  "rtx_time_relight", self.h)
-        return ms.value
+        return self._timed("rtx_time_relight", iters, C.byref(params), int(want_rgb))
 
     def time_frames(self, cam, params, iters: int) -> float:
-        ms = C.c_float()
-        abi.check(self.lib.rtx_time_frames(self.h, C.byref(cam), C.byref(params), int(iters), C.byref(ms)),
-                  "rtx_time_frames", self.h)
-        return ms.value
+        return self._timed("rtx_time_frames", iters, C.byref(cam), C.byref(params))
 
     def split_info(self) -> tuple[int, int]:
         """(heavy tiles the next frame splits, BVH frontier parts of the scene)."""
         h, p = C.c_uint32(), C.c_uint32()
-        abi.check(self.lib.rtx_split_info(self.h, C.byref(h), C.byref(p)), "rtx_split_info", self.h)
+        self._call("rtx_split_info", C.byref(h), C.byref(p))
         return h.value, p.value
 
     def split_tune_info(self) -> dict:
         """The split threshold's tuner: factor, last timed main kernel / split chain (ms), state."""
         f, m, ch, d = C.c_float(), C.c_float(), C.c_float(), C.c_uint32()
-        abi.check(self.lib.rtx_split_tune_info(self.h, C.byref(f), C.byref(m), C.byref(ch), C.byref(d)),
-                  "rtx_split_tune_info", self.h)
+        self._call("rtx_split_tune_info", C.byref(f), C.byref(m), C.byref(ch), C.byref(d))
         return {"factor": round(f.value, 4), "main_ms": round(m.value, 5), "chain_ms": round(ch.value, 5),
                 "state": ["tuning", "converged", "off"][d.value]}
 
@@ -458,46 +410,44 @@ class DeviceContext:
         for it; the heaviest tile's serialized time over the split frame's serialized span, the
         threshold, and the split frames' interval in flight on this context's stream (ms)."""
         a, b, r, t, w = C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float(), C.c_float()
-        abi.check(self.lib.rtx_inflight_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(t), C.byref(w)),
-                  "rtx_inflight_info", self.h)
+        self._call("rtx_inflight_info", C.byref(a), C.byref(b), C.byref(r), C.byref(t), C.byref(w))
         return {"concurrent": bool(a.value), "onepiece": bool(b.value), "crit": round(r.value, 3),
                 "threshold": round(t.value, 3), "split_interval_ms": round(w.value, 5)}
 
     def light_major_info(self) -> tuple[bool, int]:
         """(the last prepared frame was light-major, the largest light-major launch in wave tiles)."""
         a, b = C.c_uint32(), C.c_uint32()
-        abi.check(self.lib.rtx_light_major_info(self.h, C.byref(a), C.byref(b)), "rtx_light_major_info", self.h)
+        self._call("rtx_light_major_info", C.byref(a), C.byref(b))
         return bool(a.value), int(b.value)
 
     def cull_info(self) -> tuple[bool, int]:
         """(the uploaded scene renders with the exact cull, camera-record rebuilds so far)."""
         on, n = C.c_uint32(), C.c_uint64()
-        abi.check(self.lib.rtx_cull_info(self.h, C.byref(on), C.byref(n)), "rtx_cull_info", self.h)
+        self._call("rtx_cull_info", C.byref(on), C.byref(n))
         return bool(on.value), n.value
 
     def spec_info(self) -> tuple[int, int]:
         """(kSpec* facts of the last frame launched, the kSpecVariants index it took: -1 = generic)."""
         f, v = C.c_uint32(), C.c_int32()
-        abi.check(self.lib.rtx_spec_info(self.h, C.byref(f), C.byref(v)), "rtx_spec_info", self.h)
+        self._call("rtx_spec_info", C.byref(f), C.byref(v))
         return f.value, v.value
 
     def room_info(self) -> tuple[bool, float]:
         """(the uploaded scene's room-skip fact, room_M: the bound on a shadow origin's plane distances)."""
         f, m = C.c_uint32(), C.c_float()
-        abi.check(self.lib.rtx_room_info(self.h, C.byref(f), C.byref(m)), "rtx_room_info", self.h)
+        self._call("rtx_room_info", C.byref(f), C.byref(m))
         return bool(f.value), float(m.value)
 
     def count_work(self, cam, params) -> np.ndarray:
         out = (C.c_uint64 * 12)()
-        abi.check(self.lib.rtx_count_work(self.h, C.byref(cam), C.byref(params), out), "rtx_count_work", self.h)
+        self._call("rtx_count_work", C.byref(cam), C.byref(params), out)
         return np.array(list(out), dtype=np.uint64)
 
     def count_work_culled(self, cam, params) -> np.ndarray:
         """The 15 counters of the walk the product executes (rtx_count_work_culled): the 12 model
         counters, per-wave node-pair and triangle steps, exact-cull box tests."""
         out = (C.c_uint64 * 15)()
-        abi.check(self.lib.rtx_count_work_culled(self.h, C.byref(cam), C.byref(params), out, 15),
-                  "rtx_count_work_culled", self.h)
+        self._call("rtx_count_work_culled", C.byref(cam), C.byref(params), out, 15)
         return np.array(list(out), dtype=np.uint64)
 
 
@@ -705,6 +655,11 @@ class Renderer:
         EditLights does for lights (rtx_edit_materials)."""
         self._edit(scene, int(first), materials, "materials")
 
+    def _fill(self, name: str, want_rgb: bool, *args) -> np.ndarray:
+        """The blocking frame of entry point `name` into self.buffer (and self.rgb): self.buffer."""
+        _, self.rgb = self.ctx._frame(name, self.m_Width * self.m_Height, want_rgb, *args, px=self.buffer)
+        return self.buffer
+
     def RenderAOV(self, scene: HostScene, mask: int = AOV_ALL, upload: bool = True) -> dict:
         """The hit pass of the frame Render would render (same size, stripes and upload bookkeeping):
         the planes of `mask` as flat numpy arrays; rows this renderer's stripes do not own stay 0."""
@@ -716,18 +671,8 @@ class Renderer:
         render, shaded from the last RenderAOV's planes (all four) with the renderer's CURRENT lighting
         mode, shadows and pixel format, without tracing a primary ray.  Explicit: nothing is cached or
         reused automatically, and the scene is whatever was uploaded last.  Blocking; fills self.buffer."""
-        n = self.m_Width * self.m_Height
-        if self.ctx._aov_shape != (self.m_Width, self.m_Height, 1):
-            if self.ctx._aov_shape is None:
-                self.ctx.shade_aov_async(self.params(), want_rgb)   # no pass yet: the library says why
-            raise RuntimeError(f"ShadeAOV: the context's last hit pass is {self.ctx._aov_shape}, not this renderer's")
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.ctx.lib.rtx_shade_aov(self.ctx.h, C.byref(self.params()),
-                                        self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                        rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_shade_aov", self.ctx.h)
-        self.rgb = rgb
-        return self.buffer
+        self._own_pass("ShadeAOV", lambda: self.ctx.shade_aov_async(self.params(), want_rgb))
+        return self._fill("rtx_shade_aov", want_rgb, C.byref(self.params()))
 
     def _own_pass(self, what: str, probe) -> None:
         if self.ctx._aov_shape != (self.m_Width, self.m_Height, 1):
@@ -765,14 +710,7 @@ class Renderer:
         shadows and pixel format; light colours, intensities and material values are the scene's uploaded
         last.  Explicit, like ShadeAOV.  Blocking; fills self.buffer."""
         self._own_pass("Relight", lambda: self.ctx.relight_async(self.params(), want_rgb))
-        n = self.m_Width * self.m_Height
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.ctx.lib.rtx_relight(self.ctx.h, C.byref(self.params()),
-                                      self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                      rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_relight", self.ctx.h)
-        self.rgb = rgb
-        return self.buffer
+        return self._fill("rtx_relight", want_rgb, C.byref(self.params()))
 
     def RenderSamplePasses(self, scene: HostScene, k: int, upload: bool = True) -> None:
         """The passes an anti-aliased relighting loop starts from (not in the reference's Renderer): the hit pass
@@ -801,14 +739,7 @@ class Renderer:
                 self.ctx.relight_resolve_async(self.params(), k or 2, want_rgb)   # no pass yet: the library says why
             raise RuntimeError(f"RelightResolved: the context's last hit pass is {self.ctx._aov_shape}, not this "
                                "renderer's sample pass (RenderSamplePasses)")
-        n = self.m_Width * self.m_Height
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.ctx.lib.rtx_relight_resolve(self.ctx.h, C.byref(self.params()), k,
-                                              self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                              rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_relight_resolve", self.ctx.h)
-        self.rgb = rgb
-        return self.buffer
+        return self._fill("rtx_relight_resolve", want_rgb, C.byref(self.params()), k)
 
     def TraceRays(self, scene: HostScene, rays, mask: int = AOV_ALL, upload: bool = True) -> dict:
         """Scene::GetClosestHit on the caller's (n, 8) rays against `scene` (same upload bookkeeping as
@@ -833,14 +764,7 @@ class Renderer:
         if self.adaptive is not None:
             return self.RenderAdaptive(scene, *self.adaptive, upload=upload, want_rgb=want_rgb)
         s, cam = self._view(scene, upload)
-        n = self.m_Width * self.m_Height
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.ctx.lib.rtx_render(self.ctx.h, C.byref(cam), C.byref(self.params()),
-                                     self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                     rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_render", self.ctx.h)
-        self.rgb = rgb
-        return self.buffer
+        return self._fill("rtx_render", want_rgb, C.byref(cam), C.byref(self.params()))
 
     def RenderAdaptive(self, scene: HostScene, k: int, threshold: int, upload: bool = True,
                        want_rgb: bool = False) -> np.ndarray:
@@ -848,14 +772,7 @@ class Renderer:
         k x k samples for the pixels whose 8-bit colour differs from a 4-neighbour's by more than
         `threshold` in a channel, the plain pixel elsewhere.  Blocking; fills self.buffer."""
         _, cam = self._view(scene, upload)
-        n = self.m_Width * self.m_Height
-        rgb = np.zeros(3 * n, np.float32) if want_rgb else None
-        rc = self.ctx.lib.rtx_render_adaptive(self.ctx.h, C.byref(cam), C.byref(self.params()), int(k), int(threshold),
-                                              self.buffer.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                              rgb.ctypes.data_as(C.POINTER(C.c_float)) if want_rgb else None)
-        abi.check(rc, "rtx_render_adaptive", self.ctx.h)
-        self.rgb = rgb
-        return self.buffer
+        return self._fill("rtx_render_adaptive", want_rgb, C.byref(cam), C.byref(self.params()), int(k), int(threshold))
 
     def CycleLightingMode(self) -> None:   # Renderer.cpp:189-193
         self.m_CurrentLightingMode = (self.m_CurrentLightingMode + 1) % LightingMode.Count
