@@ -2,14 +2,12 @@
 checker of tests/test_aov_cpu.py and tests/test_gpu_aov.py).
 
 tests/aov_ref.c includes oracle/rtx_oracle.c unchanged and, per pixel, calls the oracle's own
-closest_hit plus an id-tracking copy of the same walk that it checks against it bit for bit.  `build`
-compiles it (gcc -O2 -ffp-contract=off, like the oracle) into a directory of the caller's, `planes`
-returns the four planes of a whole frame, and `same` is the contract's comparison: word for word,
-except that a NaN float equals any NaN."""
+closest_hit plus an id-tracking copy of the same walk that it checks against it bit for bit.
+checkers.lib() compiles and binds it, `planes` returns the four planes of a whole frame, and `same` is
+the contract's comparison: word for word, except that a NaN float equals any NaN."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -44,19 +42,6 @@ def golden_view(family: str, seed: int, tmp_dir):
     else:
         hs = scene_fuzz.host_scene(scene_fuzz.make(family, seed), Path(tmp_dir) / f"{name}.rtxscene")
     return (hs, *hs.view())
-
-
-def build(outdir) -> C.CDLL:
-    so = Path(outdir) / "libaov_ref.so"
-    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
-                    f"-I{ROOT / 'include'}", str(ROOT / "tests" / "aov_ref.c"), "-o", str(so), "-lm", "-lpthread"],
-                   check=True)
-    lib = C.CDLL(str(so))
-    P = C.POINTER
-    lib.aov_ref_planes.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float),
-                                   P(C.c_uint32), P(C.c_uint32)]
-    lib.aov_ref_planes.restype = C.c_int
-    return lib
 
 
 def planes(lib: C.CDLL, scene: abi.Scene, cam: abi.Camera, width: int, height: int) -> dict:

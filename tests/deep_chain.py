@@ -124,6 +124,16 @@ def left_deep_scene(T: int, layout: str):
     return s, cam, keep
 
 
+_views = {}
+
+
+def view(T: int, layout: str):
+    """(scene, camera) of left_deep_scene(T, layout), built once and kept alive; read-only."""
+    if (T, layout) not in _views:
+        _views[(T, layout)] = left_deep_scene(T, layout)
+    return _views[(T, layout)][:2]
+
+
 def write_mesh(path, pos, idx, nrm, nodes) -> None:
     """The mesh as tests/deep_chain_pack.cpp reads it: int32 T, then positions, indices, normals and the
     nodes (rtx_bvh_node, 36 bytes each), raw."""

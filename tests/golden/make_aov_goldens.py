@@ -20,6 +20,7 @@ ROOT = HERE.parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 import aov_ref  # noqa: E402
+import checkers  # noqa: E402
 
 W, H = aov_ref.GOLDEN_W, aov_ref.GOLDEN_H
 OUT = HERE / "aov"
@@ -28,7 +29,7 @@ OUT = HERE / "aov"
 def main() -> None:
     OUT.mkdir(exist_ok=True)
     with tempfile.TemporaryDirectory() as td:
-        lib = aov_ref.build(td)
+        lib = checkers.lib()
         for family, seed in aov_ref.golden_cases():
             name = f"{family}_{seed}"
             _keep, s, cam = aov_ref.golden_view(family, seed, td)

@@ -3,13 +3,11 @@ checker of tests/test_rayq_cpu.py and tests/test_gpu_rayq.py).
 
 tests/rayq_ref.c includes tests/aov_ref.c, and through it oracle/rtx_oracle.c, both unchanged: per ray
 the oracle's own closest_hit (plus aov_ref.c's id-tracking copy, checked against it bit for bit) and
-does_hit.  `build` compiles it as aov_ref.build compiles its own; rays are (n, 8) float32 rows
-{origin, direction, tmin, tmax}; results compare with aov_ref.same (word for word, a NaN float equals
-any NaN)."""
+does_hit.  checkers.lib() compiles and binds it; rays are (n, 8) float32 rows {origin, direction, tmin,
+tmax}; results compare with aov_ref.same (word for word, a NaN float equals any NaN)."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -20,28 +18,6 @@ from gp1_raytracer_2223_amd import abi
 ROOT = Path(__file__).resolve().parents[1]
 NAMES = aov_ref.NAMES
 GOLDEN = ROOT / "tests" / "golden" / "rayq"
-
-
-def build(outdir) -> C.CDLL:
-    so = Path(outdir) / "librayq_ref.so"
-    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
-                    f"-I{ROOT / 'include'}", str(ROOT / "tests" / "rayq_ref.c"), "-o", str(so), "-lm", "-lpthread"],
-                   check=True)
-    lib = C.CDLL(str(so))
-    P = C.POINTER
-    fp, up = P(C.c_float), P(C.c_uint32)
-    lib.rayq_ref_trace.argtypes = [P(abi.Scene), fp, C.c_uint32, fp, fp, up, up]
-    lib.rayq_ref_trace.restype = C.c_int
-    lib.rayq_ref_occluded.argtypes = [P(abi.Scene), fp, C.c_uint32, P(C.c_uint8)]
-    lib.rayq_ref_occluded.restype = None
-    lib.rayq_ref_primary.argtypes = [P(abi.Camera), C.c_uint32, C.c_uint32, fp]
-    lib.rayq_ref_primary.restype = None
-    lib.rayq_ref_shadow.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, C.c_uint32, fp, up]
-    lib.rayq_ref_shadow.restype = C.c_uint32
-    # aov_ref.c's own export, for the comparison with the hit pass's checker
-    lib.aov_ref_planes.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, fp, fp, up, up]
-    lib.aov_ref_planes.restype = C.c_int
-    return lib
 
 
 def _rays(rays) -> np.ndarray:
@@ -132,9 +108,10 @@ if __name__ == "__main__":
     import sys
     import tempfile
     sys.path.insert(0, str(ROOT / "tests"))
+    import checkers
     GOLDEN.mkdir(parents=True, exist_ok=True)
     with tempfile.TemporaryDirectory() as td:
-        lib_ = build(td)
+        lib_ = checkers.lib()
         for case_ in GOLDEN_CASES:
             keep_, s_, _ = golden_view(case_, td)
             np.savez_compressed(GOLDEN / f"{case_}.npz", **golden_of(lib_, s_))

@@ -8,38 +8,11 @@ shades from record + ray + that word."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
 import rayq_ref
 from gp1_raytracer_2223_amd import abi
-
-ROOT = Path(__file__).resolve().parents[1]
-
-
-def build(outdir) -> C.CDLL:
-    so = Path(outdir) / "librelight_ref.so"
-    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
-                    f"-I{ROOT / 'include'}", str(ROOT / "tests" / "relight_ref.c"), "-o", str(so), "-lm", "-lpthread"],
-                   check=True)
-    lib = C.CDLL(str(so))
-    P = C.POINTER
-    fp, up = P(C.c_float), P(C.c_uint32)
-    lib.relight_ref_shade.argtypes = [P(abi.Scene), fp, C.c_uint32, fp, fp, up, up, up, P(abi.RenderParams), up, fp]
-    lib.relight_ref_shade.restype = None
-    lib.shade_ref_rays.argtypes = [P(abi.Scene), fp, C.c_uint32, P(abi.RenderParams), up, fp, P(C.c_uint8)]
-    lib.shade_ref_rays.restype = None
-    lib.rayq_ref_trace.argtypes = [P(abi.Scene), fp, C.c_uint32, fp, fp, up, up]
-    lib.rayq_ref_trace.restype = C.c_int
-    lib.rayq_ref_occluded.argtypes = [P(abi.Scene), fp, C.c_uint32, P(C.c_uint8)]
-    lib.rayq_ref_occluded.restype = None
-    lib.rayq_ref_primary.argtypes = [P(abi.Camera), C.c_uint32, C.c_uint32, fp]
-    lib.rayq_ref_primary.restype = None
-    lib.rayq_ref_shadow.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, C.c_uint32, fp, up]
-    lib.rayq_ref_shadow.restype = C.c_uint32
-    return lib
 
 
 def plane(lib: C.CDLL, scene: abi.Scene, cam: abi.Camera, width: int, height: int):

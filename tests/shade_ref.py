@@ -3,13 +3,11 @@ tests/test_shade_cpu.py and tests/test_gpu_shade.py).
 
 tests/shade_ref.c includes tests/rayq_ref.c, and through it tests/aov_ref.c and oracle/rtx_oracle.c, all
 unchanged: per ray the oracle's render_pixel from closest_hit on, with the caller's ray in the place of
-the camera's.  `build` compiles it as rayq_ref.build compiles its own (and binds rayq_ref's exports too:
-the library is a superset); rays are (n, 8) float32 rows {origin, direction, tmin, tmax}; results compare
-with aov_ref.same (word for word, a NaN float equals any NaN)."""
+the camera's.  checkers.lib() compiles and binds it; rays are (n, 8) float32 rows {origin, direction, tmin,
+tmax}; results compare with aov_ref.same (word for word, a NaN float equals any NaN)."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -23,27 +21,6 @@ GOLDEN = ROOT / "tests" / "golden" / "shade"
 HIT, OCCLUDED, DIVIDED = 1, 2, 4   # the flags of shade_ref.c
 MODES = {"ObservedArea": abi.RTX_MODE_OBSERVED_AREA, "Radiance": abi.RTX_MODE_RADIANCE, "BRDF": abi.RTX_MODE_BRDF,
          "Combined": abi.RTX_MODE_COMBINED}
-
-
-def build(outdir) -> C.CDLL:
-    so = Path(outdir) / "libshade_ref.so"
-    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
-                    f"-I{ROOT / 'include'}", str(ROOT / "tests" / "shade_ref.c"), "-o", str(so), "-lm", "-lpthread"],
-                   check=True)
-    lib = C.CDLL(str(so))
-    P = C.POINTER
-    fp, up = P(C.c_float), P(C.c_uint32)
-    lib.shade_ref_rays.argtypes = [P(abi.Scene), fp, C.c_uint32, P(abi.RenderParams), up, fp, P(C.c_uint8)]
-    lib.shade_ref_rays.restype = None
-    lib.rayq_ref_trace.argtypes = [P(abi.Scene), fp, C.c_uint32, fp, fp, up, up]
-    lib.rayq_ref_trace.restype = C.c_int
-    lib.rayq_ref_occluded.argtypes = [P(abi.Scene), fp, C.c_uint32, P(C.c_uint8)]
-    lib.rayq_ref_occluded.restype = None
-    lib.rayq_ref_primary.argtypes = [P(abi.Camera), C.c_uint32, C.c_uint32, fp]
-    lib.rayq_ref_primary.restype = None
-    lib.rayq_ref_shadow.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, C.c_uint32, fp, up]
-    lib.rayq_ref_shadow.restype = C.c_uint32
-    return lib
 
 
 def params(mode: int = abi.RTX_MODE_COMBINED, shadows: bool = True, fmt=abi.XRGB8888) -> abi.RenderParams:
@@ -90,9 +67,10 @@ if __name__ == "__main__":
     import sys
     import tempfile
     sys.path.insert(0, str(ROOT / "tests"))
+    import checkers
     GOLDEN.mkdir(parents=True, exist_ok=True)
     with tempfile.TemporaryDirectory() as td:
-        lib_ = build(td)
+        lib_ = checkers.lib()
         for file_, case_, mode_ in GOLDEN_CASES:
             keep_, s_, _ = rayq_ref.golden_view(case_, td)
             np.savez_compressed(GOLDEN / f"{file_}.npz", **golden_of(lib_, s_, mode_))

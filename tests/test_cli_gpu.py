@@ -7,6 +7,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import oracle_bind
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene
@@ -49,10 +50,6 @@ def test_benchmark_mode_writes_reference_format(tmp_path):
     assert m and int(m.group(1)) >= 2
 
 
-def _channels(px: np.ndarray) -> np.ndarray:
-    return np.stack([(px >> s) & 0xFF for s in (16, 8, 0)], -1).astype(np.int32)
-
-
 @pytest.mark.parametrize("scene,inflight,exact,device", [("W4_Bunny", 2, True, False), ("W4_Optional", 2, False, False),
                                                          ("W4_Optional", 3, False, False),
                                                          ("W4_Optional", 4, False, False),
@@ -82,7 +79,7 @@ def test_pipelined_frame_loop_matches_oracle(tmp_path, scene, inflight, exact, d
         if exact:
             assert np.array_equal(got, ref), f"frame {k}: {int((got != ref).sum())} pixels differ"
         else:   # powf (Phong) is the device libm's: the north star's 1-LSB bound
-            assert int(np.abs(_channels(got) - _channels(ref)).max()) <= 1, f"frame {k}"
+            assert int(np.abs(gs.channels(got) - gs.channels(ref)).max()) <= 1, f"frame {k}"
 
 
 def test_viewer_keys_headless(tmp_path):

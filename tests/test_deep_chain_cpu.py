@@ -16,6 +16,7 @@ import aov_ref
 import deep_chain as dc
 import oracle_bind
 import rayq_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -23,19 +24,6 @@ CSRC = ROOT / "gp1_raytracer_2223_amd" / "csrc"
 LIB = ROOT / "gp1_raytracer_2223_amd" / "lib"
 SIZES = (64, 65, 300, 1024, 1025)   # depth 63 of 64 entries; 64: the deep stack; 1023 of 1024; 1024: the HBM stacks
 CASES = [(T, layout) for T in SIZES for layout in dc.LAYOUTS]
-
-_scenes = {}
-
-
-def _scene(T, layout):
-    if (T, layout) not in _scenes:
-        _scenes[(T, layout)] = dc.left_deep_scene(T, layout)
-    return _scenes[(T, layout)][:2]
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return rayq_ref.build(tmp_path_factory.mktemp("rayq_ref"))
 
 
 # ---------------------------------------------------------------- the model is the oracle's arithmetic
@@ -47,7 +35,7 @@ def test_the_models_slab_test_is_the_oracles():
     lib = oracle_bind.lib()
     pairs = 0
     for layout in dc.LAYOUTS:
-        s, cam = _scene(65, layout)
+        s, cam = dc.view(65, layout)
         lo, hi, *_ = dc.node_arrays(s.meshes[0])
         p = abi.make_params(dc.W, dc.H)
         rays = np.concatenate([dc.camera_tile_rays(cam, p, 110)[::9], dc.camera_tile_rays(cam, p, 45)[::13],
@@ -71,7 +59,7 @@ def test_the_models_slab_test_is_the_oracles():
 
 @pytest.mark.parametrize("w,h,fov", [(dc.W, dc.H, dc.FOV), (37, 23, None)])
 def test_the_models_primary_rays_are_the_oracles(checker, w, h, fov):
-    _, cam = _scene(65, "centred")
+    _, cam = dc.view(65, "centred")
     c = abi.Camera.from_buffer_copy(cam)
     if fov is None:
         c.fov = float(np.tan(np.radians(45.0) / 2))
@@ -100,7 +88,7 @@ def test_the_existing_chain_never_holds_more_than_one_entry(T):
 
 @pytest.mark.parametrize("T,layout", CASES)
 def test_the_left_deep_chain_fills_the_stack(T, layout):
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     hw = dc.frame_high_water(s, cam)
     full = np.nonzero(hw == T - 1)[0]
     print(f"T={T} {layout}: {full.size} of {hw.size} tiles reach {T - 1}: {full.tolist()}")
@@ -113,12 +101,12 @@ def test_an_any_hit_axis_wave_pops_the_whole_stack(T):
     """Corner layout: the axis crosses every box and misses every triangle, so each axis wave pushes T - 1
     entries and pops every one of them.  Centred layout: triangle 0 occludes the axis and the wave leaves
     from its first leaf, T - 1 entries still pending."""
-    s, cam = _scene(T, "corner")
+    s, cam = dc.view(T, "corner")
     waves = dc.axis_waves(s, cam)
     assert waves.shape[0] == 130
     for first in (0, 64, 128):
         assert dc.high_water_any(s, waves[first:first + 64]) == (T - 1, max(0, T - 1 - 64), T - 1), first
-    s, cam = _scene(T, "centred")
+    s, cam = dc.view(T, "centred")
     assert dc.high_water_any(s, dc.axis_waves(s, cam)[:64]) == (T - 1, 0, 0)
 
 
@@ -126,7 +114,7 @@ def test_an_any_hit_axis_wave_pops_the_whole_stack(T):
 
 @pytest.mark.parametrize("T,layout", CASES)
 def test_every_rim_ray_hits_its_triangle(checker, T, layout):
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     rays, tri = dc.rim_rays(s, cam)
     assert rays.shape[0] == T + -(-T // 63) and rays.shape[0] % 64 != 0
     assert (tri[0::64] == -1).all() and np.array_equal(tri[tri >= 0], np.arange(T))

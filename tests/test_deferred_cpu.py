@@ -5,26 +5,22 @@ material, primitive) as the contract words it, equals tests/shade_ref.c on the s
 stored record plus the ray is enough); and every PHASE 8 instantiation of the render kernel is built without
 scratch."""
 import ctypes as C
-import os
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_surface
 import aov_ref
 import rayq_ref
 import scene_fuzz
 import shade_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene
 
-ROOT = Path(__file__).resolve().parents[1]
-INC = ROOT / "include"
-EXE = ROOT / "gp1_raytracer_2223_amd" / "lib" / "rtx_render"
 W, H = 37, 23
-SYMBOLS = ["rtx_shade_aov_async", "rtx_shade_aov"]
 PIN = [("W1", -1.0), ("W2", -1.0), ("W3", -1.0), ("W4_Reference", -1.0), ("W4_Bunny", -1.0), ("W4_Bunny", 1.3),
        ("W4_Optional", -1.0)]
 
@@ -32,24 +28,12 @@ PIN = [("W1", -1.0), ("W2", -1.0), ("W3", -1.0), ("W4_Reference", -1.0), ("W4_Bu
 def test_header_declares_and_abi_binds_the_symbols(tmp_path):
     """The two entry points and the diag one are declared as the contract states them, exported and bound,
     and the ABI version stays 2."""
-    src = ['#include "rtx.h"', '#include "rtx_diag.h"', "int main(void) {",
-           "int (*f0)(rtx_ctx*, const rtx_render_params*, int) = rtx_shade_aov_async;",
-           "int (*f1)(rtx_ctx*, const rtx_render_params*, uint32_t*, float*) = rtx_shade_aov;",
-           "int (*f2)(rtx_ctx*, const rtx_render_params*, int, int, float*) = rtx_time_shade_aov;",
-           "return !(f0 && f1 && f2 && RTX_ABI_VERSION == 2); }"]
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-I{INC}", str(tmp_path / "l.c"), "-o", str(tmp_path / "l"),
-                    f"-L{abi.LIB_DIR}", "-lrtx_hip", f"-Wl,-rpath,{abi.LIB_DIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    subprocess.run([str(tmp_path / "l")], check=True)
-    prod, diag = (INC / "rtx.h").read_text(), (INC / "rtx_diag.h").read_text()
+    abi_surface.declared_exported_and_bound(tmp_path, {
+        "rtx_shade_aov_async": "int (*)(rtx_ctx*, const rtx_render_params*, int)",
+        "rtx_shade_aov": "int (*)(rtx_ctx*, const rtx_render_params*, uint32_t*, float*)",
+    }, {"rtx_time_shade_aov": "int (*)(rtx_ctx*, const rtx_render_params*, int, int, float*)"}, ["RTX_ABI_VERSION == 2"])
     lib = abi.load_hip()
     assert lib.rtx_abi_version() == 2
-    for n in SYMBOLS:
-        assert re.search(rf"^int {n}\(", prod, re.M), n
-    assert re.search(r"^int rtx_time_shade_aov\(", diag, re.M) and "rtx_time_shade_aov" not in prod
-    for n in SYMBOLS + ["rtx_time_shade_aov"]:
-        assert n in abi.HIP_SYMBOLS and getattr(lib, n).argtypes, n
-        assert getattr(lib, n).restype is C.c_int, n
     a = lib.rtx_shade_aov_async.argtypes
     assert a[1]._type_ is abi.RenderParams and a[2:] == [C.c_int]
     a = lib.rtx_shade_aov.argtypes
@@ -66,52 +50,17 @@ def test_null_context_is_invalid_without_a_device():
 
 
 def test_the_cpp_mirror_compiles(tmp_path):
-    (tmp_path / "m.cpp").write_text(
-        '#include "rtx_renderer.hpp"\n'
-        "void (rtx::Renderer::*f0)() = &rtx::Renderer::ShadeAov;\n"
-        "int main() { return !f0; }\n")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", f"-I{INC}", str(tmp_path / "m.cpp")],
-                   check=True)
+    abi_surface.cpp_mirror_compiles(tmp_path, [("void (rtx::Renderer::*)()", "ShadeAov")])
 
 
 @pytest.mark.parametrize("extra", [["--ss", "2"], ["--adaptive", "2,32"], ["--rays", "rays.f32"], ["--benchmark"],
                                    ["--benchmark", "2"], ["--sequence", "0.5,1.0"]],
                          ids=["ss", "adaptive", "rays", "benchmark", "benchmark_n", "sequence"])
 def test_cli_refuses_deferred_in_a_bad_combination_before_device_work(tmp_path, extra):
-    assert EXE.exists(), "lib/rtx_render is not built"
-    for args in (["--deferred"] + extra, extra + ["--deferred", "--aov", "planes"]):
-        r = subprocess.run([str(EXE), "W4_Bunny", "64", "48", "--out", "o.bmp"] + args, capture_output=True, text=True,
-                           cwd=tmp_path, timeout=60)
-        assert r.returncode != 0, args
-        assert "--deferred" in r.stderr, (args, r.stderr)
-        assert list(tmp_path.iterdir()) == [], args
+    abi_surface.cli_refuses(tmp_path, "--deferred", ["--deferred"] + extra, extra + ["--deferred", "--aov", "planes"])
 
 
 # ---- the checker: the record plus the ray is enough ----------------------------------------------
-
-def build_checker(outdir) -> C.CDLL:
-    so = Path(outdir) / "libdeferred_ref.so"
-    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
-                    f"-I{ROOT / 'include'}", str(ROOT / "tests" / "deferred_ref.c"), "-o", str(so), "-lm", "-lpthread"],
-                   check=True)
-    lib = C.CDLL(str(so))
-    P = C.POINTER
-    fp, up = P(C.c_float), P(C.c_uint32)
-    lib.deferred_ref_shade.argtypes = [P(abi.Scene), fp, C.c_uint32, fp, fp, up, up, P(abi.RenderParams), up, fp]
-    lib.deferred_ref_shade.restype = None
-    lib.shade_ref_rays.argtypes = [P(abi.Scene), fp, C.c_uint32, P(abi.RenderParams), up, fp, P(C.c_uint8)]
-    lib.shade_ref_rays.restype = None
-    lib.rayq_ref_trace.argtypes = [P(abi.Scene), fp, C.c_uint32, fp, fp, up, up]
-    lib.rayq_ref_trace.restype = C.c_int
-    lib.rayq_ref_primary.argtypes = [P(abi.Camera), C.c_uint32, C.c_uint32, fp]
-    lib.rayq_ref_primary.restype = None
-    return lib
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return build_checker(tmp_path_factory.mktemp("deferred_ref"))
-
 
 def deferred_shade(lib, scene, rays, rec, p):
     n = rays.shape[0]
@@ -158,14 +107,11 @@ def test_the_same_on_the_committed_fuzz_views(checker, tmp_path, family, seed):
 
 # ---- the PHASE 8 instantiations, from the code object's metadata only ------------------------------
 
-def test_every_phase8_instantiation_is_built_without_scratch(tmp_path):
-    from test_isa import LLVM, _code_object
-    if not os.path.exists(f"{LLVM}/clang-offload-bundler"):
-        pytest.skip("ROCm LLVM tools not present")
+def test_every_phase8_instantiation_is_built_without_scratch():
+    import isa_tools
     lib = Path(abi.LIB_DIR) / "librtx_hip.so"
     assert lib.exists(), "librtx_hip.so is not built"
-    co = _code_object(tmp_path, str(lib))
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True, text=True).stdout
+    _, notes = isa_tools.listing(str(lib))
     found = {}
     for block in notes.split("  - .")[1:]:
         m = re.search(r"\.name:\s+_Z17rtx_render_kernelILb0ELi8ELb([01])ELi(\d+)ELb([01])ELb([01])ELb0EE\w+", block)

@@ -14,15 +14,16 @@ import numpy as np
 import pytest
 
 import adaptive_ref
+import gpu_support as gs
 import oracle_bind
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, DeviceContext, Renderer, aov_host_planes
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 from test_gpu_parity import POW_FREE
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 XRGB = adaptive_ref.XRGB8888
 W0, H0 = 37, 23   # k = 2: 74 x 46 samples, neither a multiple of the 8 x 8 wave tile
 
@@ -43,18 +44,8 @@ def ref_ctx():
     ctx.close()
 
 
-_scenes = {}
 _device = {}
 _oracle = {}
-
-
-def _scene(name, t=-1.0):
-    if (name, t) not in _scenes:
-        hs = HostScene(name)
-        if t >= 0:
-            hs.update(t)
-        _scenes[(name, t)] = (hs, *hs.view())
-    return _scenes[(name, t)][1:]
 
 
 def _frozen(*arrays):
@@ -109,7 +100,7 @@ def _same(got, want, what):
 
 def _parity(ad_ctx, ref_ctx, name, t, W, H, k, tau, mode=3, shadows=1, fmt=XRGB, exact=None, s_cam=None, partial=True):
     """One adaptive frame against the device's own composition (and the oracle's where `exact`)."""
-    s, cam = s_cam if s_cam is not None else _scene(name, t)
+    s, cam = s_cam if s_cam is not None else gs.view(name, t)
     P, S = _device_ps(ref_ctx, (name, t), s, cam, W, H, k, mode, shadows, fmt)
     wpx, wrgb, E = _compose(P, S, W, H, tau, fmt)
     n = int(E.sum())
@@ -147,7 +138,7 @@ def test_parity(ad_ctx, ref_ctx, name, t, k, tau):
 @pytest.mark.parametrize("k", [2, 4, 8])
 def test_threshold_0_is_the_supersampled_frame(ad_ctx, ref_ctx, k):
     """Every pixel of this frame differs from a neighbour: the list is W * H long and A = S."""
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     P, S = _device_ps(ref_ctx, ("W4_Bunny", -1.0), s, cam, W0, H0, k)
     assert adaptive_ref.edges(P[0], W0, H0, 0).all()
     ad_ctx.upload(s)
@@ -159,7 +150,7 @@ def test_threshold_0_is_the_supersampled_frame(ad_ctx, ref_ctx, k):
 
 
 def test_threshold_255_is_the_plain_frame(ad_ctx, ref_ctx):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     P, _ = _device_ps(ref_ctx, ("W4_Bunny", -1.0), s, cam, W0, H0, 2)
     ad_ctx.upload(s)
     ad_ctx.render_adaptive(cam, abi.make_params(W0, H0), 2, 0)     # (a full list first: nothing of it may be used)
@@ -176,7 +167,7 @@ def test_modes_and_shadows(ad_ctx, ref_ctx, mode, shadows):
 
 def test_without_the_colour_plane(ref_ctx):
     """want_rgb = 0 on a context that never had a colour plane: the refinement stores pixels only."""
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     P, S = _device_ps(ref_ctx, ("W4_Bunny", -1.0), s, cam, W0, H0, 4)
     wpx, _, E = _compose(P, S, W0, H0, 32)
     ctx = DeviceContext(DEV)
@@ -230,7 +221,7 @@ def test_split_frames_and_context_state(ref_ctx):
     finally:
         del os.environ["RTX_SPLIT"]
     try:
-        s, cam = _scene("W4_Bunny")
+        s, cam = gs.view("W4_Bunny")
         p = abi.make_params(W, H)
         P, S = _device_ps(ref_ctx, ("W4_Bunny", -1.0), s, cam, W, H, k)
         want = _compose(P, S, W, H, tau)
@@ -259,7 +250,7 @@ def test_split_frames_and_context_state(ref_ctx):
         # a plain frame afterwards is a fresh context's
         _same(ctx.render(cam, p), P, "a plain frame after adaptive frames")
         # after uploading another scene the adaptive frame is that scene's
-        s2, cam2 = _scene("W2")
+        s2, cam2 = gs.view("W2")
         P2, S2 = _device_ps(ref_ctx, ("W2", -1.0), s2, cam2, W, H, k)
         want2 = _compose(P2, S2, W, H, tau)
         ctx.upload(s2)
@@ -270,7 +261,7 @@ def test_split_frames_and_context_state(ref_ctx):
 
 
 def test_errors_leave_the_context_rendering(ref_ctx):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     P, S = _device_ps(ref_ctx, ("W4_Bunny", -1.0), s, cam, W0, H0, 2)
     want = _compose(P, S, W0, H0, 32)
     ctx = DeviceContext(DEV)
@@ -330,7 +321,7 @@ def test_errors_leave_the_context_rendering(ref_ctx):
 
 def test_renderer_and_cli_take_the_mode(ref_ctx, tmp_path):
     """`Renderer(..., adaptive=(k, tau))`, `Renderer.RenderAdaptive` and `rtx_render --adaptive 2,32`."""
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     P, S = _device_ps(ref_ctx, ("W4_Bunny", -1.0), s, cam, W0, H0, 2)
     wpx, wrgb, E = _compose(P, S, W0, H0, 32)
     r = Renderer(W0, H0, device=DEV, adaptive=(2, 32))

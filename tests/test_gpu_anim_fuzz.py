@@ -15,7 +15,6 @@ reference on these very cases.  Every comparison is bit-exact:
     leaf loop on leaves of thousands, without the device builder in the way).
 An error status (timeout, capacity) on any of these meshes is a failure, never retried."""
 import functools
-import os
 from pathlib import Path
 
 import numpy as np
@@ -23,14 +22,15 @@ import pytest
 
 import aov_ref
 import mesh_fuzz
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import DeviceAnimation, DeviceContext
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 from test_gpu_anim import _compare_state, _image
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 G = Path(__file__).resolve().parent / "golden" / "meshfuzz"
 W, H = 44, 28
 FRAMES = [(3, 1), (0, 1)]
@@ -66,11 +66,6 @@ def assets(tmp_path_factory):
 def _host(assets, case):
     d, scene = assets(case)
     return HostScene(f"file:{scene}", asset_dir=str(d))
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return aov_ref.build(tmp_path_factory.mktemp("aov_ref"))
 
 
 @pytest.fixture(scope="module")

@@ -14,16 +14,19 @@ import numpy as np
 import pytest
 
 import aov_ref
+import gpu_support as gs
 import oracle_bind
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import (AOV_ALL, AOV_DEPTH, AOV_MATERIAL, AOV_NORMAL, AOV_PRIMITIVE,
                                              DeviceAnimation, DeviceContext, DeviceGroup, Renderer,
                                              aov_host_planes)
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
+from gpu_support import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 ROOT = Path(__file__).resolve().parents[1]
 G = ROOT / "tests" / "golden" / "aov"
 W, H = 37, 23
@@ -31,36 +34,14 @@ SENTINEL = {"depth": np.float32(-7.5), "normal": np.float32(-7.5), "material": n
             "primitive": np.uint32(0xDEADBEEF)}
 
 
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return aov_ref.build(tmp_path_factory.mktemp("aov_ref"))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = DeviceContext(DEV)
-    yield c
-    c.close()
-
-
-_scenes = {}
 _want = {}
-
-
-def _scene(name, t=-1.0):
-    if (name, t) not in _scenes:
-        hs = HostScene(name)
-        if t >= 0:
-            hs.update(t)
-        _scenes[(name, t)] = (hs, *hs.view())
-    return _scenes[(name, t)][1:]
 
 
 def _ref(checker, name, t=-1.0, w=W, h=H):
     """The checker's planes (computed once per case, never written to)."""
     key = (name, t, w, h)
     if key not in _want:
-        s, cam = _scene(name, t)
+        s, cam = gs.view(name, t)
         p = aov_ref.planes(checker, s, cam, w, h)
         for a in p.values():
             a.setflags(write=False)
@@ -73,20 +54,13 @@ def _equal(got, want, what, names=aov_ref.NAMES):
     assert not bad, f"{what}: planes {bad} differ"
 
 
-def _colour_ok(c, s, cam, w=W, h=H):
-    """A colour frame of the pow-free Bunny scene equals the oracle's."""
-    gpx, grgb = c.render(cam, abi.make_params(w, h))
-    rpx, rrgb = oracle_bind.render(s, cam, abi.make_params(w, h))
-    assert np.array_equal(gpx, rpx) and np.array_equal(grgb.view(np.uint32), rrgb.view(np.uint32))
-
-
 PARITY = [("W1", -1.0), ("W2", -1.0), ("W3", -1.0), ("W4_Reference", -1.0), ("W4_Bunny", -1.0), ("W4_Bunny", 1.3),
           ("W4_Optional", -1.0)]
 
 
 @pytest.mark.parametrize("name,t", PARITY)
 def test_parity(ctx, checker, name, t):
-    s, cam = _scene(name, t)
+    s, cam = gs.view(name, t)
     ctx.upload(s)
     got = ctx.render_aov(cam, abi.make_params(W, H))
     assert sorted(got) == sorted(aov_ref.NAMES)
@@ -109,7 +83,7 @@ def test_fuzz_scenes_and_goldens(ctx, checker, tmp_path, family, seed):
 
 
 def test_mask_subsets_and_lazy_planes(checker):
-    s, cam = _scene("W4_Reference")
+    s, cam = gs.view("W4_Reference")
     want = _ref(checker, "W4_Reference")
     p = abi.make_params(W, H)
     c = DeviceContext(DEV)
@@ -134,7 +108,7 @@ def test_mask_subsets_and_lazy_planes(checker):
 
 def test_culled_walk(checker):
     """Synthetic100k renders with the exact cull: the pass takes the CULLK instantiation."""
-    s, cam = _scene("Synthetic100k")
+    s, cam = gs.view("Synthetic100k")
     c = DeviceContext(DEV)
     try:
         c.upload(s)
@@ -162,7 +136,7 @@ def test_deep_stack_variants(ctx, checker, T):
 
 def test_stripes_gather_into_one_frame(checker):
     w, h, n = 37, 53, 3
-    s, cam = _scene("W4_Reference")
+    s, cam = gs.view("W4_Reference")
     want = _ref(checker, "W4_Reference", -1.0, w, h)
     frame = {k: np.full_like(want[k], SENTINEL[k]) for k in aov_ref.NAMES}
     ctxs = [DeviceContext(DEV) for _ in range(n)]
@@ -189,7 +163,7 @@ def test_stripes_gather_into_one_frame(checker):
 
 def test_views_equal_single_view_passes(ctx):
     n = 3
-    s, cam = _scene("W4_Reference")
+    s, cam = gs.view("W4_Reference")
     views = []
     for f in range(n):
         v = abi.Camera()
@@ -211,7 +185,7 @@ def test_views_equal_single_view_passes(ctx):
 
 def test_group_equals_single_context(ctx):
     w, h = 37, 53
-    s, cam = _scene("W4_Reference")
+    s, cam = gs.view("W4_Reference")
     ctx.upload(s)
     want = ctx.render_aov(cam, abi.make_params(w, h))
     grp = DeviceGroup([DEV, DEV])
@@ -225,7 +199,7 @@ def test_group_equals_single_context(ctx):
 
 
 def test_colour_frames_are_untouched(checker):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     p = abi.make_params(W, H)
     c = DeviceContext(DEV)
     try:
@@ -264,7 +238,7 @@ def test_split_frames_interleaved_with_passes(checker):
     after each equal the same frames without the passes, frame by frame, and the passes (which
     render every tile themselves) equal the checker."""
     w, h = 64, 48
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     p = abi.make_params(w, h)
     want = _ref(checker, "W4_Bunny", -1.0, w, h)
     a, b = _split_ctx(), _split_ctx()
@@ -292,7 +266,7 @@ def test_device_update(checker):
     anim = DeviceAnimation(dev_scene, c)
     try:
         anim.update(1.3, c)
-        got = c.render_aov(_scene("W4_Reference", 1.3)[1], abi.make_params(W, H))
+        got = c.render_aov(gs.view("W4_Reference", 1.3)[1], abi.make_params(W, H))
         assert list(anim.status(0)[:1]) == [0]
         _equal(got, _ref(checker, "W4_Reference", 1.3), "after a device Update")
         assert (aov_ref.kind(got["primitive"]) == 3).any()
@@ -325,14 +299,14 @@ def test_renderer_and_cli(checker, tmp_path):
 
 
 def test_errors_leave_the_context_usable(checker):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     want = _ref(checker, "W4_Bunny")
     p = abi.make_params(W, H)
     c = DeviceContext(DEV)
     lib, h = c.lib, c.h
 
     def still_renders(after):
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         _equal(c.render_aov(cam, p), want, f"after {after}")
 
     try:

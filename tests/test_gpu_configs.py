@@ -13,13 +13,13 @@ bit-exact, i.e. both SHA-256 equal.  W3 uses Cook-Torrance (powf in Fresnel): th
 libm's powf may differ by an ulp, so it is checked on the 4096 samples within tolerance and
 its SHA is reported, not required; so are W4_Reference and W4_Optional (Cook-Torrance
 spheres / mesh), whose 1080p frames the reference also produced (tests/golden/make_goldens.py)."""
-import hashlib
 import os
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene
 
@@ -34,24 +34,16 @@ CONFIGS = [("W1", 640, 480, True), ("W3", 1280, 720, False), ("W4_Bunny", 1920, 
 FRAMES = 4
 
 
-def _channels(px):
-    return np.stack([(px >> 16) & 255, (px >> 8) & 255, px & 255], -1).astype(np.int32)
-
-
-def _sha(a: np.ndarray) -> str:
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
 def check_frame(g, px, rgb, exact, what):
     rgb = rgb.reshape(-1, 3)
     idx = g["idx"]
     d = np.abs(rgb[idx] - g["rgb"])
     assert not np.isnan(rgb).any(), what
     assert float(d.max(initial=0.0)) <= TOL, f"{what}: max-abs {d.max()}"
-    assert np.abs(_channels(px[idx]) - _channels(g["pixels"])).max(initial=0) <= 1, what
+    assert np.abs(gs.channels(px[idx]) - gs.channels(g["pixels"])).max(initial=0) <= 1, what
     if exact:
-        assert _sha(px) == str(g["sha_pixels"][0]), f"{what}: uint32 frame differs from the reference"
-        assert _sha(rgb) == str(g["sha_rgb"][0]), f"{what}: float frame differs from the reference"
+        assert gs.sha(px) == str(g["sha_pixels"][0]), f"{what}: uint32 frame differs from the reference"
+        assert gs.sha(rgb) == str(g["sha_rgb"][0]), f"{what}: float frame differs from the reference"
 
 
 @pytest.fixture
@@ -76,7 +68,7 @@ def test_config_full_resolution(fresh_ctx, name, W, H, exact):
         check_frame(g, px, rgb, exact, f"{name} {W}x{H} frame {f + 1}")
         heavy.append(fresh_ctx.split_info()[0])
     print(f"{name} {W}x{H}: heavy tiles per frame after measuring {heavy}, "
-          f"sha match {_sha(px) == str(g['sha_pixels'][0])}")
+          f"sha match {gs.sha(px) == str(g['sha_pixels'][0])}")
 
 
 def test_synthetic100k_split_path_is_exercised(fresh_ctx):

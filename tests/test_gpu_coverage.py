@@ -22,17 +22,19 @@ import numpy as np
 import pytest
 
 import aov_ref
+import checkers
 import devbuf
+import gpu_support as gs
 import oracle_bind
 import ss_ref
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, AOV_DEPTH, AOV_NORMAL, AOV_PRIMITIVE, DeviceContext
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 from test_gpu_aov import SENTINEL as AOV_SENTINEL
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 K_MAX_HEAVY_TILES = 8192   # kMaxHeavyTiles (csrc/rtx_kernels.h)
 K_MAX_LIGHTS = 32          # kMaxSplitLights, kMaxCullLights, kMaxLmLights
 KNOBS = ("RTX_XCD_ORDER", "RTX_SPLIT", "RTX_SPLIT_PARTS", "RTX_DEFER_JOIN", "RTX_LIGHT_MAJOR", "RTX_CULL_MIN_SA",
@@ -72,15 +74,7 @@ cull_ctx = _fixture(RTX_CULL_MIN_SA="0", RTX_CULL_RATIO="0", RTX_CULL_ANIMATED="
 
 # ---- scenes, cameras and expected frames: built once per module, never written to ----------------
 
-_scenes = {}
 _oracle = {}
-
-
-def _scene(name):
-    if name not in _scenes:
-        hs = HostScene(name)
-        _scenes[name] = (hs, *hs.view())
-    return _scenes[name][1:]
 
 
 def _moved(cam, dx):
@@ -101,7 +95,7 @@ def _want(name, W, H, mode=3, sh=1, dx=0.0, k=1):
     """The oracle's whole frame of scene `name` with the camera moved by dx along x, supersampled k x k."""
     key = (name, W, H, mode, sh, float(np.float32(dx)), k)
     if key not in _oracle:
-        s, cam = _scene(name)
+        s, cam = gs.view(name)
         px, rgb = oracle_bind.render(s, _moved(cam, dx), abi.make_params(k * W, k * H, mode, sh))
         if k > 1:
             rgb = ss_ref.resolve(rgb, W, H, k)
@@ -174,7 +168,7 @@ ORDER_SHAPES = [(328, 264), (328, 200), (44, 28), (8, 8), (40, 32)]
 @pytest.mark.parametrize("which", ["plain", "xcd"])
 def test_cost_order_one_view(plain_ctx, xcd_ctx, which, W, H):
     ctx = {"plain": plain_ctx, "xcd": xcd_ctx}[which]
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     want = [_want("W4_Bunny", W, H)]
     p = abi.make_params(W, H)
     ctx.upload(s)
@@ -194,7 +188,7 @@ STRIPE_CASES = [(3, 16, 2), (3, 32, 3), (3, 48, 9), (8, 16, 3), (8, 32, 9), (8, 
 def test_cost_order_views_and_stripes(plain_ctx, xcd_ctx, which, views, rows, step):
     ctx = {"plain": plain_ctx, "xcd": xcd_ctx}[which]
     W, H = 72, 200
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     cams = _views(cam, views)
     want = [_want("W4_Bunny", W, H, dx=0.05 * v) for v in range(views)]
     ctx.upload(s)
@@ -221,7 +215,7 @@ def test_split_force(split_ctx, split_nodefer_ctx, which, W, H, name, mode, sh):
     """Frame 2 is the first one the split launches render; frames 3.. repeat it, and a repeated frame's
     main kernel starts beside the previous frame's chain (the deferred join; RTX_DEFER_JOIN=0: never)."""
     ctx = {"defer": split_ctx, "nodefer": split_nodefer_ctx}[which]
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     want = [_want(name, W, H, mode, sh)]
     p = abi.make_params(W, H, mode, sh)
     ctx.upload(s)
@@ -240,7 +234,7 @@ def test_split_more_heavy_tiles_than_the_cap(split_ctx):
     render those and the main kernel the 128 tiles past the cap."""
     W, H = 1024, 520
     assert _tiles(W, H) == K_MAX_HEAVY_TILES + 128
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     want = [_want("W4_Bunny", W, H)]
     p = abi.make_params(W, H)
     split_ctx.upload(s)
@@ -255,7 +249,7 @@ def test_split_with_a_moving_camera(split_ctx):
     """The motion schedule: every frame is measured and split, and PHASE 3 must hand every hit-key and
     occlusion slot back reset (hit_key = ~0, occ_bits = 0) for the next frame's other rays."""
     W, H = 256, 144
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     p = abi.make_params(W, H)
     split_ctx.upload(s)
     _queue(split_ctx, cam, p, 2)              # measured frame, first split frame
@@ -270,7 +264,7 @@ def test_split_with_a_moving_camera(split_ctx):
 
 @pytest.mark.parametrize("W,H", [(192, 128), (44, 28)], ids=lambda v: str(v))
 def test_light_major(lm_ctx, W, H):
-    s, cam = _scene("Bunny8Lights")
+    s, cam = gs.view("Bunny8Lights")
     want = [_want("Bunny8Lights", W, H)]
     lm_ctx.upload(s)
     # the warm-up at this shape is a BRDF-mode frame: it allocates the buffers, and the Combined frames
@@ -290,7 +284,7 @@ def test_light_major(lm_ctx, W, H):
 @pytest.mark.parametrize("which", ["plain", "split"])
 def test_supersampled(plain_ctx, split_ctx, which, W, H, k):
     ctx = {"plain": plain_ctx, "split": split_ctx}[which]
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     want = [_want("W4_Bunny", W, H, k=k)]
     p = abi.make_params(W, H)
     ctx.upload(s)
@@ -312,7 +306,7 @@ def test_supersampled(plain_ctx, split_ctx, which, W, H, k):
 
 def test_two_contexts_in_flight(plain_ctx):
     W, H = 320, 180
-    s, cam = _scene("Synthetic100k")
+    s, cam = gs.view("Synthetic100k")
     want = [_want("Synthetic100k", W, H)]
     p = abi.make_params(W, H)
     other = _ctx()
@@ -339,10 +333,10 @@ def _word(x):
 
 
 @pytest.fixture(scope="module")
-def aov_want(tmp_path_factory):
+def aov_want():
     """The checker's planes of the pass below (tests/aov_ref.py), computed once."""
-    s, cam = _scene("W4_Bunny")
-    want = aov_ref.planes(aov_ref.build(tmp_path_factory.mktemp("aov_ref")), s, cam, 37, 53)
+    s, cam = gs.view("W4_Bunny")
+    want = aov_ref.planes(checkers.lib(), s, cam, 37, 53)
     for a in want.values():
         a.setflags(write=False)
     return want
@@ -354,7 +348,7 @@ def test_hit_pass_writes_its_planes_rows_only(plain_ctx, aov_want, mask):
     everything else — unnamed planes, rows it does not own, the colour frame buffer — keeps its sentinel."""
     W, H, step = 37, 53, 3
     ctx = plain_ctx
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     want = aov_want
     elems ={"depth": 1, "normal": 3, "material": 1, "primitive": 1}
     for k in aov_ref.NAMES:   # the sentinels cannot be output

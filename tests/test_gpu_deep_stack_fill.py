@@ -12,7 +12,6 @@ import os
 import re
 from pathlib import Path
 
-import ctypes as C
 import numpy as np
 import pytest
 
@@ -24,12 +23,14 @@ import oracle_bind
 import rayq_ref
 import shade_ref
 import ss_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, DeviceContext
+from gpu_support import DEV
+from gpu_support import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 ROOT = Path(__file__).resolve().parents[1]
 W, H = dc.W, dc.H
 SIZES = (64, 65, 1024, 1025)
@@ -38,25 +39,6 @@ FRAME_CASES = [(T, layout) for T in (64, 65, 300, 1024, 1025) for layout in dc.L
 TWO = [(T, layout) for T in (65, 1025) for layout in dc.LAYOUTS]
 MODES = ((3, 1), (0, 1))
 TAU = 8   # the oracle's plain frames have 1,400 to 4,300 pixels above it, most of them on the chain
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    """tests/shade_ref.c holds rayq_ref.c and aov_ref.c: one library checks the shaded rays, the queries
-    and the hit pass."""
-    lib = shade_ref.build(tmp_path_factory.mktemp("shade_ref"))
-    P = C.POINTER
-    lib.aov_ref_planes.argtypes = [P(abi.Scene), P(abi.Camera), C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float),
-                                   P(C.c_uint32), P(C.c_uint32)]
-    lib.aov_ref_planes.restype = C.c_int
-    return lib
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = DeviceContext(DEV)
-    yield c
-    c.close()
 
 
 def _ctx_env(**env):
@@ -72,20 +54,14 @@ def _ctx_env(**env):
                 os.environ[k] = v
 
 
-_scenes, _frames, _tiles, _planes = {}, {}, {}, {}
-
-
-def _scene(T, layout):
-    if (T, layout) not in _scenes:
-        _scenes[(T, layout)] = dc.left_deep_scene(T, layout)
-    return _scenes[(T, layout)][:2]
+_frames, _tiles, _planes = {}, {}, {}
 
 
 def _oracle(T, layout, w=W, h=H, mode=3, shadows=1):
     """The oracle's frame (computed once per case, never written to)."""
     key = (T, layout, w, h, mode, shadows)
     if key not in _frames:
-        s, cam = _scene(T, layout)
+        s, cam = dc.view(T, layout)
         px, rgb = oracle_bind.render(s, cam, abi.make_params(w, h, mode, shadows))
         px.setflags(write=False)
         rgb.setflags(write=False)
@@ -96,7 +72,7 @@ def _oracle(T, layout, w=W, h=H, mode=3, shadows=1):
 def _full_tiles(T, layout):
     """The wave tiles of the 160 x 96 frame that hold T - 1 pending entries, by the model."""
     if (T, layout) not in _tiles:
-        s, cam = _scene(T, layout)
+        s, cam = dc.view(T, layout)
         full = np.nonzero(dc.frame_high_water(s, cam) == T - 1)[0]
         assert full.size == 36 and (np.diff(full) == 1).sum() >= 2, full
         _tiles[(T, layout)] = full
@@ -104,14 +80,14 @@ def _full_tiles(T, layout):
 
 
 def _tile_rays(T, layout):
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     p = abi.make_params(W, H)
     return np.concatenate([dc.camera_tile_rays(cam, p, int(t)) for t in _full_tiles(T, layout)])
 
 
 def _ref_planes(checker, T, layout):
     if (T, layout) not in _planes:
-        s, cam = _scene(T, layout)
+        s, cam = dc.view(T, layout)
         _planes[(T, layout)] = aov_ref.planes(checker, s, cam, W, H)
     return _planes[(T, layout)]
 
@@ -138,7 +114,7 @@ def test_frames_and_work_counters(ctx, T, layout):
     """Each frame three times (tile order, then the cost-ordered dispatch).  The counting variant walks
     with its second stack (sT, hstkT); a lost or repeated entry changes the slab and triangle counters
     even where its triangle is smaller than a pixel."""
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     _full_tiles(T, layout)   # (the model's 36 full tiles: asserted)
     ctx.upload(s)
     for mode, sh in MODES:
@@ -171,7 +147,7 @@ def test_the_64_entry_stack_at_its_limit(plain_ctx, which, layout):
     cull and the part walks of the split launches."""
     T = 64
     env = {**(CULL if "cull" in which else {}), **(SPLIT if "split" in which else {})}
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     c = _ctx_env(**env)
     try:
         c.upload(s)
@@ -198,7 +174,7 @@ _hi = {}
 
 def _oracle_hi(T, layout):
     if (T, layout) not in _hi:
-        s, cam = _scene(T, layout)
+        s, cam = dc.view(T, layout)
         _, hi = oracle_bind.render(s, cam, abi.make_params(2 * W, 2 * H))
         hi.setflags(write=False)
         _hi[(T, layout)] = hi
@@ -207,7 +183,7 @@ def _oracle_hi(T, layout):
 
 @pytest.mark.parametrize("T,layout", TWO)
 def test_supersampling(T, layout):
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     rgb = ss_ref.resolve(_oracle_hi(T, layout), W, H, 2)
     c = DeviceContext(DEV)
     try:
@@ -225,7 +201,7 @@ def test_supersampling(T, layout):
 
 @pytest.mark.parametrize("T,layout", CASES)
 def test_hit_pass_and_deferred_shade(ctx, checker, T, layout):
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     ctx.upload(s)
     frames = {}
     for mode, sh in MODES:
@@ -252,7 +228,7 @@ def test_hit_pass_and_deferred_shade(ctx, checker, T, layout):
 @pytest.mark.parametrize("T,layout", TWO)
 def test_adaptive(ctx, checker, T, layout):
     """Persistent waves: with the stacks in HBM one stack per resident wave, reused from item to item."""
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     P = _oracle(T, layout)
     S = adaptive_ref.supersampled(_oracle_hi(T, layout), W, H, 2)
     E = adaptive_ref.edges(P[0], W, H, TAU)
@@ -282,7 +258,7 @@ def _query(c, checker, s, rays, what, lengths=()):
 
 @pytest.mark.parametrize("T,layout", CASES)
 def test_ray_queries(ctx, checker, T, layout):
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     ctx.upload(s)
     rays, tri = dc.rim_rays(s, cam)
     planes, occ = _query(ctx, checker, s, rays, f"T={T} {layout} rim rays", lengths=(1, 63, 64, 65))
@@ -318,7 +294,7 @@ def test_a_large_query_sizes_the_hbm_stacks_per_launch(ctx, checker, layout):
     rim set repeated to more than four launches' worth.  Its length is no multiple of 64, so every repeat
     puts the rays into other lanes."""
     T = 1025
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     chunk = _launch_rays(T - 1)
     assert 64 <= chunk < 1 << 20 and chunk % 64 == 0, chunk
     n = 4 * chunk + 1000
@@ -340,7 +316,7 @@ def test_a_large_query_sizes_the_hbm_stacks_per_launch(ctx, checker, layout):
 @pytest.mark.parametrize("T,layout", CASES)
 def test_shaded_rays(ctx, checker, T, layout):
     """The shadow rays of these hits are any-hit walks on full stacks."""
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     ctx.upload(s)
     rim, _ = dc.rim_rays(s, cam)
     for what, rays in (("rim rays", rim), ("full tiles", _tile_rays(T, layout))):
@@ -366,7 +342,7 @@ def test_hbm_stacks_follow_the_launch(checker, layout):
     """One context: a small frame, a larger one, the small one again, a query and a deferred shade.  The
     stacks are regrown and rebound per launch; each result equals its reference."""
     T = 1025
-    s, cam = _scene(T, layout)
+    s, cam = dc.view(T, layout)
     c = DeviceContext(DEV)
     try:
         c.upload(s)

@@ -15,58 +15,24 @@ import pytest
 
 import aov_ref
 import devbuf
+import gpu_support as gs
 import oracle_bind
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, AOV_DEPTH, DeviceContext, Renderer, aov_host_planes
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import CONFIGS, DEV, FP, LIGHTS, MATS, POW_FREE_MODES, UP
+from gpu_support import ctx  # noqa: F401
 from test_gpu_deep_bvh import deep_scene
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 ROOT = Path(__file__).resolve().parents[1]
 EXE = ROOT / "gp1_raytracer_2223_amd" / "lib" / "rtx_render"
 W, H = 37, 23   # five tile columns and three tile rows, one of each partial
-CONFIGS = [(mode, sh) for mode in range(4) for sh in (0, 1)]
-POW_FREE_MODES = (abi.RTX_MODE_OBSERVED_AREA, abi.RTX_MODE_RADIANCE)
-UP, FP = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = DeviceContext(DEV)
-    yield c
-    c.close()
-
-
-_scenes = {}
-
-
-def _scene(name):
-    if name not in _scenes:
-        if name.startswith("fuzz:"):   # a committed fuzz scene (tests/golden/fuzz)
-            hs = HostScene(f"file:{ROOT / 'tests' / 'golden' / 'fuzz' / (name[5:] + '.rtxscene')}")
-        else:
-            hs = HostScene(name)
-        _scenes[name] = (hs, *hs.view())
-    return _scenes[name][1:]
 
 
 def _shade_rc(c, p, want_rgb=1):
     return c.lib.rtx_shade_aov_async(c.h, C.byref(p) if p is not None else None, want_rgb)
-
-
-def _frames(c, cam, w, h, configs, seen=None):
-    """The colour frames of `configs` (computed once, never written to), and the variants they took."""
-    out = {}
-    for mode, sh in configs:
-        px, rgb = c.render(cam, abi.make_params(w, h, mode, sh))
-        px.setflags(write=False)
-        rgb.setflags(write=False)
-        out[(mode, sh)] = (px, rgb)
-        if seen is not None:
-            seen.add(c.spec_info()[1])
-    return out
 
 
 def _shade_and_check(c, w, h, mode, sh, want, what, n_views=1, shape=None):
@@ -78,9 +44,9 @@ def _shade_and_check(c, w, h, mode, sh, want, what, n_views=1, shape=None):
 
 
 def _equals_the_frame(c, name, w, h, seen, oracle_all_modes=False):
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     c.upload(s)
-    frames = _frames(c, cam, w, h, CONFIGS, seen)
+    frames = gs.frames(c, cam, w, h, CONFIGS, seen)
     room = c.room_info()[0]
     c.render_aov_async(cam, abi.make_params(w, h), AOV_ALL)
     for (mode, sh), want in frames.items():
@@ -130,12 +96,12 @@ def test_the_scenes_covered_every_variant(ctx):
 
 @pytest.mark.parametrize("name", ["Synthetic100k", "W4_Optional"])
 def test_exact_cull(name):
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     w, h = 64, 40
     c = DeviceContext(DEV)
     try:
         c.upload(s)
-        frames = _frames(c, cam, w, h, [(3, 1)])
+        frames = gs.frames(c, cam, w, h, [(3, 1)])
         assert c.cull_info()[0], f"{name} renders without the exact cull"
         c.render_aov_async(cam, abi.make_params(w, h), AOV_ALL)
         _shade_and_check(c, w, h, 3, 1, frames[(3, 1)], name)
@@ -157,7 +123,7 @@ def test_deep_stacks(ctx, T):
     s, cam, keep = deep_scene(T)
     w, h = 64, 40
     ctx.upload(s)
-    frames = _frames(ctx, cam, w, h, [(0, 1)])
+    frames = gs.frames(ctx, cam, w, h, [(0, 1)])
     assert (frames[(0, 1)][0] != frames[(0, 1)][0][0]).any()
     ctx.render_aov_async(cam, abi.make_params(w, h), AOV_ALL)
     _shade_and_check(ctx, w, h, 0, 1, frames[(0, 1)], f"chain of {T}")
@@ -168,23 +134,12 @@ def test_deep_stacks(ctx, T):
 
 # ---- 4. views and stripes -----------------------------------------------------------------------------
 
-def _cams3(cam):
-    cams = []
-    for k, dx in enumerate((0.0, 1.5, -2.0)):
-        c2 = abi.Camera()
-        C.memmove(C.byref(c2), C.byref(cam), C.sizeof(abi.Camera))
-        c2.origin[0] = cam.origin[0] + dx
-        c2.origin[1] = cam.origin[1] + 0.25 * k
-        cams.append(c2)
-    return cams
-
-
 @pytest.mark.parametrize("first", [0, 1])
 def test_views_and_stripes(ctx, first):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     w, h, nv = 40, 32, 3
     n = w * h
-    cams = _cams3(cam)
+    cams = gs.cams3(cam)
     arr = (abi.Camera * nv)(*cams)
     p = abi.make_params(w, h, 3, 1, abi.XRGB8888, 16, first, 2)
     ctx.upload(s)
@@ -217,12 +172,6 @@ def test_views_and_stripes(ctx, first):
 
 # ---- 5. relight ---------------------------------------------------------------------------------------
 
-ROOM = ["plane 0 0 10   0 0 -1  1", "plane 0 0 0    0 1 0   1", "plane 0 10 0   0 -1 0  1",
-        "plane 5 0 0   -1 0 0   1", "plane -5 0 0   1 0 0   1"]
-BUNNY = "mesh lowpoly_bunny2 2 back scale 2 2 2"
-MATS = ["material lambert 0.49 0.57 0.57 1", "material lambert 1 1 1 1", "material lambert 0.8 0.3 0.3 1",
-        "material lambert 0.3 0.8 0.3 1"]   # + the default material 0: five
-LIGHTS = ["light point 0 5 5  50 1 0.61 0.45", "light point -2.5 5 -5  70 1 0.8 0.45"]
 # name -> (materials, lights, the variant and the room fact its frames take)
 RELIGHT = {
     "moved_recoloured": (MATS, ["light point 1.5 6 3  60 0.4 0.7 1", LIGHTS[1]], 0, True),
@@ -233,26 +182,20 @@ RELIGHT = {
 }
 
 
-def _file_scene(tmp_path, name, mats, lights):
-    path = tmp_path / f"{name}.rtxscene"
-    path.write_text("\n".join(["camera 0 3 -9 45", *mats, *ROOM, BUNNY, *lights]) + "\n")
-    return HostScene(f"file:{path}")
-
-
 def test_relight(tmp_path):
     c = DeviceContext(DEV)
     try:
-        base = _file_scene(tmp_path, "base", MATS, LIGHTS)
+        base = gs.file_scene(tmp_path, "base", MATS, LIGHTS)
         s, cam = base.view()
         assert s.n_materials == 5
         c.upload(s)
-        frames = _frames(c, cam, W, H, CONFIGS)
+        frames = gs.frames(c, cam, W, H, CONFIGS)
         assert c.spec_info()[1] == 0 and c.room_info()[0]
         c.render_aov_async(cam, abi.make_params(W, H), AOV_ALL)
         for (mode, sh), want in frames.items():   # one pass: every mode and shadow toggle
             _shade_and_check(c, W, H, mode, sh, want, f"base mode {mode} shadows {sh}")
         for name, (mats, lights, variant, room) in RELIGHT.items():
-            hs = _file_scene(tmp_path, name, mats, lights)
+            hs = gs.file_scene(tmp_path, name, mats, lights)
             s2, cam2 = hs.view()
             assert s2.n_materials == 5 and bytes(cam2) == bytes(cam)
             c.upload(s2)   # the same geometry and material indices: no new pass
@@ -269,7 +212,7 @@ def test_relight(tmp_path):
             if room is not None:
                 assert c.room_info()[0] == room, name
         # a scene with fewer materials than the pass's: refused on the host
-        four = _file_scene(tmp_path, "four_materials", MATS[:3], LIGHTS)
+        four = gs.file_scene(tmp_path, "four_materials", MATS[:3], LIGHTS)
         s4, _ = four.view()
         assert s4.n_materials == 4
         c.upload(s4)
@@ -284,12 +227,12 @@ def test_relight(tmp_path):
 # ---- 6. isolation and records ---------------------------------------------------------------------------
 
 def test_isolation_and_records():
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     n = W * H
     c = DeviceContext(DEV)
     try:
         c.upload(s)
-        frames = _frames(c, cam, W, H, [(3, 1), (0, 0)])
+        frames = gs.frames(c, cam, W, H, [(3, 1), (0, 0)])
         big = c.render(cam, abi.make_params(64, 48))   # the last colour frame: 64 x 48, variant 0
         spec, split = c.spec_info(), c.split_info()
         assert spec[1] == 0
@@ -311,7 +254,7 @@ def test_isolation_and_records():
         abi.check(c.lib.rtx_download(c.h, px.ctypes.data_as(UP), None), "rtx_download", c.h)
         assert aov_ref.same(px, frames[(3, 1)][0])
         # a shade queued between two frames of different cameras changes neither
-        cam_b = _cams3(cam)[1]
+        cam_b = gs.cams3(cam)[1]
         p = abi.make_params(W, H)
         want_a, want_b = c.render(cam, p), c.render(cam_b, p)
         assert not np.array_equal(want_a[0], want_b[0])
@@ -334,7 +277,7 @@ def test_the_dispatch_order_changes_no_pixel():
     """The shade reads the dispatch order of the context's last frames when they had its tile set: before any
     frame (tile order), after frames of another size, after frames of its size, and on a context without
     cost-ordered dispatch, the same words."""
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     w, h = 96, 64
     n = w * h
     p = abi.make_params(w, h)
@@ -369,15 +312,8 @@ def test_the_dispatch_order_changes_no_pixel():
 
 # ---- 7. the error table -----------------------------------------------------------------------------------
 
-def _renders_correctly(c, s, cam):
-    p = abi.make_params(W, H)
-    px, rgb = c.render(cam, p)
-    rpx, rrgb = oracle_bind.render(s, cam, p)
-    assert np.array_equal(px, rpx) and np.array_equal(rgb.view(np.uint32), rrgb.view(np.uint32))
-
-
 def test_error_table():
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     p = abi.make_params(W, H)
     px = np.zeros(W * H, np.uint32)
     c = DeviceContext(DEV)
@@ -386,21 +322,21 @@ def test_error_table():
         c.upload(s)
         assert _shade_rc(c, p) == abi.RTX_E_STATE                     # no pass yet
         assert b"pass" in c.lib.rtx_last_error(c.h)
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         assert _shade_rc(c, None) == abi.RTX_E_INVALID
         assert c.lib.rtx_shade_aov(c.h, C.byref(p), None, None) == abi.RTX_E_INVALID
         c.render_aov(cam, p, AOV_DEPTH)
         assert _shade_rc(c, p) == abi.RTX_E_STATE                     # not all four planes
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         c.render_aov(cam, p, AOV_ALL)
         for bad in (abi.make_params(W, H, 4), abi.make_params(W, H, -1), abi.make_params(W, H, 3, 1, (25, 8, 0, 0))):
             assert _shade_rc(c, bad) == abi.RTX_E_INVALID             # what rtx_render rejects
             assert c.lib.rtx_render_async(c.h, C.byref(cam), C.byref(bad), 0) == abi.RTX_E_INVALID
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         c.set_supersample(2)
         assert _shade_rc(c, p) == abi.RTX_E_UNSUPPORTED
         c.set_supersample(1)
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         want = c.render(cam, p)
         devbuf.poison(c, W * H)
         assert c.lib.rtx_shade_aov(c.h, C.byref(p), px.ctypes.data_as(UP), None) == abi.RTX_OK   # and it still shades

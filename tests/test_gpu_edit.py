@@ -9,7 +9,6 @@ all 8 mode / shadow configurations.  Frames are 64 x 48 unless a case says other
 The edits are tests/edit_cases.py's; tests/test_edit_cpu.py shows on the CPU that its moves flip the room-skip
 fact and that its material bit patterns hold denormals, huge values and both zeros."""
 import ctypes as C
-import os
 import subprocess
 from pathlib import Path
 
@@ -18,39 +17,24 @@ import pytest
 import torch   # at collection, before librtx_hip.so is loaded: imported after it, torch finds no device
 
 import edit_cases as EC
+import gpu_support as gs
 import oracle_bind
 import pack_cases
 import relight_ref
 import shadow_update_scenes as sus
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, DeviceAnimation, DeviceContext, Renderer
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import CONFIGS, DEV, POW_FREE_MODES
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 ROOT = Path(__file__).resolve().parents[1]
 LIB = ROOT / "gp1_raytracer_2223_amd" / "lib"
 EXE = LIB / "rtx_render"
 W, H = 64, 48
-CONFIGS = [(mode, sh) for mode in range(4) for sh in (0, 1)]
-POW_FREE_MODES = (abi.RTX_MODE_OBSERVED_AREA, abi.RTX_MODE_RADIANCE)
 KMAXVIEWS = 8   # rtx_cull_dump: light l's anchor is record copy KMAXVIEWS + l
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
-
-
-_scenes = {}
-
-
-def _scene(name):
-    if name not in _scenes:
-        hs = HostScene(name)
-        _scenes[name] = (hs, *hs.view())
-    return _scenes[name][1:]
 
 
 def _with(s, lights=None, materials=None):
@@ -126,7 +110,7 @@ def _value_edit(s, round_=0):
 def test_value_edits(name):
     """Light colours and intensities and every material value, on a context whose schedule and cull view records
     are warm (a frame rendered before the edit), then again from first > 0 to the last record."""
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     c = DeviceContext(DEV)
     try:
         c.upload(s)
@@ -148,7 +132,7 @@ def test_value_edits(name):
 def test_edit_as_the_first_call_after_upload(name):
     """The cull boxes and light records are pending then (Synthetic100k: exact cull on): the pending build must use
     the edited lights."""
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     c = DeviceContext(DEV)
     try:
         c.upload(s)
@@ -190,7 +174,7 @@ def test_moved_lights(checker, tmp_path, which):
     """A move inside the room, out of it and back: the room-skip fact flips both ways (the two room scenes), and
     after every move the context is the fresh one."""
     if which == "W4_Bunny":
-        s, cam = _scene(which)
+        s, cam = gs.view(which)
     else:
         hs = sus.file_scene(tmp_path, which, "base")
         s, cam = hs.view()
@@ -229,7 +213,7 @@ def _dump(ctx, anchor):
 def test_moved_light_rebuilds_its_own_cull_anchor(checker):
     """Synthetic100k, exact cull on: after a move only the moved light's anchor records are rebuilt (equal to the
     fresh context's, like every other anchor's); the camera anchors are not (cull_updates stays)."""
-    s, cam = _scene("Synthetic100k")
+    s, cam = gs.view("Synthetic100k")
     c, f = DeviceContext(DEV), DeviceContext(DEV)
     try:
         p = abi.make_params(W, H)
@@ -278,7 +262,7 @@ def test_device_material_values_equal_the_host_form():
     """16 rounds of 256 materials whose eight floats are random bit patterns (finite): the device form's Lambert
     term, product and division, gives the host form's image byte for byte.  A division by reciprocal or a contracted
     multiply-add would show here."""
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     mats = EC.many_materials(s)
     s256 = _with(s, materials=list(mats))
     values = EC.random_material_values()
@@ -303,7 +287,7 @@ def test_device_material_values_equal_the_host_form():
 def test_device_forms_from_first_above_zero_read_n_records():
     """first > 0 and n short of the last record, from a sentinel-guarded buffer: the records outside the range keep
     their values, so a read past n records would show; lights and materials; then the context is the fresh one."""
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     lights, mats = _value_edit(s)
     nl, nm = len(lights), len(mats)
     assert nl >= 3 and nm >= 3
@@ -333,7 +317,7 @@ def test_edits_are_ordered_with_the_frames():
     (W4_Optional at 256 x 144: the split chain of a frame reads the image on another stream): each frame gathered
     behind its render is the frame of its own scene."""
     w, h = 256, 144
-    s, cam = _scene("W4_Optional")
+    s, cam = gs.view("W4_Optional")
     lights, mats = _value_edit(s)
     lights[0] = EC.moved(lights[0], EC.MOVE_IN)
     sB = _with(s, lights, mats)
@@ -379,8 +363,8 @@ def test_edits_are_ordered_with_the_frames():
 def test_edits_beside_uploads():
     """An edit followed at once by the upload of a third scene, and an upload followed at once by an edit (the
     upload's copy out of the pinned image still pending): both are the fresh context."""
-    s, cam = _scene("W4_Optional")
-    s3, cam3 = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Optional")
+    s3, cam3 = gs.view("W4_Bunny")
     lights, mats = _value_edit(s)
     lights[1] = EC.moved(lights[1], EC.MOVE_OUT)
     c = DeviceContext(DEV)
@@ -401,7 +385,7 @@ def test_edits_beside_uploads():
 # ---- 5. a payload of several launches -----------------------------------------------------------------------------
 
 def test_all_256_materials():
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     mats = EC.many_materials(s)
     c = DeviceContext(DEV)
     try:
@@ -417,7 +401,7 @@ def test_all_256_materials():
 # ---- 6. errors ----------------------------------------------------------------------------------------------------
 
 def test_error_table():
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     lib = abi.load_hip()
     lights, mats = _value_edit(s)
     nl, nm = len(lights), len(mats)

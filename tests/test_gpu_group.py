@@ -4,25 +4,20 @@ path as G devices (one host thread + stream per context, each gathering its 16-r
 with hipMemcpy2DAsync into the caller's frame).  The stitched frame must equal one
 context's render bit for bit, and at full resolution the reference's own frame."""
 import ctypes as C
-import hashlib
-import os
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import DeviceContext, DeviceGroup
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 
 pytestmark = pytest.mark.gpu
 
 G = Path(__file__).resolve().parent / "golden"
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
-
-
-def _sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("name", ["W4_Bunny", "W3"])
@@ -77,7 +72,7 @@ def test_group_full_resolution_matches_reference(name, W, H):
         for f in range(3):   # frame 1 measures tile costs, the rest run cost-ordered / split
             frame[:] = 0
             grp.render(cam, abi.make_params(W, H), want_rgb=False, out_px=frame)
-            assert _sha(frame) == str(g["sha_pixels"][0]), f"{name} frame {f + 1}"
+            assert gs.sha(frame) == str(g["sha_pixels"][0]), f"{name} frame {f + 1}"
     finally:
         lib.rtx_host_unregister(c0, frame.ctypes.data_as(C.c_void_p))
         grp.close()

@@ -5,22 +5,22 @@ the reference's light loop over every light from the published occlusion, Render
 Occlusion is a yes/no per (pixel, light) and the shading runs the same operations in the same order, so
 the pixels must be the one-piece kernel's bit for bit, and the oracle's / the reference's."""
 import ctypes as C
-import hashlib
 import os
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import oracle_bind
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import DeviceContext
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 
 pytestmark = pytest.mark.gpu
 
 G = Path(__file__).resolve().parent / "golden"
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 POW_FREE = {"W1", "W2", "W4_Bunny", "Synthetic100k", "Bunny8Lights"}
 
 
@@ -50,14 +50,6 @@ def one_ctx():
     c.close()
 
 
-def _sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def _channels(px):
-    return np.stack([(px >> 16) & 255, (px >> 8) & 255, px & 255], -1).astype(np.int32)
-
-
 CASES = [("W4_Bunny", -1.0), ("W4_Bunny", 1.3), ("W3", -1.0), ("W3_Test", -1.0), ("W4_Reference", -1.0),
          ("W4_Optional", -1.0), ("W4_Optional", 1.3), ("Bunny8Lights", -1.0), ("Synthetic100k", -1.0), ("W2", -1.0)]
 
@@ -83,7 +75,7 @@ def test_light_major_equals_one_piece(lm_ctx, one_ctx, name, t, mode):
         assert np.array_equal(rgb.view(np.uint32), ref_rgb.view(np.uint32)), f"{name} m{mode} frame {f} rgb"
     rpx, rrgb = oracle_bind.render(s, cam, p)
     assert float(np.abs(rgb - rrgb).max()) <= 1e-4
-    assert np.abs(_channels(px) - _channels(rpx)).max() <= 1
+    assert np.abs(gs.channels(px) - gs.channels(rpx)).max() <= 1
     if name in POW_FREE or mode in (0, 1):
         assert np.array_equal(px, rpx), f"{name} m{mode}: {(px != rpx).sum()} pixels differ from the oracle"
 
@@ -101,7 +93,7 @@ def test_light_major_with_every_tile_split():
         px, rgb = c.render(cam, p)
         assert c.split_info()[0] == 24 * 16
         rpx, rrgb = oracle_bind.render(s, cam, p)
-        assert float(np.abs(rgb - rrgb).max()) <= 1e-4 and np.abs(_channels(px) - _channels(rpx)).max() <= 1
+        assert float(np.abs(rgb - rrgb).max()) <= 1e-4 and np.abs(gs.channels(px) - gs.channels(rpx)).max() <= 1
     finally:
         c.close()
 
@@ -130,7 +122,7 @@ def test_shares_light_major_match_reference(name, W, H, s_):
         finally:
             c.close()
     if g is not None:
-        assert _sha(frame) == str(g["sha_pixels"][0]), name
+        assert gs.sha(frame) == str(g["sha_pixels"][0]), name
     else:
         one = _ctx(RTX_LIGHT_MAJOR="0")
         try:

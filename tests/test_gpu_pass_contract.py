@@ -11,7 +11,6 @@ The expected codes and message texts are literals here, copied from the library'
 calling the library.  The scene is the room of tests/shadow_update_scenes.py."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
@@ -20,12 +19,11 @@ import shadow_update_scenes as sus
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, AOV_DEPTH, DeviceContext, aov_host_planes
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV, FP, UP
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 W, H = 32, 16
-UP, FP = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
 INVALID, STATE, UNSUPPORTED = abi.RTX_E_INVALID, abi.RTX_E_STATE, abi.RTX_E_UNSUPPORTED
 
 # ---- the literals (rtx_pass.hip, rtx_relight.hip) ----------------------------------------------------------------

@@ -5,52 +5,32 @@ and the lengths around a wave boundary, through every walk (octant copies, fast,
 LDS and in HBM), the device variants, beside frames and passes they must not disturb, after a device
 Update, through the Python Renderer, and on the error paths."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch   # at collection, before librtx_hip.so is loaded: imported after it, torch finds no device
 
 import aov_ref
+import gpu_support as gs
 import oracle_bind
 import rayq_rays
 import rayq_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import (AOV_ALL, AOV_DEPTH, AOV_MATERIAL, AOV_NORMAL, AOV_PRIMITIVE, AOV_PLANES,
                                              DeviceAnimation, DeviceContext, Renderer, aov_host_planes)
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
+from gpu_support import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 W, H = 37, 23
 SEED = 7
 NAMES = aov_ref.NAMES
 
 
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return rayq_ref.build(tmp_path_factory.mktemp("rayq_ref"))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = DeviceContext(DEV)
-    yield c
-    c.close()
-
-
-_scenes = {}
 _cases = {}
-
-
-def _scene(name, t=-1.0):
-    if (name, t) not in _scenes:
-        hs = HostScene(name)
-        if t >= 0:
-            hs.update(t)
-        _scenes[(name, t)] = (hs, *hs.view())
-    return _scenes[(name, t)][1:]
 
 
 def _frozen(rays, planes, occ):
@@ -64,7 +44,7 @@ def _sets(checker, name, t=-1.0):
     that applies to it, computed once and never written to."""
     key = (name, t)
     if key not in _cases:
-        s, cam = _scene(name, t)
+        s, cam = gs.view(name, t)
         sets = {"primary": rayq_ref.primary(checker, cam, W, H), "scatter": rayq_rays.scatter(SEED, 512),
                 "nonfinite": rayq_rays.nonfinite(s, SEED)}
         if s.n_lights:
@@ -95,7 +75,7 @@ PARITY = [("W1", -1.0), ("W2", -1.0), ("W3", -1.0), ("W4_Reference", -1.0), ("W4
 
 @pytest.mark.parametrize("name,t", PARITY)
 def test_parity(ctx, checker, name, t):
-    s, _ = _scene(name, t)
+    s, _ = gs.view(name, t)
     ctx.upload(s)
     for k, (rays, planes, occ) in _sets(checker, name, t).items():
         assert 65 < rays.shape[0] <= 2048, (k, rays.shape)
@@ -128,7 +108,7 @@ def test_committed_goldens(ctx, tmp_path, case):
 
 @pytest.mark.parametrize("name", ["W4_Bunny", "W3"])
 def test_primary_rays_equal_the_hit_pass(ctx, checker, name):
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     ctx.upload(s)
     want = ctx.render_aov(cam, abi.make_params(W, H))
     got = ctx.trace_rays(_sets(checker, name)["primary"][0])
@@ -168,19 +148,14 @@ def test_hbm_stacks_cut_a_large_query_into_launches(ctx, checker):
     del keep
 
 
-def _torch():
-    assert torch.cuda.is_available(), "torch sees no GPU (was librtx_hip.so loaded before torch was imported?)"
-    return torch, torch.device("cuda", DEV)
-
-
 SENT_F = np.float32(-7.5)
 
 
 def test_device_variants_and_mask_subsets(ctx, checker):
     """Rays and outputs as torch tensors.  The four planes and the occlusion bytes lie in one sentinel-
     filled buffer with guard words between them: a query writes the planes of its mask and nothing else."""
-    torch, dev = _torch()
-    s, _ = _scene("W4_Bunny")
+    torch, dev = gs.torch_device()
+    s, _ = gs.view("W4_Bunny")
     ctx.upload(s)
     rays, planes, occ = _sets(checker, "W4_Bunny")["aimed"]
     for n in (rays.shape[0], 65, 1):
@@ -214,22 +189,15 @@ def test_device_variants_and_mask_subsets(ctx, checker):
     assert sorted(got) == ["material", "normal"] and not aov_ref.diff(got, planes, ["normal", "material"])
 
 
-def _colour_ok(c, s, cam, w=W, h=H):
-    """A colour frame of the pow-free Bunny scene equals the oracle's."""
-    gpx, grgb = c.render(cam, abi.make_params(w, h))
-    rpx, rrgb = oracle_bind.render(s, cam, abi.make_params(w, h))
-    assert np.array_equal(gpx, rpx) and np.array_equal(grgb.view(np.uint32), rrgb.view(np.uint32))
-
-
 def test_frames_and_passes_are_untouched(checker):
-    torch, dev = _torch()
-    s, cam = _scene("W4_Bunny")
+    torch, dev = gs.torch_device()
+    s, cam = gs.view("W4_Bunny")
     rays, planes, occ = _sets(checker, "W4_Bunny")["aimed"]
     p = abi.make_params(W, H)
     c = DeviceContext(DEV)
     try:
         c.upload(s)
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         spec, sched = c.spec_info(), c.split_info()
         pass_planes = c.render_aov(cam, p)
         assert not aov_ref.diff(c.trace_rays(rays), planes)
@@ -242,7 +210,7 @@ def test_frames_and_passes_are_untouched(checker):
         c.gather_async(px)
         c.synchronize()
         assert np.array_equal(px, oracle_bind.render(s, cam, p)[0])
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         assert c.spec_info() == spec and c.split_info() == sched
         # a query between two frames in flight changes neither
         cam2 = abi.Camera()
@@ -267,7 +235,7 @@ def test_frames_and_passes_are_untouched(checker):
         c.set_supersample(2)
         assert not aov_ref.diff(c.trace_rays(rays), planes) and np.array_equal(c.occluded(rays), occ)
         c.set_supersample(1)
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
     finally:
         c.close()
 
@@ -325,7 +293,7 @@ def test_renderer(checker):
 
 
 def test_errors_leave_the_context_usable(checker):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     rays, planes, occ = _sets(checker, "W4_Bunny")["aimed"]
     n = rays.shape[0]
     c = DeviceContext(DEV)
@@ -390,6 +358,6 @@ def test_errors_leave_the_context_usable(checker):
         # a good call through the raw entry point fills only what it was given
         assert lib.rtx_trace_rays(h, rp, n, AOV_DEPTH, C.byref(out)) == abi.RTX_OK
         assert aov_ref.same(depth, planes["depth"]) and (normal == 0).all()
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
     finally:
         c.close()

@@ -11,10 +11,9 @@ import pytest
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import DeviceContext
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 
 pytestmark = pytest.mark.gpu
-
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 
 
 def _ctx(**env):

@@ -9,14 +9,15 @@ import os
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import oracle_bind
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import DeviceContext
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import BUNNY, DEV, ROOM
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 W, H = 128, 72
 TOL = 1e-4                                   # test_gpu_parity.py's tolerance where powf runs
 POW_FREE = {"W4_Bunny", "Bunny8Lights"}      # Lambert only: bit-exact
@@ -46,10 +47,6 @@ def off_ctx():
     ctx.close()
 
 
-def _channels(px):
-    return np.stack([(px >> 16) & 255, (px >> 8) & 255, px & 255], -1).astype(np.int32)
-
-
 def _same(name, a, b):
     assert np.array_equal(a[0], b[0]), f"{name}: {int((a[0] != b[0]).sum())} pixels differ between skip on and off"
     assert np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), f"{name}: colour words differ between skip on and off"
@@ -60,7 +57,7 @@ def _vs_oracle(name, gpu, ref, exact):
     assert not np.isnan(grgb).any()
     d = np.abs(grgb - rrgb)
     assert float(d.max(initial=0.0)) <= TOL, f"{name}: max-abs {d.max()}"
-    assert np.abs(_channels(gpx) - _channels(rpx)).max(initial=0) <= 1, name
+    assert np.abs(gs.channels(gpx) - gs.channels(rpx)).max(initial=0) <= 1, name
     if exact:
         assert np.array_equal(gpx, rpx), f"{name}: {int((gpx != rpx).sum())} pixels differ from the oracle"
         assert np.array_equal(grgb.view(np.uint32), rrgb.view(np.uint32)), \
@@ -90,11 +87,8 @@ def test_catalogue_skip_on_equals_off_and_oracle(on_ctx, off_ctx, name, t):
 
 # ---- scenes where the fact or the lane condition fails (Lambert only: bit-exact) ---------------
 
-ROOM = ["plane 0 0 10   0 0 -1  1", "plane 0 0 0    0 1 0   1", "plane 0 10 0   0 -1 0  1",
-        "plane 5 0 0   -1 0 0   1", "plane -5 0 0   1 0 0   1"]
 OUTWARD = ["plane 0 0 10   0 0 1  1", "plane 0 0 0    0 -1 0   1", "plane 0 10 0   0 1 0  1",
            "plane 5 0 0   1 0 0   1", "plane -5 0 0   -1 0 0   1"]
-BUNNY = "mesh lowpoly_bunny2 2 back scale 2 2 2"
 INSIDE = ["light point 0 5 5  50 1 0.61 0.45", "light point -2.5 5 -5  70 1 0.8 0.45"]
 ONE_ULP = float(np.nextafter(np.float32(5), np.float32(0)))
 

@@ -9,7 +9,6 @@ to a frame on the frame's own rays, the fuzz scenes and committed goldens, deep 
 launch chunking, the device variants, isolation from frames and passes, a device Update, the Python
 Renderer, the error table and the CLI's --rays."""
 import ctypes as C
-import os
 import subprocess
 from pathlib import Path
 
@@ -18,13 +17,17 @@ import pytest
 import torch   # at collection, before librtx_hip.so is loaded: imported after it, torch finds no device
 
 import aov_ref
+import gpu_support as gs
 import oracle_bind
 import rayq_rays
 import rayq_ref
 import shade_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, DeviceAnimation, DeviceContext, Renderer, aov_host_planes
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
+from gpu_support import ctx  # noqa: F401
 from test_gpu_parity import POW_FREE, _compare
 from test_gpu_rayq import PARITY
 
@@ -32,7 +35,6 @@ pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parents[1]
 EXE = ROOT / "gp1_raytracer_2223_amd" / "lib" / "rtx_render"
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 W, H = 37, 23
 SEED = 7
 OA, RADIANCE, BRDF, COMBINED = (abi.RTX_MODE_OBSERVED_AREA, abi.RTX_MODE_RADIANCE, abi.RTX_MODE_BRDF,
@@ -42,37 +44,15 @@ FEW_CONFIGS = [(COMBINED, 1), (OA, 0)]
 UNIT_SETS = ("primary", "shadow")
 
 
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return shade_ref.build(tmp_path_factory.mktemp("shade_ref"))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = DeviceContext(DEV)
-    yield c
-    c.close()
-
-
-_scenes = {}
 _rays = {}
 _want = {}
-
-
-def _scene(name, t=-1.0):
-    if (name, t) not in _scenes:
-        hs = HostScene(name)
-        if t >= 0:
-            hs.update(t)
-        _scenes[(name, t)] = (hs, *hs.view())
-    return _scenes[(name, t)][1:]
 
 
 def _sets(checker, name, t=-1.0):
     """{set: rays} of a catalogue scene: every set that applies to it, made once and never written to."""
     key = (name, t)
     if key not in _rays:
-        s, cam = _scene(name, t)
+        s, cam = gs.view(name, t)
         sets = {"primary": rayq_ref.primary(checker, cam, W, H), "scatter": rayq_rays.scatter(SEED, 512),
                 "nonfinite": rayq_rays.nonfinite(s, SEED)}
         if s.n_lights:
@@ -90,7 +70,7 @@ def _ref(checker, name, t, k, mode, shadows):
     """The checker's (pixels, rgb, flags) of set k of a catalogue scene, computed once per configuration."""
     key = (name, t, k, mode, shadows)
     if key not in _want:
-        out = shade_ref.shade(checker, _scene(name, t)[0], _sets(checker, name, t)[k], shade_ref.params(mode, shadows))
+        out = shade_ref.shade(checker, gs.view(name, t)[0], _sets(checker, name, t)[k], shade_ref.params(mode, shadows))
         for a in out:
             a.setflags(write=False)
         _want[key] = out
@@ -113,7 +93,7 @@ def _exact(c, rays, p, want_px, want_rgb, what):
 
 @pytest.mark.parametrize("name,t", PARITY)
 def test_parity(ctx, checker, name, t):
-    s, _ = _scene(name, t)
+    s, _ = gs.view(name, t)
     ctx.upload(s)
     for k, rays in _sets(checker, name, t).items():
         assert 65 < rays.shape[0] <= 2048, (k, rays.shape)
@@ -139,7 +119,7 @@ def test_parity(ctx, checker, name, t):
 @pytest.mark.parametrize("name", ["W4_Bunny", "W3"])
 def test_primary_rays_equal_the_frame(ctx, checker, name):
     """Both are the device's own arithmetic, powf included: word for word on every scene."""
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     ctx.upload(s)
     rays = _sets(checker, name)["primary"]
     for mode, shadows in ALL_CONFIGS:
@@ -219,19 +199,14 @@ def test_hbm_stacks_cut_a_large_call_into_launches(ctx, checker):
     del keep
 
 
-def _torch():
-    assert torch.cuda.is_available(), "torch sees no GPU (was librtx_hip.so loaded before torch was imported?)"
-    return torch, torch.device("cuda", DEV)
-
-
 SENT = np.uint32(0xC0FFEE11)
 
 
 def test_device_variant_and_output_subsets(ctx, checker):
     """Rays and outputs as torch tensors.  Pixels and rgb lie in one sentinel-filled buffer of 32-bit
     words with guard words around them: a call writes the outputs it was given and nothing else."""
-    torch, dev = _torch()
-    s, _ = _scene("W4_Bunny")
+    torch, dev = gs.torch_device()
+    s, _ = gs.view("W4_Bunny")
     ctx.upload(s)
     rays = _sets(checker, "W4_Bunny")["aimed"]
     p = shade_ref.params(COMBINED, True)
@@ -258,16 +233,9 @@ def test_device_variant_and_output_subsets(ctx, checker):
             assert (host[keep] == SENT).all(), (n, use_px, use_rgb)
 
 
-def _colour_ok(c, s, cam, w=W, h=H):
-    """A colour frame of the pow-free Bunny scene equals the oracle's."""
-    gpx, grgb = c.render(cam, abi.make_params(w, h))
-    rpx, rrgb = oracle_bind.render(s, cam, abi.make_params(w, h))
-    assert np.array_equal(gpx, rpx) and np.array_equal(grgb.view(np.uint32), rrgb.view(np.uint32))
-
-
 def test_frames_and_passes_are_untouched(checker):
-    torch, dev = _torch()
-    s, cam = _scene("W4_Bunny")
+    torch, dev = gs.torch_device()
+    s, cam = gs.view("W4_Bunny")
     rays = _sets(checker, "W4_Bunny")["aimed"]
     n = rays.shape[0]
     want_px, want_rgb, _ = _ref(checker, "W4_Bunny", -1.0, "aimed", COMBINED, 1)
@@ -275,7 +243,7 @@ def test_frames_and_passes_are_untouched(checker):
     c = DeviceContext(DEV)
     try:
         c.upload(s)
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         spec, sched = c.spec_info(), c.split_info()
         pass_planes = c.render_aov(cam, p)
         px, rgb = c.shade_rays(rays, p)
@@ -288,7 +256,7 @@ def test_frames_and_passes_are_untouched(checker):
         c.gather_async(fpx)
         c.synchronize()
         assert np.array_equal(fpx, oracle_bind.render(s, cam, p)[0])
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         assert c.spec_info() == spec and c.split_info() == sched
         # a call between two frames in flight changes neither
         cam2 = abi.Camera()
@@ -312,7 +280,7 @@ def test_frames_and_passes_are_untouched(checker):
         c.set_supersample(2)
         assert shade_ref.same(*c.shade_rays(rays, p), want_px, want_rgb)
         c.set_supersample(1)
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
     finally:
         c.close()
 
@@ -377,7 +345,7 @@ def test_renderer_follows_mode_and_shadows(checker):
 
 
 def test_errors_leave_the_context_usable(checker):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     rays = _sets(checker, "W4_Bunny")["aimed"]
     want_px, want_rgb, _ = _ref(checker, "W4_Bunny", -1.0, "aimed", COMBINED, 1)
     n = rays.shape[0]
@@ -442,7 +410,7 @@ def test_errors_leave_the_context_usable(checker):
         fpx, frgb = c.shade_rays(rays, q)
         w_px, w_rgb, _ = shade_ref.shade(checker, s, rays, q)
         assert shade_ref.same(fpx, frgb, w_px, w_rgb) and not np.array_equal(fpx, want_px)
-        _colour_ok(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
     finally:
         c.close()
 

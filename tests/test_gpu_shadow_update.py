@@ -19,37 +19,25 @@ import pytest
 
 import aov_ref
 import devbuf
+import gpu_support as gs
 import oracle_bind
 import relight_ref
 import shadow_update_scenes as sus
 import shadowbuf
 import shadowforge
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, AOV_DEPTH, DeviceContext, Renderer, aov_host_planes
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import CONFIGS, DEV, POW_FREE_MODES
+from gpu_support import ctx  # noqa: F401
 from test_gpu_deep_bvh import deep_scene
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 ROOT = Path(__file__).resolve().parents[1]
 EXE = ROOT / "gp1_raytracer_2223_amd" / "lib" / "rtx_render"
 W, H = 37, 23   # five tile columns and three tile rows, one of each partial
-CONFIGS = [(mode, sh) for mode in range(4) for sh in (0, 1)]
-POW_FREE_MODES = (abi.RTX_MODE_OBSERVED_AREA, abi.RTX_MODE_RADIANCE)
-UP = C.POINTER(C.c_uint32)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = DeviceContext(DEV)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
 
 
 @pytest.fixture(scope="module")
@@ -364,17 +352,6 @@ def test_generic_kernel(files):
 
 # ---- 5. views and stripes -----------------------------------------------------------------------------------------
 
-def _cams3(cam):
-    cams = []
-    for k, dx in enumerate((0.0, 1.5, -2.0)):
-        c2 = abi.Camera()
-        C.memmove(C.byref(c2), C.byref(cam), C.sizeof(abi.Camera))
-        c2.origin[0] = cam.origin[0] + dx
-        c2.origin[1] = cam.origin[1] + 0.25 * k
-        cams.append(c2)
-    return cams
-
-
 @pytest.mark.parametrize("first", [0, 1])
 def test_views_and_stripes(ctx, checker, first):
     hs = HostScene("W4_Bunny")
@@ -382,7 +359,7 @@ def test_views_and_stripes(ctx, checker, first):
     s1 = _moved(s0, {2: (-1.0, 1.0, 1.0)})
     w, h, nv = 40, 32, 3
     n = w * h
-    cams = _cams3(cam)
+    cams = gs.cams3(cam)
     p = abi.make_params(w, h, 3, 1, abi.XRGB8888, 16, first, 2)
     want0 = [relight_ref.plane(checker, s0, cv, w, h)[0] for cv in cams]
     want1 = [relight_ref.plane(checker, s1, cv, w, h)[0] for cv in cams]
@@ -412,17 +389,6 @@ def test_views_and_stripes(ctx, checker, first):
 
 # ---- 6. 32 lights ---------------------------------------------------------------------------------------------------
 
-def _many_lights(k):
-    """k point lights inside the room, on a ring above the bunny; the last one where the base L0 is
-    (tests/test_gpu_relight.py's, re-stated)."""
-    out = []
-    for i in range(k - 1):
-        a = 2.0 * np.pi * i / max(k - 1, 1)
-        out.append(f"light point {3.5 * np.cos(a):.4f} {4.0 + 0.1 * i:.4f} {4.0 + 3.5 * np.sin(a):.4f}  "
-                   f"{6 + i % 5} {0.3 + 0.02 * i:.3f} 0.7 {1.0 - 0.02 * i:.3f}")
-    return out + ["light point 0 5 5  50 1 0.61 0.45"]
-
-
 def _lights_scene(tmp_path, name, lights):
     path = tmp_path / f"{name}.rtxscene"
     path.write_text("\n".join([sus.CAMERA, *sus.MATS, *sus.GEOMETRY["room"], *lights]) + "\n")
@@ -433,7 +399,7 @@ def test_32_lights_and_the_refusal_of_33(checker, tmp_path):
     c = DeviceContext(DEV)
     p = abi.make_params(W, H)
     try:
-        hs = _lights_scene(tmp_path, "lights32", _many_lights(32))
+        hs = _lights_scene(tmp_path, "lights32", gs.many_lights(32))
         s0, cam = hs.view()
         assert s0.n_lights == 32
         s1 = _moved(s0, {31: (1.5, 1.0, -2.0), 0: (-1.5, 0.5, -1.0)})
@@ -452,7 +418,7 @@ def test_32_lights_and_the_refusal_of_33(checker, tmp_path):
         assert c.refresh_shadows_async() == mask
         assert np.array_equal(shadowbuf.peek(c, W * H), bits1)
         _relit_equals_a_fresh_render(c, cam, W, H, 3, 1, "32 lights")
-        hs33 = _lights_scene(tmp_path, "lights33", _many_lights(33))
+        hs33 = _lights_scene(tmp_path, "lights33", gs.many_lights(33))
         s33, _ = hs33.view()
         assert s33.n_lights == 33
         c.upload(s33)
@@ -469,13 +435,6 @@ def test_32_lights_and_the_refusal_of_33(checker, tmp_path):
 
 # ---- 7. the error table and isolation ---------------------------------------------------------------------------------
 
-def _renders_correctly(c, s, cam):
-    p = abi.make_params(W, H)
-    px, rgb = c.render(cam, p)
-    rpx, rrgb = oracle_bind.render(s, cam, p)
-    assert np.array_equal(px, rpx) and np.array_equal(rgb.view(np.uint32), rrgb.view(np.uint32))
-
-
 def test_error_table(files):
     hs = HostScene("W4_Bunny")
     s, cam = hs.view()
@@ -490,15 +449,15 @@ def test_error_table(files):
         c.upload(s)
         assert upd(1) == abi.RTX_E_STATE                                                   # no hit pass
         assert lib.rtx_refresh_shadows_async(c.h, None) == abi.RTX_E_STATE
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         c.render_aov(cam, p, AOV_DEPTH)
         assert upd(1) == abi.RTX_E_STATE                                                   # fewer than four planes
         assert lib.rtx_refresh_shadows_async(c.h, None) == abi.RTX_E_STATE
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         c.render_aov(cam, p, AOV_ALL)
         assert upd(1) == abi.RTX_E_STATE and b"shadow pass" in lib.rtx_last_error(c.h)     # no shadow pass
         assert lib.rtx_time_shadows_update(c.h, 1, 1, C.byref(ms)) == abi.RTX_E_STATE
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         c.render_shadows_async()
         plane = shadowbuf.peek(c, W * H)
         assert upd(0) == abi.RTX_OK and upd(0b111) == abi.RTX_OK
@@ -510,12 +469,12 @@ def test_error_table(files):
         assert lib.rtx_time_shadows_update(c.h, 1, 1, None) == abi.RTX_E_INVALID
         assert c.time_shadows_update(0b101, 2) > 0.0
         assert np.array_equal(shadowbuf.peek(c, W * H), plane)
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         c.set_supersample(2)
         assert upd(1) == abi.RTX_E_UNSUPPORTED
         assert lib.rtx_refresh_shadows_async(c.h, None) == abi.RTX_E_UNSUPPORTED
         c.set_supersample(1)
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         # a light outside the mask moved: refused by name, the plane and its record as before
         s1 = _moved(s, {1: (0.5, 0.0, 0.5), 2: (0.0, 0.5, 0.0)})
         c.upload(s1)
@@ -529,7 +488,7 @@ def test_error_table(files):
         shadowforge.write(c, plane)
         c.upload(s)
         assert lib.rtx_relight_async(c.h, C.byref(p), 0) == abi.RTX_OK                    # the record was kept
-        _renders_correctly(c, s, cam)
+        gs.renders_correctly(c, s, cam, W, H)
         # a changed light count
         s2, cam2, _ = files("room", "base")
         s3, _, _ = files("room", "added")
@@ -537,12 +496,12 @@ def test_error_table(files):
         c.upload(s3)
         assert upd(0b1000) == abi.RTX_E_STATE and upd(0b1111) == abi.RTX_E_STATE
         assert b"lights" in lib.rtx_last_error(c.h)
-        _renders_correctly(c, s3, cam2)
+        gs.renders_correctly(c, s3, cam2, W, H)
         # a hit pass newer than the plane
         c.upload(s2)
         c.render_aov(cam2, p, AOV_ALL)
         assert upd(1) == abi.RTX_E_STATE and b"earlier hit pass" in lib.rtx_last_error(c.h)
-        _renders_correctly(c, s2, cam2)
+        gs.renders_correctly(c, s2, cam2, W, H)
     finally:
         c.close()
 
@@ -572,7 +531,7 @@ def test_isolation():
         assert not aov_ref.diff(after, before)
         assert c.spec_info() == spec and c.split_info() == split
         # queued between two frames of different cameras, it changes neither
-        cam_b = _cams3(cam)[1]
+        cam_b = gs.cams3(cam)[1]
         want_a, want_b = c.render(cam, p), c.render(cam_b, p)
         assert not np.array_equal(want_a[0], want_b[0])
         got = [(np.zeros(n, np.uint32), np.zeros(3 * n, np.float32)) for _ in range(2)]

@@ -10,16 +10,16 @@ import os
 import numpy as np
 import pytest
 
+import gpu_support as gs
 import oracle_bind
 import ss_ref
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import DeviceContext, DeviceGroup
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 from test_gpu_parity import POW_FREE, _compare
 
 pytestmark = pytest.mark.gpu
-
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 
 
 @pytest.fixture(scope="module")
@@ -42,24 +42,14 @@ def split_ctx():
     ctx.close()
 
 
-_scenes = {}
 _oracle = {}
-
-
-def _scene(name, t=-1.0):
-    if (name, t) not in _scenes:
-        hs = HostScene(name)
-        if t >= 0:
-            hs.update(t)
-        _scenes[(name, t)] = (hs, *hs.view())
-    return _scenes[(name, t)][1:]
 
 
 def _ref(name, t, W, H, k, mode=3, shadows=1):
     """The oracle's supersampled frame (computed once per case, never written to)."""
     key = (name, t, W, H, k, mode, shadows)
     if key not in _oracle:
-        s, cam = _scene(name, t)
+        s, cam = gs.view(name, t)
         _, hi = oracle_bind.render(s, cam, abi.make_params(k * W, k * H, mode, shadows))
         rgb = ss_ref.resolve(hi, W, H, k)
         px = ss_ref.quantize(rgb)
@@ -81,7 +71,7 @@ PARITY = [(n, -1.0, k) for n in ("W4_Bunny", "W2", "W3") for k in (2, 4, 8)] + [
 @pytest.mark.parametrize("name,t,k", PARITY)
 def test_parity(ss_ctx, name, t, k):
     W, H = 37, 23   # k = 2: 74 x 46 samples, neither a multiple of the 8 x 8 wave tile
-    s, cam = _scene(name, t)
+    s, cam = gs.view(name, t)
     ss_ctx.upload(s)
     ss_ctx.set_supersample(k)
     gpx, grgb = ss_ctx.render(cam, abi.make_params(W, H))
@@ -90,7 +80,7 @@ def test_parity(ss_ctx, name, t, k):
 
 
 def test_k1_after_k4_is_todays_frame(ss_ctx):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     ss_ctx.upload(s)
     ss_ctx.set_supersample(4)
     ss_ctx.render(cam, abi.make_params(80, 60))       # a larger frame first: its pixels stay in the buffer
@@ -112,7 +102,7 @@ def test_k1_after_k4_is_todays_frame(ss_ctx):
 @pytest.mark.parametrize("shadows", [0, 1])
 def test_modes(ss_ctx, mode, shadows):
     W, H = 40, 30
-    s, cam = _scene("W3")
+    s, cam = gs.view("W3")
     ss_ctx.upload(s)
     ss_ctx.set_supersample(2)
     gpx, grgb = ss_ctx.render(cam, abi.make_params(W, H, mode, shadows))
@@ -122,7 +112,7 @@ def test_modes(ss_ctx, mode, shadows):
 
 def test_stripes_stitch_bit_identical(ss_ctx):
     W, H = 64, 48
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     ss_ctx.upload(s)
     ss_ctx.set_supersample(2)
     full, full_rgb = ss_ctx.render(cam, abi.make_params(W, H))
@@ -140,7 +130,7 @@ def test_stripes_stitch_bit_identical(ss_ctx):
 
 def test_views_equal_single_view_frames(ss_ctx):
     W, H, N = 37, 23, 2
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     views = (abi.Camera * N)()
     for f in range(N):
         C.memmove(C.byref(views[f]), C.byref(cam), C.sizeof(abi.Camera))
@@ -161,7 +151,7 @@ def test_views_equal_single_view_frames(ss_ctx):
 
 def test_group_equals_single_context(ss_ctx):
     W, H = 64, 48
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     ss_ctx.upload(s)
     ss_ctx.set_supersample(2)
     want = ss_ctx.render(cam, abi.make_params(W, H))
@@ -180,7 +170,7 @@ def test_group_equals_single_context(ss_ctx):
 
 def test_split_path(split_ctx):
     W, H = 64, 48
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     split_ctx.upload(s)
     split_ctx.set_supersample(2)
     p = abi.make_params(W, H)
@@ -204,7 +194,7 @@ def test_light_major_frame():
         del os.environ["RTX_LIGHT_MAJOR"]
     try:
         W, H = 64, 48
-        s, cam = _scene("W4_Bunny")
+        s, cam = gs.view("W4_Bunny")
         ctx.upload(s)
         ctx.set_supersample(2)
         rpx, rrgb = _ref("W4_Bunny", -1.0, W, H, 2)
@@ -258,7 +248,7 @@ def test_renderer_and_cli_take_the_factor(tmp_path):
 
 
 def test_work_counters_count_the_sample_frame(ss_ctx):
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     ss_ctx.upload(s)
     ss_ctx.set_supersample(2)
     a = ss_ctx.count_work(cam, abi.make_params(64, 48))
@@ -270,7 +260,7 @@ def test_work_counters_count_the_sample_frame(ss_ctx):
 
 def test_errors_leave_the_factor_and_the_context_intact(ss_ctx):
     W, H = 37, 23
-    s, cam = _scene("W4_Bunny")
+    s, cam = gs.view("W4_Bunny")
     lib, h = ss_ctx.lib, ss_ctx.h
     ss_ctx.upload(s)
     ss_ctx.set_supersample(2)

@@ -3,7 +3,6 @@ context's frame is still in flight on the device selects its heavy tiles with a 
 and pauses the tuner.  Only the split of the work changes, so every frame must equal the one a
 context rendering alone produces, and the reference's; contexts leaving the process-wide registry
 (rtx_destroy) while others are in flight must not disturb them."""
-import os
 
 import numpy as np
 import pytest
@@ -12,10 +11,9 @@ import oracle_bind
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import DeviceContext
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import DEV
 
 pytestmark = pytest.mark.gpu
-
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 
 
 def _alone(s, cam, p):

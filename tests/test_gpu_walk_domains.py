@@ -17,29 +17,18 @@ import rayq_ref
 import relight_ref
 import shade_ref
 import walk_domains as WD
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.renderer import AOV_ALL, DeviceContext
+from gpu_support import DEV
+from gpu_support import ctx  # noqa: F401
 from test_gpu_adaptive import _compose, _oracle_ps, _same
 from test_gpu_rayq import _check
 
 pytestmark = pytest.mark.gpu
 
-DEV = int(os.environ.get("RTX_TEST_DEVICE", "0"))
 FW, FH = 64, 48
 MODES = (abi.RTX_MODE_OBSERVED_AREA, abi.RTX_MODE_COMBINED)
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    """relight_ref's library: a superset of shade_ref's, rayq_ref's and aov_ref's."""
-    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = DeviceContext(DEV)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")

@@ -1,13 +1,13 @@
 """The C++ host scene layer (librtx_host.so) against the reference's own scene
 construction: world-space triangles, BVH node arrays and the BVH-permuted triangle order
 must be bit-identical (tests/golden/scene_*.npz, obj_*.npz)."""
-import hashlib
 import re
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as gs
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene, parse_obj, RENDERABLE, SCENES
 
@@ -18,10 +18,6 @@ REF_RES = G / "obj"
 def _u(a):
     a = np.asarray(a)
     return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def _sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def _scene_files():
@@ -53,10 +49,10 @@ def test_scene_matches_reference(path):
         p = f"mesh{i}_"
         links = m["node_links"].reshape(-1, 3)
         if g[p + "indices"].dtype.kind == "U":   # large mesh: SHA-256 goldens
-            assert _sha(m["tpositions"]) == str(g[p + "tpositions"][0])
-            assert _sha(m["indices"]) == str(g[p + "indices"][0])
-            assert _sha(m["tnormals"]) == str(g[p + "tnormals"][0])
-            assert _sha(m["node_bounds"]) == str(g[p + "node_bounds"][0])
+            assert gs.sha(m["tpositions"]) == str(g[p + "tpositions"][0])
+            assert gs.sha(m["indices"]) == str(g[p + "indices"][0])
+            assert gs.sha(m["tnormals"]) == str(g[p + "tnormals"][0])
+            assert gs.sha(m["node_bounds"]) == str(g[p + "node_bounds"][0])
             continue
         assert np.array_equal(_u(m["tpositions"]), _u(g[p + "tpositions"]))
         assert np.array_equal(m["indices"], g[p + "indices"])

@@ -7,52 +7,22 @@ wave-uniform scene read into a per-lane vector load, +17 % kernel time, with cor
   * per-lane vector loads are confined to the few per-hit gathers (material, hit record),
   * no scratch, and a VGPR count that keeps >= 7 waves per SIMD.
 """
-import os
 import re
-import subprocess
 
 import pytest
 
-LLVM = "/opt/rocm/lib/llvm/bin"
+import isa_tools
+
 # product variants of the PHASE-0 render kernel (COUNT = false, default-depth stack)
 PRODUCT = "_Z17rtx_render_kernelILb0ELi0ELb0E"
 DEEP = "_Z17rtx_render_kernelILb0ELi0ELb1E"
 
 
-def _code_object(tmp_path, lib):
-    fb = tmp_path / "fatbin.bin"
-    co = tmp_path / "gfx950.co"
-    subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, str(fb)], check=True)
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fb}", f"--output={co}"], check=True)
-    return co
-
-
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    if not os.path.exists(f"{LLVM}/clang-offload-bundler"):
-        pytest.skip("ROCm LLVM tools not present")
-    from gp1_raytracer_2223_amd import build
-    lib = os.path.join(os.path.dirname(build.__file__), "lib", "librtx_hip.so")
-    if not os.path.exists(lib):
-        build.build_hip()
-    co = _code_object(tmp_path_factory.mktemp("isa"), lib)
-    dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--mcpu=gfx950", str(co)], check=True,
-                         capture_output=True, text=True).stdout
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True,
-                           text=True).stdout
-    out = {}
-    for m in re.finditer(r"^[0-9a-f]+ <(_Z17rtx_render_kernel\w+)>:", dis, re.M):
-        name = m.group(1)
-        body = dis[m.end():dis.index("s_endpgm", m.end())]
-        meta = {}
-        for block in notes.split("  - .")[1:]:
-            if re.search(rf"\.name:\s+{name}\b", block):
-                for key in ("vgpr_count", "sgpr_count", "private_segment_fixed_size"):
-                    mm = re.search(rf"\.{key}:\s+(\d+)", block)
-                    if mm:
-                        meta[key] = int(mm.group(1))
-        out[name] = (body, meta)
+def isa():
+    """{symbol: (body up to the first s_endpgm, meta)} of every rtx_render_kernel instantiation."""
+    out = {n: (body[:body.index("s_endpgm")], meta)
+           for n, (body, meta) in isa_tools.kernels(isa_tools.product_library(), r"_Z17rtx_render_kernel\w+$").items()}
     assert any(n.startswith(PRODUCT) for n in out), sorted(out)
     return out
 

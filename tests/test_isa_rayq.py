@@ -3,45 +3,19 @@ as tests/test_isa.py does for the render kernel): the six instantiations of rtx_
 HSTK> use no scratch, fetch node pairs and triangles through the scalar unit, and stay at 8 waves per
 SIMD by their registers (profiles/rayq/resource_usage.txt: 25-33 VGPRs; the next occupancy step is
 64)."""
-import os
 import re
-import subprocess
 
 import pytest
 
-from test_isa import LLVM, _code_object
+import isa_tools
 
-KERNEL = re.compile(r"^[0-9a-f]+ <(_Z16rtx_query_kernelILb([01])ELb([01])ELb([01])E\w+)>:", re.M)
+KERNEL = r"_Z16rtx_query_kernelILb([01])ELb([01])ELb([01])E\w+$"   # <ANY, DEEP, HSTK>
 VGPR_STEP = 64   # 512 / 64 = 8 waves per SIMD
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    if not os.path.exists(f"{LLVM}/clang-offload-bundler"):
-        pytest.skip("ROCm LLVM tools not present")
-    from gp1_raytracer_2223_amd import build
-    lib = os.path.join(os.path.dirname(build.__file__), "lib", "librtx_hip.so")
-    if not os.path.exists(lib):
-        build.build_hip()
-    co = _code_object(tmp_path_factory.mktemp("isa_rayq"), lib)
-    dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--mcpu=gfx950", str(co)], check=True, capture_output=True,
-                         text=True).stdout
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True,
-                           text=True).stdout
-    header = re.compile(r"^[0-9a-f]+ <", re.M)
-    out = {}
-    for m in KERNEL.finditer(dis):
-        nxt = header.search(dis, m.end())   # (the kernel has several s_endpgm: its body runs to the next symbol)
-        body = dis[m.end():nxt.start() if nxt else len(dis)]
-        meta = {}
-        for block in notes.split("  - .")[1:]:
-            if re.search(rf"\.name:\s+{m.group(1)}\b", block):
-                for key in ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size"):
-                    mm = re.search(rf"\.{key}:\s+(\d+)", block)
-                    if mm:
-                        meta[key] = int(mm.group(1))
-        out[tuple(int(m.group(k)) for k in (2, 3, 4))] = (body, meta)
-    return out
+def kernels():
+    return isa_tools.kernels(isa_tools.product_library(), KERNEL)
 
 
 def test_the_six_instantiations_exist(kernels):

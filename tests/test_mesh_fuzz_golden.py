@@ -240,8 +240,9 @@ def test_frames_show_the_meshes(tmp_path):
     case's final frame (of at least two triangles where the mesh has nine or more) — but for `overflow`, where
     Moller-Trumbore itself overflows at 1e19 and no ray hits a triangle, in the reference either."""
     import aov_ref
+    import checkers
     from gp1_raytracer_2223_amd.scene import HostScene
-    lib = aov_ref.build(tmp_path)
+    lib = checkers.lib()
     for family, seed in mesh_fuzz.COMMITTED:
         case = mesh_fuzz.make(family, seed)
         d = tmp_path / case.name

@@ -2,79 +2,47 @@
 sets' own conditions (so that no GPU test of them is vacuous), the checker of tests/rayq_ref.py against
 the hit pass's checker, and its committed goldens."""
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_surface
 import aov_ref
+import gpu_support as gs
 import rayq_rays
 import rayq_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
-from gp1_raytracer_2223_amd.scene import HostScene
 
-ROOT = Path(__file__).resolve().parents[1]
-INC = ROOT / "include"
 W, H = 37, 23
 SEED = 7
-SYMBOLS = ["rtx_trace_rays", "rtx_occluded", "rtx_trace_rays_device", "rtx_occluded_device"]
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return rayq_ref.build(tmp_path_factory.mktemp("rayq_ref"))
-
-
-_scenes = {}
-
-
-def _scene(name):
-    if name not in _scenes:
-        hs = HostScene(name)
-        _scenes[name] = (hs, *hs.view())
-    return _scenes[name][1:]
 
 
 def test_header_declares_and_abi_binds_the_query_symbols(tmp_path):
     """rtx_ray as the C compiler sees it equals the ctypes mirror (32 bytes), the four entry points are
     declared as the issue states them, exported and bound, and the ABI version stays 2."""
     fields = ["origin", "direction", "tmin", "tmax"]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "rtx.h"', "int main(void) {",
-           'printf("size %zu\\n", sizeof(rtx_ray));', 'printf("version %d\\n", RTX_ABI_VERSION);']
-    src += [f'printf("{f} %zu\\n", offsetof(rtx_ray, {f}));' for f in fields]
-    src += ["int (*f0)(rtx_ctx*, const rtx_ray*, uint32_t, uint32_t, const rtx_aov_planes*) = rtx_trace_rays;",
-            "int (*f1)(rtx_ctx*, const rtx_ray*, uint32_t, uint8_t*) = rtx_occluded;",
-            "int (*f2)(rtx_ctx*, const rtx_ray*, uint32_t, uint32_t, const rtx_aov_planes*) = rtx_trace_rays_device;",
-            "int (*f3)(rtx_ctx*, const rtx_ray*, uint32_t, uint8_t*) = rtx_occluded_device;",
-            "return !(f0 && f1 && f2 && f3); }"]
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-I{INC}", str(tmp_path / "l.c"), "-o", str(tmp_path / "l"),
-                    f"-L{abi.LIB_DIR}", "-lrtx_hip", f"-Wl,-rpath,{abi.LIB_DIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    out = subprocess.run([str(tmp_path / "l")], check=True, capture_output=True, text=True).stdout
+    prints = ['printf("size %zu\\n", sizeof(rtx_ray));', 'printf("version %d\\n", RTX_ABI_VERSION);']
+    prints += [f'printf("{f} %zu\\n", offsetof(rtx_ray, {f}));' for f in fields]
+    trace = "int (*)(rtx_ctx*, const rtx_ray*, uint32_t, uint32_t, const rtx_aov_planes*)"
+    occluded = "int (*)(rtx_ctx*, const rtx_ray*, uint32_t, uint8_t*)"
+    out = abi_surface.declared_exported_and_bound(tmp_path, {
+        "rtx_trace_rays": trace, "rtx_occluded": occluded, "rtx_trace_rays_device": trace, "rtx_occluded_device": occluded,
+    }, {}, statements=prints)
     c = {k: int(v) for k, v in (line.split() for line in out.strip().splitlines())}
     assert c["version"] == 2 and abi.load_hip().rtx_abi_version() == 2
     assert c["size"] == 32 == C.sizeof(abi.Ray)
     assert [n for n, _ in abi.Ray._fields_] == fields
     for f in fields:
         assert c[f] == getattr(abi.Ray, f).offset, f
-    prod = (INC / "rtx.h").read_text()
     lib = abi.load_hip()
-    for n in SYMBOLS:
-        assert re.search(rf"^int {n}\(", prod, re.M), n
-        assert n in abi.HIP_SYMBOLS and getattr(lib, n).argtypes, n
     assert lib.rtx_trace_rays.argtypes[1]._type_ is abi.Ray and lib.rtx_trace_rays.argtypes[4]._type_ is abi.AovPlanes
 
 
 def test_the_cpp_mirror_compiles(tmp_path):
-    (tmp_path / "m.cpp").write_text(
-        '#include "rtx_renderer.hpp"\n'
-        "rtx::Renderer::AovFrame (rtx::Renderer::*f0)(const std::vector<rtx_ray>&, uint32_t) = &rtx::Renderer::TraceRays;\n"
-        "std::vector<uint8_t> (rtx::Renderer::*f1)(const std::vector<rtx_ray>&) = &rtx::Renderer::Occluded;\n"
-        "int main() { return !(f0 && f1); }\n")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", f"-I{INC}", str(tmp_path / "m.cpp")],
-                   check=True)
+    abi_surface.cpp_mirror_compiles(tmp_path, [
+        ("rtx::Renderer::AovFrame (rtx::Renderer::*)(const std::vector<rtx_ray>&, uint32_t)", "TraceRays"),
+        ("std::vector<uint8_t> (rtx::Renderer::*)(const std::vector<rtx_ray>&)", "Occluded")])
 
 
 def _shares(planes):
@@ -84,7 +52,7 @@ def _shares(planes):
 
 
 def test_ray_sets_shapes_and_recipes():
-    s, _ = _scene("W4_Bunny")
+    s, _ = gs.view("W4_Bunny")
     for r in (rayq_rays.scatter(SEED), rayq_rays.aimed(s, SEED), rayq_rays.octant(s, SEED),
               rayq_rays.nonfinite(s, SEED)):
         assert r.dtype == np.float32 and r.ndim == 2 and r.shape[1] == 8 and 65 < r.shape[0] <= 2048
@@ -114,7 +82,7 @@ def test_ray_sets_shapes_and_recipes():
 
 
 def test_floors_aimed_bunny(checker):
-    s, _ = _scene("W4_Bunny")
+    s, _ = gs.view("W4_Bunny")
     rays = rayq_rays.aimed(s, SEED)
     p = rayq_ref.trace(checker, s, rays)
     sh = _shares(p)
@@ -126,13 +94,13 @@ def test_floors_aimed_bunny(checker):
 
 
 def test_floors_aimed_optional(checker):
-    s, _ = _scene("W4_Optional")
+    s, _ = gs.view("W4_Optional")
     sh = _shares(rayq_ref.trace(checker, s, rayq_rays.aimed(s, SEED)))
     assert sh[3] >= 0.25 and sh[0] >= 0.05, sh
 
 
 def test_floors_scatter(checker):
-    s, _ = _scene("W1")
+    s, _ = gs.view("W1")
     rays = rayq_rays.scatter(SEED)
     sh = _shares(rayq_ref.trace(checker, s, rays))
     assert sh[1] >= 0.03 and sh[2] >= 0.25 and sh[0] >= 0.25, sh
@@ -142,7 +110,7 @@ def test_floors_scatter(checker):
 
 @pytest.mark.parametrize("name", ["W4_Bunny", "W4_Reference"])
 def test_floors_shadow(checker, name):
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     rays, pixel = rayq_ref.shadow(checker, s, cam, W, H, 0)
     assert rays.shape[0] == pixel.size > 64 and (np.diff(pixel.astype(np.int64)) > 0).all()
     occ = rayq_ref.occluded(checker, s, rays).mean()
@@ -152,7 +120,7 @@ def test_floors_shadow(checker, name):
 @pytest.mark.parametrize("name", ["W1", "W3", "W4_Reference", "W4_Bunny"])
 def test_primary_rays_give_the_hit_pass_planes(checker, name):
     """The checker on its own primary rays equals aov_ref.c's frame, word for word."""
-    s, cam = _scene(name)
+    s, cam = gs.view(name)
     got = rayq_ref.trace(checker, s, rayq_ref.primary(checker, cam, W, H))
     want = aov_ref.planes(checker, s, cam, W, H)
     for k in aov_ref.NAMES:

@@ -6,58 +6,41 @@ word for word when the bits are Scene::DoesHit's answers; and the new kernels' c
 pass (PHASE 9) is instantiated where deferred shading (PHASE 8) is, nothing uses scratch, and the relight kernel
 uses no LDS."""
 import ctypes as C
-import os
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_surface
 import aov_ref
 import rayq_ref
 import relight_ref
 import scene_fuzz
 import shade_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene
 
-ROOT = Path(__file__).resolve().parents[1]
-INC = ROOT / "include"
-EXE = ROOT / "gp1_raytracer_2223_amd" / "lib" / "rtx_render"
 W, H = 37, 23
-SYMBOLS = ["rtx_render_shadows_async", "rtx_download_shadows", "rtx_gather_shadows_async", "rtx_device_shadow_buffer",
-           "rtx_relight_async", "rtx_relight"]
-DIAG = ["rtx_time_shadows", "rtx_time_relight"]
 PIN = ["W4_Bunny", "W3", "W4_Reference", "W1"]
 
 
 def test_header_declares_and_abi_binds_the_symbols(tmp_path):
     """Every entry point is declared as the contract states it, exported and bound, and the ABI version stays 2."""
-    src = ['#include "rtx.h"', '#include "rtx_diag.h"', "int main(void) {",
-           "int (*f0)(rtx_ctx*) = rtx_render_shadows_async;",
-           "int (*f1)(rtx_ctx*, uint32_t*) = rtx_download_shadows;",
-           "int (*f2)(rtx_ctx*, uint32_t*) = rtx_gather_shadows_async;",
-           "int (*f3)(rtx_ctx*, uint32_t**) = rtx_device_shadow_buffer;",
-           "int (*f4)(rtx_ctx*, const rtx_render_params*, int) = rtx_relight_async;",
-           "int (*f5)(rtx_ctx*, const rtx_render_params*, uint32_t*, float*) = rtx_relight;",
-           "int (*f6)(rtx_ctx*, int, float*) = rtx_time_shadows;",
-           "int (*f7)(rtx_ctx*, const rtx_render_params*, int, int, float*) = rtx_time_relight;",
-           "return !(f0 && f1 && f2 && f3 && f4 && f5 && f6 && f7 && RTX_ABI_VERSION == 2 && RTX_AOV_ALL == 15); }"]
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-I{INC}", str(tmp_path / "l.c"), "-o", str(tmp_path / "l"),
-                    f"-L{abi.LIB_DIR}", "-lrtx_hip", f"-Wl,-rpath,{abi.LIB_DIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    subprocess.run([str(tmp_path / "l")], check=True)
-    prod, diag = (INC / "rtx.h").read_text(), (INC / "rtx_diag.h").read_text()
+    abi_surface.declared_exported_and_bound(tmp_path, {
+        "rtx_render_shadows_async": "int (*)(rtx_ctx*)",
+        "rtx_download_shadows": "int (*)(rtx_ctx*, uint32_t*)",
+        "rtx_gather_shadows_async": "int (*)(rtx_ctx*, uint32_t*)",
+        "rtx_device_shadow_buffer": "int (*)(rtx_ctx*, uint32_t**)",
+        "rtx_relight_async": "int (*)(rtx_ctx*, const rtx_render_params*, int)",
+        "rtx_relight": "int (*)(rtx_ctx*, const rtx_render_params*, uint32_t*, float*)",
+    }, {
+        "rtx_time_shadows": "int (*)(rtx_ctx*, int, float*)",
+        "rtx_time_relight": "int (*)(rtx_ctx*, const rtx_render_params*, int, int, float*)",
+    }, ["RTX_ABI_VERSION == 2", "RTX_AOV_ALL == 15"])
     lib = abi.load_hip()
     assert lib.rtx_abi_version() == 2
-    for n in SYMBOLS:
-        assert re.search(rf"^int {n}\(", prod, re.M), n
-    for n in DIAG:
-        assert re.search(rf"^int {n}\(", diag, re.M) and n not in prod, n
-    for n in SYMBOLS + DIAG:
-        assert n in abi.HIP_SYMBOLS and getattr(lib, n).argtypes, n
-        assert getattr(lib, n).restype is C.c_int, n
     a = lib.rtx_relight.argtypes
     assert a[1]._type_ is abi.RenderParams and a[2]._type_ is C.c_uint32 and a[3]._type_ is C.c_float
     assert lib.rtx_relight_async.argtypes[2:] == [C.c_int]
@@ -83,34 +66,18 @@ def test_null_context_is_invalid_without_a_device():
 
 
 def test_the_cpp_mirror_compiles(tmp_path):
-    (tmp_path / "m.cpp").write_text(
-        '#include "rtx_renderer.hpp"\n'
-        "std::vector<uint32_t> (rtx::Renderer::*f0)() = &rtx::Renderer::RenderShadows;\n"
-        "void (rtx::Renderer::*f1)() = &rtx::Renderer::Relight;\n"
-        "int main() { return !(f0 && f1); }\n")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", f"-I{INC}", str(tmp_path / "m.cpp")],
-                   check=True)
+    abi_surface.cpp_mirror_compiles(tmp_path, [("std::vector<uint32_t> (rtx::Renderer::*)()", "RenderShadows"),
+                                               ("void (rtx::Renderer::*)()", "Relight")])
 
 
 @pytest.mark.parametrize("extra", [["--ss", "2"], ["--adaptive", "2,32"], ["--rays", "rays.f32"], ["--benchmark"],
                                    ["--benchmark", "2"], ["--sequence", "0.5,1.0"], ["--deferred"]],
                          ids=["ss", "adaptive", "rays", "benchmark", "benchmark_n", "sequence", "deferred"])
 def test_cli_refuses_relight_in_a_bad_combination_before_device_work(tmp_path, extra):
-    assert EXE.exists(), "lib/rtx_render is not built"
-    for args in (["--relight"] + extra, extra + ["--relight", "--aov", "planes"]):
-        r = subprocess.run([str(EXE), "W4_Bunny", "64", "48", "--out", "o.bmp"] + args, capture_output=True, text=True,
-                           cwd=tmp_path, timeout=60)
-        assert r.returncode != 0, args
-        assert "--relight" in r.stderr, (args, r.stderr)
-        assert list(tmp_path.iterdir()) == [], args
+    abi_surface.cli_refuses(tmp_path, "--relight", ["--relight"] + extra, extra + ["--relight", "--aov", "planes"])
 
 
 # ---- the checker: the record, the ray and one bit per light are enough -------------------------------
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
-
 
 def _equals_shade_ref(checker, s, cam, what):
     rays = rayq_ref.primary(checker, cam, W, H)
@@ -165,14 +132,11 @@ def _phase_kernels(notes: str, phase: int) -> dict:
     return found
 
 
-def test_the_new_kernels_metadata(tmp_path):
-    from test_isa import LLVM, _code_object
-    if not os.path.exists(f"{LLVM}/clang-offload-bundler"):
-        pytest.skip("ROCm LLVM tools not present")
+def test_the_new_kernels_metadata():
+    import isa_tools
     lib = Path(abi.LIB_DIR) / "librtx_hip.so"
     assert lib.exists(), "librtx_hip.so is not built"
-    co = _code_object(tmp_path, str(lib))
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True, text=True).stdout
+    _, notes = isa_tools.listing(str(lib))
     shade8, shadow9 = _phase_kernels(notes, 8), _phase_kernels(notes, 9)
     # the shadow pass walks as deferred shading does: the same (DEEP, SPEC, HSTK, CULLK) set, none with scratch
     assert len(shadow9) == 13 and set(shadow9) == set(shade8), (sorted(shadow9), sorted(shade8))

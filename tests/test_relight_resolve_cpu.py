@@ -5,7 +5,6 @@ refuses --resolve in a bad combination before any device work; the checkers agre
 word for word); and the new kernel's code-object metadata: a name of its own beside the one rtx_relight_kernel, no
 scratch, no LDS, and no more registers than the generic render kernel may use."""
 import ctypes as C
-import os
 import re
 import subprocess
 from pathlib import Path
@@ -13,43 +12,30 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import abi_surface
 import rayq_ref
 import relight_ref
 import shade_ref
 import ss_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import CONFIGS
 
 ROOT = Path(__file__).resolve().parents[1]
-INC = ROOT / "include"
 EXE = ROOT / "gp1_raytracer_2223_amd" / "lib" / "rtx_render"
 W, H = 37, 23
-SYMBOLS = ["rtx_relight_resolve_async", "rtx_relight_resolve"]
-DIAG = ["rtx_time_relight_resolve"]
-CONFIGS = [(mode, sh) for mode in range(4) for sh in (0, 1)]
 
 
 def test_header_declares_and_abi_binds_the_symbols(tmp_path):
     """Every entry point is declared as the issue states it, exported and bound, and the ABI version stays 2."""
-    src = ['#include "rtx.h"', '#include "rtx_diag.h"', "int main(void) {",
-           "int (*f0)(rtx_ctx*, const rtx_render_params*, uint32_t, int) = rtx_relight_resolve_async;",
-           "int (*f1)(rtx_ctx*, const rtx_render_params*, uint32_t, uint32_t*, float*) = rtx_relight_resolve;",
-           "int (*f2)(rtx_ctx*, const rtx_render_params*, uint32_t, int, int, float*) = rtx_time_relight_resolve;",
-           "return !(f0 && f1 && f2 && RTX_ABI_VERSION == 2); }"]
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-I{INC}", str(tmp_path / "l.c"), "-o", str(tmp_path / "l"),
-                    f"-L{abi.LIB_DIR}", "-lrtx_hip", f"-Wl,-rpath,{abi.LIB_DIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    subprocess.run([str(tmp_path / "l")], check=True)
-    prod, diag = (INC / "rtx.h").read_text(), (INC / "rtx_diag.h").read_text()
+    abi_surface.declared_exported_and_bound(tmp_path, {
+        "rtx_relight_resolve_async": "int (*)(rtx_ctx*, const rtx_render_params*, uint32_t, int)",
+        "rtx_relight_resolve": "int (*)(rtx_ctx*, const rtx_render_params*, uint32_t, uint32_t*, float*)",
+    }, {"rtx_time_relight_resolve": "int (*)(rtx_ctx*, const rtx_render_params*, uint32_t, int, int, float*)"},
+        ["RTX_ABI_VERSION == 2"])
     lib = abi.load_hip()
     assert lib.rtx_abi_version() == 2
-    for n in SYMBOLS:
-        assert re.search(rf"^int {n}\(", prod, re.M), n
-    for n in DIAG:
-        assert re.search(rf"^int {n}\(", diag, re.M) and n not in prod, n
-    for n in SYMBOLS + DIAG:
-        assert n in abi.HIP_SYMBOLS and getattr(lib, n).argtypes, n
-        assert getattr(lib, n).restype is C.c_int, n
     a = lib.rtx_relight_resolve.argtypes
     assert a[1]._type_ is abi.RenderParams and a[2] is C.c_uint32
     assert a[3]._type_ is C.c_uint32 and a[4]._type_ is C.c_float
@@ -73,13 +59,8 @@ def test_null_context_is_invalid_without_a_device():
 
 
 def test_the_cpp_mirror_compiles(tmp_path):
-    (tmp_path / "m.cpp").write_text(
-        '#include "rtx_renderer.hpp"\n'
-        "void (rtx::Renderer::*f0)(uint32_t) = &rtx::Renderer::RenderSamplePasses;\n"
-        "void (rtx::Renderer::*f1)() = &rtx::Renderer::RelightResolved;\n"
-        "int main() { return !(f0 && f1); }\n")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", f"-I{INC}", str(tmp_path / "m.cpp")],
-                   check=True)
+    abi_surface.cpp_mirror_compiles(tmp_path, [("void (rtx::Renderer::*)(uint32_t)", "RenderSamplePasses"),
+                                               ("void (rtx::Renderer::*)()", "RelightResolved")])
 
 
 @pytest.mark.parametrize("args", [["--resolve", "2"], ["--resolve", "4", "--deferred"],
@@ -88,12 +69,7 @@ def test_the_cpp_mirror_compiles(tmp_path):
                                   ["--relight", "--resolve", "16"], ["--relight", "--resolve", "2x"], ["--relight", "--resolve"]],
                          ids=["no_relight", "deferred_instead", "aov", "k3", "k1", "k16", "k2x", "no_k"])
 def test_cli_refuses_resolve_in_a_bad_combination_before_device_work(tmp_path, args):
-    assert EXE.exists(), "lib/rtx_render is not built"
-    r = subprocess.run([str(EXE), "W4_Bunny", "64", "48", "--out", "o.bmp"] + args, capture_output=True, text=True,
-                       cwd=tmp_path, timeout=60)
-    assert r.returncode == 2, (args, r.returncode, r.stderr)
-    assert "--resolve" in r.stderr, (args, r.stderr)
-    assert list(tmp_path.iterdir()) == [], args
+    abi_surface.cli_refuses(tmp_path, "--resolve", args, returncode=2)
 
 
 def test_cli_still_refuses_relight_with_ss_and_names_resolve_in_its_usage(tmp_path):
@@ -105,11 +81,6 @@ def test_cli_still_refuses_relight_with_ss_and_names_resolve_in_its_usage(tmp_pa
 
 
 # ---- the checkers agree on the resolved frame ---------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
-
 
 @pytest.mark.parametrize("k", [2, 4, 8])
 @pytest.mark.parametrize("name", ["W4_Bunny", "W3"])
@@ -134,14 +105,11 @@ def test_resolved_relight_ref_equals_resolved_shade_ref(checker, name, k):
 
 # ---- the new kernel, from the code object's metadata only ---------------------------------------------------
 
-def test_the_resolve_kernels_metadata(tmp_path):
-    from test_isa import LLVM, _code_object
-    if not os.path.exists(f"{LLVM}/clang-offload-bundler"):
-        pytest.skip("ROCm LLVM tools not present")
+def test_the_resolve_kernels_metadata():
+    import isa_tools
     lib = Path(abi.LIB_DIR) / "librtx_hip.so"
     assert lib.exists(), "librtx_hip.so is not built"
-    co = _code_object(tmp_path, str(lib))
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True, text=True).stdout
+    _, notes = isa_tools.listing(str(lib))
     blocks = notes.split("  - .")[1:]
     resolve = [b for b in blocks if re.search(r"\.name:\s+_Z26rtx_relight_resolve_kernel\w+", b)]
     assert len(resolve) == 3, "one instantiation per factor: 2 x 2, 4 x 4, 8 x 8"

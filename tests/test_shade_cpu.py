@@ -2,51 +2,30 @@
 oracle's frames, the ABI additions, the ray sets' own conditions (so that no GPU test of them is vacuous)
 and the committed goldens."""
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_surface
+import gpu_support as gs
 import oracle_bind
 import rayq_rays
 import rayq_ref
 import shade_ref
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
-from gp1_raytracer_2223_amd.scene import HostScene
 
-ROOT = Path(__file__).resolve().parents[1]
-INC = ROOT / "include"
 W, H = 37, 23
 SEED = 7
-SYMBOLS = ["rtx_shade_rays", "rtx_shade_rays_device"]
 PIN = [("W1", -1.0), ("W2", -1.0), ("W3", -1.0), ("W4_Reference", -1.0), ("W4_Bunny", -1.0), ("W4_Bunny", 1.3),
        ("W4_Optional", -1.0)]
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return shade_ref.build(tmp_path_factory.mktemp("shade_ref"))
-
-
-_scenes = {}
-
-
-def _scene(name, t=-1.0):
-    if (name, t) not in _scenes:
-        hs = HostScene(name)
-        if t >= 0:
-            hs.update(t)
-        _scenes[(name, t)] = (hs, *hs.view())
-    return _scenes[(name, t)][1:]
 
 
 @pytest.mark.parametrize("name,t", PIN)
 def test_primary_rays_give_the_oracles_frame(checker, name, t):
     """The checker on a frame's primary rays equals oracle_bind.render bit for bit, pixels and rgb, in
     all four lighting modes with shadows on and off (7 scenes x 4 x 2 = 56 combinations)."""
-    s, cam = _scene(name, t)
+    s, cam = gs.view(name, t)
     rays = rayq_ref.primary(checker, cam, W, H)
     for mode in range(4):
         for shadows in (0, 1):
@@ -60,44 +39,27 @@ def test_primary_rays_give_the_oracles_frame(checker, name, t):
 def test_header_declares_and_abi_binds_the_shade_symbols(tmp_path):
     """The two entry points and the diag one are declared as the issue states them, exported and bound,
     and the ABI version stays 2."""
-    src = ['#include "rtx.h"', '#include "rtx_diag.h"', "int main(void) {",
-           "int (*f0)(rtx_ctx*, const rtx_ray*, uint32_t, const rtx_render_params*, uint32_t*, float*) = rtx_shade_rays;",
-           "int (*f1)(rtx_ctx*, const rtx_ray*, uint32_t, const rtx_render_params*, uint32_t*, float*) = "
-           "rtx_shade_rays_device;",
-           "int (*f2)(rtx_ctx*, const rtx_ray*, uint32_t, const rtx_render_params*, uint32_t*, float*, int, float*) = "
-           "rtx_time_shade_rays;",
-           "return !(f0 && f1 && f2 && RTX_ABI_VERSION == 2); }"]
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-I{INC}", str(tmp_path / "l.c"), "-o", str(tmp_path / "l"),
-                    f"-L{abi.LIB_DIR}", "-lrtx_hip", f"-Wl,-rpath,{abi.LIB_DIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    subprocess.run([str(tmp_path / "l")], check=True)
-    prod, diag = (INC / "rtx.h").read_text(), (INC / "rtx_diag.h").read_text()
+    shade = "int (*)(rtx_ctx*, const rtx_ray*, uint32_t, const rtx_render_params*, uint32_t*, float*)"
+    abi_surface.declared_exported_and_bound(tmp_path, {"rtx_shade_rays": shade, "rtx_shade_rays_device": shade}, {
+        "rtx_time_shade_rays":
+            "int (*)(rtx_ctx*, const rtx_ray*, uint32_t, const rtx_render_params*, uint32_t*, float*, int, float*)",
+    }, ["RTX_ABI_VERSION == 2"])
     lib = abi.load_hip()
     assert lib.rtx_abi_version() == 2
-    for n in SYMBOLS:
-        assert re.search(rf"^int {n}\(", prod, re.M), n
-    assert re.search(r"^int rtx_time_shade_rays\(", diag, re.M)
-    for n in SYMBOLS + ["rtx_time_shade_rays"]:
-        assert n in abi.HIP_SYMBOLS and getattr(lib, n).argtypes, n
     assert lib.rtx_shade_rays.argtypes[1]._type_ is abi.Ray and lib.rtx_shade_rays.argtypes[3]._type_ is abi.RenderParams
     assert lib.rtx_shade_rays.restype is C.c_int
 
 
 def test_the_cpp_mirror_compiles(tmp_path):
-    (tmp_path / "m.cpp").write_text(
-        '#include "rtx_renderer.hpp"\n'
-        "rtx::Renderer::ShadedRays (rtx::Renderer::*f0)(const std::vector<rtx_ray>&) = &rtx::Renderer::ShadeRays;\n"
-        "rtx::Renderer::ShadedRays (rtx::Renderer::*f1)(rtx_host_scene*, const std::vector<rtx_ray>&, bool) = "
-        "&rtx::Renderer::ShadeRays;\n"
-        "int main() { return !(f0 && f1); }\n")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", f"-I{INC}", str(tmp_path / "m.cpp")],
-                   check=True)
+    abi_surface.cpp_mirror_compiles(tmp_path, [
+        ("rtx::Renderer::ShadedRays (rtx::Renderer::*)(const std::vector<rtx_ray>&)", "ShadeRays"),
+        ("rtx::Renderer::ShadedRays (rtx::Renderer::*)(rtx_host_scene*, const std::vector<rtx_ray>&, bool)", "ShadeRays")])
 
 
 def _shares(checker, name, rays):
     """The shares of `rays` that hit, that have an occluded light and whose colour MaxToOne divides, in
     Combined with shadows on."""
-    s, _ = _scene(name)
+    s, _ = gs.view(name)
     px, rgb, flags = shade_ref.shade(checker, s, rays, shade_ref.params())
     share = {k: float(((flags & bit) != 0).mean()) for k, bit in
              (("hit", shade_ref.HIT), ("occluded", shade_ref.OCCLUDED), ("divided", shade_ref.DIVIDED))}
@@ -106,12 +68,12 @@ def _shares(checker, name, rays):
 
 
 def test_floors_aimed_bunny(checker):
-    sh, _, _ = _shares(checker, "W4_Bunny", rayq_rays.aimed(_scene("W4_Bunny")[0], SEED))
+    sh, _, _ = _shares(checker, "W4_Bunny", rayq_rays.aimed(gs.view("W4_Bunny")[0], SEED))
     assert sh["hit"] >= 0.5 and sh["occluded"] >= 0.3, sh
 
 
 def test_floors_aimed_optional(checker):
-    sh, _, _ = _shares(checker, "W4_Optional", rayq_rays.aimed(_scene("W4_Optional")[0], SEED))
+    sh, _, _ = _shares(checker, "W4_Optional", rayq_rays.aimed(gs.view("W4_Optional")[0], SEED))
     assert sh["occluded"] >= 0.5, sh
 
 
@@ -121,17 +83,17 @@ def test_floors_scatter_w3(checker):
 
 
 def test_floors_max_to_one_primary_w2(checker):
-    sh, _, _ = _shares(checker, "W2", rayq_ref.primary(checker, _scene("W2")[1], W, H))
+    sh, _, _ = _shares(checker, "W2", rayq_ref.primary(checker, gs.view("W2")[1], W, H))
     assert sh["divided"] >= 0.1, sh
 
 
 def test_floors_max_to_one_aimed_reference(checker):
-    sh, _, _ = _shares(checker, "W4_Reference", rayq_rays.aimed(_scene("W4_Reference")[0], SEED))
+    sh, _, _ = _shares(checker, "W4_Reference", rayq_rays.aimed(gs.view("W4_Reference")[0], SEED))
     assert sh["divided"] >= 0.4, sh
 
 
 def test_a_scene_without_lights_is_black(checker):
-    s, cam = _scene("W1")
+    s, cam = gs.view("W1")
     assert s.n_lights == 0
     for rays in (rayq_ref.primary(checker, cam, W, H), rayq_rays.scatter(SEED), rayq_rays.nonfinite(s, SEED)):
         for mode in range(4):

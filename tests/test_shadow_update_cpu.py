@@ -4,46 +4,27 @@ compiles; the command-line program refuses a malformed --move-light before any d
 feature rests on, on the checker alone: bit l of the plane depends only on the hit record and on light l's origin
 and type, so the planes of two scenes agree in every bit whose light kept its key."""
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_surface
 import relight_ref
 import shadow_update_scenes as sus
+from checkers import checker  # noqa: F401
 from gp1_raytracer_2223_amd import abi
 from gp1_raytracer_2223_amd.scene import HostScene
 
-ROOT = Path(__file__).resolve().parents[1]
-INC = ROOT / "include"
-EXE = ROOT / "gp1_raytracer_2223_amd" / "lib" / "rtx_render"
 W, H = 37, 23
-SYMBOLS = ["rtx_update_shadows_async", "rtx_refresh_shadows_async"]
-DIAG = ["rtx_time_shadows_update"]
 
 
 def test_header_declares_and_abi_binds_the_symbols(tmp_path):
-    src = ['#include "rtx.h"', '#include "rtx_diag.h"', "int main(void) {",
-           "int (*f0)(rtx_ctx*, uint32_t) = rtx_update_shadows_async;",
-           "int (*f1)(rtx_ctx*, uint32_t*) = rtx_refresh_shadows_async;",
-           "int (*f2)(rtx_ctx*, uint32_t, int, float*) = rtx_time_shadows_update;",
-           "return !(f0 && f1 && f2 && RTX_ABI_VERSION == 2); }"]
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-I{INC}", str(tmp_path / "l.c"), "-o", str(tmp_path / "l"),
-                    f"-L{abi.LIB_DIR}", "-lrtx_hip", f"-Wl,-rpath,{abi.LIB_DIR}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    subprocess.run([str(tmp_path / "l")], check=True)
-    prod, diag = (INC / "rtx.h").read_text(), (INC / "rtx_diag.h").read_text()
+    abi_surface.declared_exported_and_bound(tmp_path, {
+        "rtx_update_shadows_async": "int (*)(rtx_ctx*, uint32_t)",
+        "rtx_refresh_shadows_async": "int (*)(rtx_ctx*, uint32_t*)",
+    }, {"rtx_time_shadows_update": "int (*)(rtx_ctx*, uint32_t, int, float*)"}, ["RTX_ABI_VERSION == 2"])
     lib = abi.load_hip()
     assert lib.rtx_abi_version() == 2
-    for n in SYMBOLS:
-        assert re.search(rf"^int {n}\(", prod, re.M), n
-    for n in DIAG:
-        assert re.search(rf"^int {n}\(", diag, re.M) and n not in prod, n
-    for n in SYMBOLS + DIAG:
-        assert n in abi.HIP_SYMBOLS and getattr(lib, n).argtypes, n
-        assert getattr(lib, n).restype is C.c_int, n
     assert lib.rtx_update_shadows_async.argtypes[1:] == [C.c_uint32]
     assert lib.rtx_refresh_shadows_async.argtypes[1]._type_ is C.c_uint32
     assert lib.rtx_time_shadows_update.argtypes[1:3] == [C.c_uint32, C.c_int]
@@ -62,13 +43,8 @@ def test_null_context_is_invalid_without_a_device():
 
 
 def test_the_cpp_mirror_compiles(tmp_path):
-    (tmp_path / "m.cpp").write_text(
-        '#include "rtx_renderer.hpp"\n'
-        "std::vector<uint32_t> (rtx::Renderer::*f0)(uint32_t) = &rtx::Renderer::UpdateShadows;\n"
-        "std::vector<uint32_t> (rtx::Renderer::*f1)(uint32_t*) = &rtx::Renderer::RefreshShadows;\n"
-        "int main() { return !(f0 && f1); }\n")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", f"-I{INC}", str(tmp_path / "m.cpp")],
-                   check=True)
+    abi_surface.cpp_mirror_compiles(tmp_path, [("std::vector<uint32_t> (rtx::Renderer::*)(uint32_t)", "UpdateShadows"),
+                                               ("std::vector<uint32_t> (rtx::Renderer::*)(uint32_t*)", "RefreshShadows")])
 
 
 @pytest.mark.parametrize("arg", [None, "", "1", "1,2,3", "1,2,3,4,5", "x,1,2,3", "1,a,2,3", "-1,0,0,0", "1,2,3,4x",
@@ -78,15 +54,10 @@ def test_the_cpp_mirror_compiles(tmp_path):
 @pytest.mark.parametrize("relight", [False, True])
 def test_cli_refuses_a_bad_move_light_before_device_work(tmp_path, arg, relight):
     """(W4_Bunny has three lights: 3 and 99 name none.)"""
-    assert EXE.exists(), "lib/rtx_render is not built"
     args = ["--move-light"] + ([arg] if arg is not None else [])
     if relight:
         args = ["--relight", "--aov", "planes"] + args
-    r = subprocess.run([str(EXE), "W4_Bunny", "64", "48", "--out", "o.bmp"] + args, capture_output=True, text=True,
-                       cwd=tmp_path, timeout=60)
-    assert r.returncode != 0, args
-    assert "--move-light" in r.stderr, (args, r.stderr)
-    assert list(tmp_path.iterdir()) == [], args
+    abi_surface.cli_refuses(tmp_path, "--move-light", args)
 
 
 def test_host_light_set_origin():
@@ -104,11 +75,6 @@ def test_host_light_set_origin():
 
 
 # ---- bit l depends on light l alone ----------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
-
 
 # The words that differ per bit, as the checker counted them when the scenes were chosen: {variant: {bit: count}}
 COUNTS = {

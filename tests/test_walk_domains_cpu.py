@@ -12,14 +12,10 @@ import aov_ref
 import pack_cases as PC
 import rayq_ref
 import walk_domains as WD
+from checkers import checker  # noqa: F401
 from test_pack_cpu import build_harness, parse, run_harness
 
 F32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return rayq_ref.build(tmp_path_factory.mktemp("rayq_ref"))
 
 
 @pytest.fixture(scope="module")
@@ -188,14 +184,8 @@ FRAMES = [("giant", "none"), ("giant", "back"), ("over", "none"), ("sliver", "no
           ("needle", "back")]
 
 
-@pytest.fixture(scope="module")
-def relight_checker(tmp_path_factory):
-    import relight_ref
-    return relight_ref.build(tmp_path_factory.mktemp("relight_ref"))
-
-
 @pytest.mark.parametrize("name,cull", FRAMES)
-def test_the_frames_are_not_flat(relight_checker, folder, name, cull):
+def test_the_frames_are_not_flat(checker, folder, name, cull):
     """The 64 x 48 frame of a scene's camera hits triangles and misses them, has at least 3 distinct
     colour words in both modes, and its point light is occluded in some hit pixels and not in others.
     `needle`'s frame shows a plane, and the occluder of its far light is the triangle whose t is NaN: with
@@ -203,7 +193,7 @@ def test_the_frames_are_not_flat(relight_checker, folder, name, cull):
     import oracle_bind
     import relight_ref
     from gp1_raytracer_2223_amd import abi
-    lib = relight_checker
+    lib = checker
     if name == "needle":
         hs, s, cam = WD.needle_scene(cull, folder, True)
         kind = aov_ref.kind(aov_ref.planes(lib, s, cam, 64, 48)["primitive"])
