@@ -81,4 +81,73 @@ __device__ __forceinline__ void div3_exact(float& x, float& y, float& z, float m
     }
 }
 
+// RN(sqrt(x)) for x == 0, every x >= 2^-96 and +inf: v_sqrt_f32 (1 ulp) plus one residual
+// correction against its two neighbours, without the denormal scaling and class handling of
+// the correctly rounded sqrtf (7 VALU less).  Compared with sqrtf over all 2^31 non-negative
+// inputs by tools/validate_sqrt.hip -DFAST=1 (profiles/r01/validate_sqrt_fast.txt,
+// profiles/fixedpath/validate_sqrt_fast.txt): it differs only below 2^-96.  It has no domain
+// test of its own: the caller's covers it (norm_ray3).
+__device__ __forceinline__ float sqrt_rn(float x) {
+    float s = __builtin_amdgcn_sqrtf(x);
+    const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
+    const float rm = fmaf(-sm, s, x), rp = fmaf(-sp, s, x);
+    s = (rm <= 0.f) ? sm : s;
+    s = (rp > 0.f) ? sp : s;
+    return s;
+}
+
+// A ray direction in one piece: m = RN(sqrt(x*x + y*y + z*z)), (x, y, z) = RN((x, y, z) / m)
+// (Vector3::Normalize) and r = RN(1 / (x, y, z)) of the normalised direction (dae::Ray's
+// inversedDir), with ONE domain test and ONE wave-uniform fallback for the three steps, which
+// sqrtf, div3_exact and rcp3_exact each guarded with a divergent region of their own.  The fast
+// forms (sqrt_rn, div_rn, rcp_rn) are computed in every lane; a wave with a lane outside the
+// domain recomputes that lane with the IEEE forms, which are right for any operand.
+// The test, with s = x*x + y*y + z*z as computed, lo = min |component| before and dlo after
+// the normalisation:   2^-96 <= s <= 2^120   and   lo >= 2^-60   and   dlo >= 2^-60.
+//   * sqrt_rn: s >= 2^-96 is its domain (s is a sum of squares: never negative).
+//   * div3_exact needs fast_rcp_ok(m) and lo >= 2^-60.  The square root is monotone and
+//     sqrt(2^-96) = 2^-48, sqrt(2^120) = 2^60 are exact, so m lies in [2^-48, 2^60].  (Each
+//     numerator is at most 2^60 too: a sum of non-negative terms rounds to no less than any of
+//     them, and the square of the next float above 2^60 already rounds above 2^120.)
+//   * rcp3_exact needs dlo >= 2^-60 and |x| + |y| + |z| <= 2^60 after the normalisation.  In the two
+//     domains above every quotient is the correctly rounded one of |x| / m with m >= max |component|
+//     (1 - 2u), so each is at most 1 + 3u and their sum below 4: the upper bound holds.
+//   * a NaN component makes s NaN and an infinite one makes it inf: both fail the test on s (v_min3
+//     would drop a NaN, but lo and dlo are read only once s has passed).
+// Returns rcp3_exact's ballot: the lanes whose normalised direction is outside its domain.  In a
+// wave that skips the fallback every lane is inside (the test implies it), so the ballot is 0; the
+// fallback evaluates rcp3_exact's own condition on the final direction.
+// ONE = false: the three guarded steps as they were (a kernel that the merged form costs a wave of occupancy).
+template <bool ONE = true>
+__device__ __forceinline__ unsigned long long norm_ray3(float& x, float& y, float& z, float& m, float& rx, float& ry,
+                                                        float& rz) {
+    if constexpr (!ONE) {
+        m = sqrtf(x * x + y * y + z * z);
+        div3_exact(x, y, z, m);
+        return rcp3_exact(x, y, z, rx, ry, rz);
+    }
+    const float x0 = x, y0 = y, z0 = z;
+    const float s = x0 * x0 + y0 * y0 + z0 * z0;
+    m = sqrt_rn(s);
+    const float r = rcp_rn(m);
+    x = div_rn(x0, m, r); y = div_rn(y0, m, r); z = div_rn(z0, m, r);
+    rx = rcp_rn(x); ry = rcp_rn(y); rz = rcp_rn(z);
+    const float lo = fminf(fminf(fabsf(x0), fabsf(y0)), fabsf(z0));
+    const float dlo = fminf(fminf(fabsf(x), fabsf(y)), fabsf(z));
+    // (2^-96 <= s <= 2^120 on the bits, one unsigned compare: zero, a denormal, inf and NaN all fall outside)
+    const bool in = (__float_as_uint(s) - 0x0f800000u <= 0x7b800000u - 0x0f800000u) && lo >= 0x1p-60f && dlo >= 0x1p-60f;
+    unsigned long long slow = 0;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!in) != 0, 0)) {   // wave-uniform
+        if (!in) {
+            m = sqrtf(s);
+            x = x0 / m; y = y0 / m; z = z0 / m;
+            rx = 1.f / x; ry = 1.f / y; rz = 1.f / z;
+        }
+        const float l3 = fminf(fminf(fabsf(x), fabsf(y)), fabsf(z));
+        const float sum = (fabsf(x) + fabsf(y)) + fabsf(z);
+        slow = __builtin_amdgcn_ballot_w64(!(l3 >= 0x1p-60f && sum <= 0x1p60f));
+    }
+    return slow;
+}
+
 }  // namespace rtxd

@@ -132,6 +132,11 @@ __device__ __forceinline__ Ray make_ray(float ox, float oy, float oz, float dx, 
     r.tmin = tmin; r.tmax = tmax;
     return r;
 }
+// ... for a direction whose inverse the caller already has (RTX_DIR_NORMALISE)
+__device__ __forceinline__ Ray make_ray(float ox, float oy, float oz, float dx, float dy, float dz, float ix, float iy,
+                                        float iz, float tmin, float tmax) {
+    return {ox, oy, oz, dx, dy, dz, ix, iy, iz, tmin, tmax};
+}
 
 // HitTest_Sphere (Utils.h:52-66) in two steps, so that the square root (16 VALU when
 // correctly rounded) runs only when some lane's ray passes within the radius:
@@ -204,7 +209,7 @@ __device__ __forceinline__ bool finite3(float x, float y, float z) {
 __device__ __forceinline__ unsigned long long plane_cand(float num, float den, float tmax) {
     const int same = (__float_as_int(num) ^ __float_as_int(den)) >= 0;
     const int beyond = fmaf(fabsf(den), tmax, -fabsf(num)) < 0.f;
-    return ballot(same & !beyond);
+    return ballot(same) & ballot(!beyond);   // (a ballot per compare: one of a conjunction goes through a VGPR boolean)
 }
 
 // HitTest_Triangle (Utils.h:109-184), Möller–Trumbore with the reference's cull rules
@@ -929,12 +934,19 @@ __device__ __forceinline__ uint32_t q8(float c) {
 // functions: as __forceinline__ functions they left the values alone but moved the register allocation of
 // 128 of the render kernel's 162 instantiations (tools/codeobj_diff.py), and as macros render_tile is the
 // text it was.  They name the variables of the scope they expand in.
+// RTX_DIR_NORMALISE: the magnitude M of the direction X, Y, Z, the direction normalised by it, and the ray
+// constructor's inverse direction IX, IY, IZ with its slow ballot SLOW (make_ray) for the expansions that cast
+// the ray; the others leave them unused.
+#define RTX_DIR_NORMALISE(ONE, X, Y, Z, M, IX, IY, IZ, SLOW)                                      \
+    float M, IX, IY, IZ;                                                                          \
+    const unsigned long long SLOW = norm_ray3<ONE>(X, Y, Z, M, IX, IY, IZ);                       \
+    (void)IX; (void)IY; (void)IZ; (void)SLOW
 // RTX_PRIMARY_DIR: the primary ray's direction dx, dy, dz, normalised from the magnitude dm
 // (Renderer.cpp:104-114; Matrix::TransformVector Matrix.cpp:35-42).
 // (px + 0.5f) / W and (2 * (py + 0.5f)) / H as Markstein quotients with the exact
 // reciprocals RN(1/W), RN(1/H) (divided on the host, FrameArgs): numerators in [0.5, 2^17], divisors in
 // [1, 2^16] lie inside div_rn's domain (rtx_fastdiv.h), so each is the IEEE quotient.
-#define RTX_PRIMARY_DIR(F, V)                                                                     \
+#define RTX_PRIMARY_DIR(F, V, ONE)                                                                \
     const int W = static_cast<int>(F.width), H = static_cast<int>(F.height);                      \
     const float fW = static_cast<float>(W), fH = static_cast<float>(H);                           \
     const float cx = (2.f * div_rn(px + 0.5f, fW, F.inv_width) - 1) * F.aspect * V.fov;           \
@@ -942,15 +954,13 @@ __device__ __forceinline__ uint32_t q8(float c) {
     float dx = V.right[0] * cx + V.up[0] * cy + V.forward[0] * 1.f;                               \
     float dy = V.right[1] * cx + V.up[1] * cy + V.forward[1] * 1.f;                               \
     float dz = V.right[2] * cx + V.up[2] * cy + V.forward[2] * 1.f;                               \
-    const float dm = sqrtf(dx * dx + dy * dy + dz * dz);                                          \
-    div3_exact(dx, dy, dz, dm) /* dx /= dm; ... (Vector3::Normalize) */
+    RTX_DIR_NORMALISE(ONE, dx, dy, dz, dm, dix, diy, diz, dslow) /* dx /= dm; ... (Vector3::Normalize) */
 // RTX_LIGHT_DIR: LightUtils::GetDirectionToLight (Utils.h:341-353) from originOffset: lx, ly, lz normalised
 // from the magnitude mag (the shadow ray's tmax), for the light record L0 of type ltype.
-#define RTX_LIGHT_DIR()                                                                           \
+#define RTX_LIGHT_DIR(ONE)                                                                        \
     const bool known = (ltype == RTX_LIGHT_POINT || ltype == RTX_LIGHT_DIRECTIONAL);              \
     float lx = known ? L0.x - oox : 0.f, ly = known ? L0.y - ooy : 0.f, lz = known ? L0.z - ooz : 0.f; \
-    const float mag = sqrtf(lx * lx + ly * ly + lz * lz);                                         \
-    div3_exact(lx, ly, lz, mag)
+    RTX_DIR_NORMALISE(ONE, lx, ly, lz, mag, lix, liy, liz, lslow)
 // RTX_LIGHT_TERM: one unoccluded light's term of lighting mode MODE (Renderer.cpp:143-175) added to fr, fg,
 // fb; KINDS and COUNT are shade's.
 #define RTX_LIGHT_TERM(MODE, KINDS, COUNT)                                                        \
@@ -1062,6 +1072,9 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     constexpr bool kRoom = (SPEC & kSpecRoomPlanes) != 0 && (SPEC & kSpecFivePlanes) != 0;
     constexpr bool kCullBack = (SPEC & kSpecCullBack) != 0 && !COUNT;
     constexpr bool kStored = PHASE == 8 || PHASE == 9;   // the hit record is a stored hit pass's (the planes)
+    // the rays' merged domain test (norm_ray3), but for the generic shadow pass without the cull: its two more
+    // SGPRs are the kernel's 101st and 102nd, and it would run 7 waves per SIMD for 8
+    constexpr bool kDomOne = RTX_FIX_DOMAIN && !(PHASE == 9 && SPEC == 0 && !CULLK);
 #if RTX_STAMPS
     // diagnostic build only: per-wave {start, end, hw_id} in the counters buffer
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
@@ -1094,9 +1107,9 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
     if (COUNT && valid) cnt.c[kPixels] = 1;
 
     // ---- primary ray
-    RTX_PRIMARY_DIR(F, V);
-    unsigned long long vslow;
-    const Ray vr = make_ray(V.origin[0], V.origin[1], V.origin[2], dx, dy, dz, 0.0001f, FLT_MAX, vslow);
+    RTX_PRIMARY_DIR(F, V, kDomOne);
+    const unsigned long long vslow = dslow;
+    const Ray vr = make_ray(V.origin[0], V.origin[1], V.origin[2], dx, dy, dz, dix, diy, diz, 0.0001f, FLT_MAX);
     const unsigned long long active = ballot(valid);
     // FAST: every active lane's inverse direction finite and non-zero (make_ray's domain)
     const bool fast = (active & vslow) == 0 && S.tri_fast;
@@ -1141,6 +1154,34 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         // the view's record through a readfirstlane'd index: scalar loads (the view index
         // itself stays a VGPR value; making it uniform everywhere measured slower)
         const ViewCam& VU = F.cam[uni(view)];
+        const auto room_hit = [&](float t, int k) {
+            const bool h = valid & (t >= vr.tmin) & (t < vr.tmax);
+            sc_t = h ? t : sc_t;
+            const bool b = h & (t < best_t);
+            best_t = b ? t : best_t;
+            best_kind = b ? 2u : best_kind;
+            best_idx = b ? static_cast<uint32_t>(k * 32) : best_idx;
+        };
+#if RTX_FIX_ROOM
+        // the five numerators and room_fast lie side by side in the record: read together ahead of the one
+        // branch, they are one scalar fetch and one wait for the wave, not one of each per plane
+        const float ra[5] = {VU.room_a[0], VU.room_a[1], VU.room_a[2], VU.room_a[3], VU.room_a[4]};
+        if (fast && VU.room_fast) {
+            for_room_planes([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                constexpr int A = kRoomAxes[k];
+                room_hit(div_rn(ra[k], room_d<A>(vr), room_inv<A>(vr)), k);
+            });
+        } else {
+            for_room_planes([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                constexpr int A = kRoomAxes[k];
+                float4 p0, p1;
+                ldcb32(S.planes, k * 32u, p0, p1);
+                room_hit(room_a<A>(p0, vr) / room_d<A>(vr), k);
+            });
+        }
+#else
         const bool mk = fast && VU.room_fast;
         for_room_planes([&](auto kc) {
             constexpr int k = decltype(kc)::value;
@@ -1153,13 +1194,9 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
                 ldcb32(S.planes, k * 32u, p0, p1);
                 t = room_a<A>(p0, vr) / room_d<A>(vr);
             }
-            const bool h = valid & (t >= vr.tmin) & (t < vr.tmax);
-            sc_t = h ? t : sc_t;
-            const bool b = h & (t < best_t);
-            best_t = b ? t : best_t;
-            best_kind = b ? 2u : best_kind;
-            best_idx = b ? static_cast<uint32_t>(k * 32) : best_idx;
+            room_hit(t, k);
         });
+#endif
     }
     for (uint32_t i = 0; i < ((RTX_ABL_PPLANE || room_p || PHASE == 5 || PHASE == 6 || kStored) ? 0u : n_pl * 32u);
          i += 32u) {
@@ -1275,7 +1312,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
         if (did) { hx = vr.ox + vr.dx * best_t; hy = vr.oy + vr.dy * best_t; hz = vr.oz + vr.dz * best_t; }
     } else if (did) {
         hx = vr.ox + vr.dx * best_t; hy = vr.oy + vr.dy * best_t; hz = vr.oz + vr.dz * best_t;
-        if (best_kind == 1) {
+        if ((!RTX_FIX_HIT || !kNoSph) && best_kind == 1) {   // (no sphere arm in a variant without spheres)
             const float4 s = ldcb16(S.spheres, best_idx);
             nx = hx - s.x; ny = hy - s.y; nz = hz - s.z;
             const float m = sqrtf(nx * nx + ny * ny + nz * nz);   // closestHit.normal.Normalize()
@@ -1386,7 +1423,7 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
             float4 L0, L1;
             ldcb32(S.lights, opaque(li * 32u), L0, L1);
             const int ltype = kPoint ? RTX_LIGHT_POINT : __float_as_int(L0.w);
-            RTX_LIGHT_DIR();
+            RTX_LIGHT_DIR(kDomOne);
             bool occ = false;
             if (lm_shade && f_shadows) {   // PHASE 6: published by the previous launch
                 const unsigned long long mk = F.lm_mask[static_cast<size_t>(tile) * F.lm_lights + li];
@@ -1394,8 +1431,8 @@ __device__ __forceinline__ void render_tile(const DevScene& S, const FrameArgs& 
             } else if (f_shadows) {
                 // Scene::DoesHit (Scene.cpp:68-96) on Ray{originOffset, l, 1e-4, |l|}; `live` =
                 // lanes still without an occluder (first hit wins, order irrelevant for a bool)
-                unsigned long long sslow;
-                const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, 0.0001f, mag, sslow);
+                const unsigned long long sslow = lslow;
+                const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, lix, liy, liz, 0.0001f, mag);
                 unsigned long long live = hitmask;
                 const bool sfast = (hitmask & sslow) == 0 && S.tri_fast;
                 const int soct =
@@ -1919,11 +1956,11 @@ __device__ __forceinline__ void light_loop(const DevScene& S, const Ray& r, cons
             float4 L0, L1;
             ldcb32(S.lights, opaque(li * 32u), L0, L1);
             const int ltype = __float_as_int(L0.w);
-            RTX_LIGHT_DIR();
+            RTX_LIGHT_DIR(bool(RTX_FIX_DOMAIN));
             bool occ = false;
             if (shadows) {
-                unsigned long long sslow;
-                const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, 0.0001f, mag, sslow);
+                const unsigned long long sslow = lslow;
+                const Ray sr = make_ray(oox, ooy, ooz, lx, ly, lz, lix, liy, liz, 0.0001f, mag);
                 const WaveWalk sw = wave_walk(S, sr, sslow, hitmask);
                 const unsigned long long live = any_hit(S, sr, sw, hitmask, lane, stk, cnt);
                 occ = did & !((live >> lane) & 1ull);
@@ -2071,7 +2108,7 @@ __global__ void __launch_bounds__(kBlockThreads, (DEEP && !HSTK) ? 2 : RTX_MIN_W
         const int py = static_cast<int>(((xy >> 16) << n) | sy);
 
         // ---- primary ray (Renderer.cpp:104-114), as render_tile makes it for the sample frame
-        RTX_PRIMARY_DIR(A, A);
+        RTX_PRIMARY_DIR(A, A, bool(RTX_FIX_DOMAIN));
         unsigned long long slow;
         // (a tail lane keeps the shade kernel's harmless ray; it is in no mask)
         const Ray r = make_ray(valid ? A.origin[0] : 0.f, valid ? A.origin[1] : 0.f, valid ? A.origin[2] : 0.f,
@@ -2145,7 +2182,7 @@ __global__ void __launch_bounds__(kRelightThreads) rtx_relight_kernel(const DevS
     const ViewCam& V = A.cam[view];
     const int px = static_cast<int>(seg * 64u + lane), py = static_cast<int>(row);
     const bool valid = px < static_cast<int>(A.width);
-    RTX_PRIMARY_DIR(A, V);
+    RTX_PRIMARY_DIR(A, V, bool(RTX_FIX_DOMAIN));
     (void)dm;
 
     // ---- closestHit from the planes, as PHASE 8 reads it
@@ -2176,7 +2213,7 @@ __global__ void __launch_bounds__(kRelightThreads) rtx_relight_kernel(const DevS
             float4 L0, L1;
             ldcb32(S.lights, opaque(li * 32u), L0, L1);
             const int ltype = __float_as_int(L0.w);
-            RTX_LIGHT_DIR();
+            RTX_LIGHT_DIR(bool(RTX_FIX_DOMAIN));
             (void)mag;   // (the shadow ray's tmax: no ray here)
             if (!did) continue;
             // (with shadows on the host has checked the plane's light count against the scene's, at most 32)
@@ -2240,7 +2277,7 @@ rtx_relight_resolve_kernel(const DevScene S, const RelightArgs A) {
 #pragma unroll 1
     for (uint32_t sy = 0; sy < K; ++sy) {
         const int py = static_cast<int>(static_cast<uint32_t>(orow) * K + sy);
-        RTX_PRIMARY_DIR(A, V);
+        RTX_PRIMARY_DIR(A, V, bool(RTX_FIX_DOMAIN));
         (void)dm;
 
         // ---- closestHit from the planes, as PHASE 8 reads it
@@ -2271,7 +2308,7 @@ rtx_relight_resolve_kernel(const DevScene S, const RelightArgs A) {
                 float4 L0, L1;
                 ldcb32(S.lights, opaque(li * 32u), L0, L1);
                 const int ltype = __float_as_int(L0.w);
-                RTX_LIGHT_DIR();
+                RTX_LIGHT_DIR(bool(RTX_FIX_DOMAIN));
                 (void)mag;   // (the shadow ray's tmax: no ray here)
                 if (!did) continue;
                 if (A.shadows && li < 32u && ((bits >> li) & 1u)) {

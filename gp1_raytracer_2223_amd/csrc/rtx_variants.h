@@ -61,6 +61,26 @@
 #define RTX_P1_SHARED_T 1
 #endif
 
+// The fixed path of render_tile (everything a wave runs outside the walks), one switch per step so that
+// each has an A/B of its own (1: the step, 0: the form before it).  Same values either way.
+// profiles/fixedpath/INDEX.md has the per-step kernel times and instruction counts; the steps that lost
+// their A/B are not in the kernel.
+// RTX_FIX_DOMAIN: a ray's square root, normalisation and reciprocals under one domain test and one
+// wave-uniform fallback (norm_ray3, rtx_fastdiv.h) instead of sqrtf + div3_exact + rcp3_exact.
+#ifndef RTX_FIX_DOMAIN
+#define RTX_FIX_DOMAIN 1
+#endif
+// RTX_FIX_ROOM: the camera's five room-plane numerators fetched together, one branch around the planes.
+#ifndef RTX_FIX_ROOM
+#define RTX_FIX_ROOM 1
+#endif
+// RTX_FIX_HIT: the hit record without the sphere arm where the variant has no spheres.  0, product: measured
+// once, W4_Bunny another -1.5 % (-16 SALU per wave) but Synthetic100k above the parent's spread
+// (profiles/fixedpath/ab_kernel.txt); to be repeated before it is turned on.
+#ifndef RTX_FIX_HIT
+#define RTX_FIX_HIT 0
+#endif
+
 // ---- diagnostics (never a product build) -------------------------------------------------
 // RTX_STAMPS=1: per-wave {start, end, hw id, node-pair steps, triangle steps, lane-work}
 // stamps, read back by rtx_debug_stamps / tools/stamps.py.  RTX_STAMPS_LEAN: the stamps

@@ -4,11 +4,13 @@
 // correctly rounded on a class, the render kernel may use it there (rtx_fastdiv.h).
 // Build+run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-//         tools/validate_sqrt.hip -o /tmp/vs && /tmp/vs
+//         -Igp1_raytracer_2223_amd/csrc [-DFAST=1] tools/validate_sqrt.hip -o /tmp/vs && /tmp/vs
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
+
+#include "rtx_fastdiv.h"
 
 #ifndef FAST
 #define FAST 0   // 1: validate sqrt_fast instead of the bare v_sqrt_f32
@@ -24,16 +26,9 @@ __device__ int cls(uint32_t u) {
     return 5;
 }
 
-// The render kernel's fast path (rtx_fastdiv.h sqrt_rn): v_sqrt_f32 plus one residual
-// correction, no scaling, valid where claimed below.
-__device__ float sqrt_fast(float x) {
-    float s = __builtin_amdgcn_sqrtf(x);
-    const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
-    const float rm = fmaf(-sm, s, x), rp = fmaf(-sp, s, x);
-    s = (rm <= 0.f) ? sm : s;
-    s = (rp > 0.f) ? sp : s;
-    return s;
-}
+// The render kernel's fast path: rtx_fastdiv.h's sqrt_rn itself (v_sqrt_f32 plus one residual correction,
+// no scaling), valid where claimed below.  Build with -Igp1_raytracer_2223_amd/csrc -DFAST=1.
+__device__ float sqrt_fast(float x) { return rtxd::sqrt_rn(x); }
 
 __global__ void k(unsigned long long* bad, unsigned long long* tested, unsigned* first) {
     const uint64_t tid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
