@@ -39,6 +39,21 @@ def ctx():
     c.close()
 
 
+def ctx_env(**env):
+    """A context created with the knobs of `env` set in the environment (they are read once, at creation)."""
+    from gp1_raytracer_2223_amd.renderer import DeviceContext
+    saved = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return DeviceContext(DEV)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 _views = {}
 
 

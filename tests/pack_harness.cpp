@@ -2,7 +2,7 @@
 // tests/test_pack_cpu.py, which compiles this file and csrc/rtx_pack.cpp with the address and
 // undefined-behaviour sanitizers and links librtx_host.so for the scenes.  One command per input line:
 //   scene LABEL NAME ASSET_DIR [t=TIME] [parts=N] [nocull=1] [no_octant=1] [room_skip_off=1]
-//                              [refine=I,J] [reserve=1] [uploads=N]
+//                              [refine=I,J] [reserve=1] [uploads=N] [min_sa=RATIO]
 //       pack NAME (a catalogue scene, file:PATH, chain:T, lights:N or tris:A.B,...), emit it with all 8 octant copies
 //       on the host, check the image's structure, print one line of hashes and facts per upload
 //   refuse CASE     pack one of the minimal hand-built refusals, print the code and the message
@@ -158,6 +158,7 @@ PackOptions options(const Loaded& L, const std::map<std::string, std::string>& k
     if (kv.count("parts")) o.split_parts = static_cast<uint32_t>(std::atoi(kv.at("parts").c_str()));
     o.no_octant = kv.count("no_octant");
     o.room_skip_off = kv.count("room_skip_off");
+    if (kv.count("min_sa")) o.cull_min_sa = std::strtod(kv.at("min_sa").c_str(), nullptr);
     if (kv.count("refine")) {
         std::stringstream ss(kv.at("refine"));
         for (std::string tok; std::getline(ss, tok, ',');) o.part_refine.push_back(std::atoi(tok.c_str()));

@@ -7,7 +7,9 @@
 2. The bound holds on adversarial searches: tools/mt_graze_search.c aims millions of rays at
    points beside Synthetic100k-like slivers, nearly inside their planes, in both the camera form
    (origin anchor) and the shadow form (light anchor), and fails on any accepted ray whose exact
-   distance to the triangle exceeds rtx_cull.h's margin.
+   distance to the triangle exceeds rtx_cull.h's margin.  The same search then runs away from that shape
+   and place: scaled by 2^20 and 2^28, translated by 1e3 and 1e5 (where the vertices themselves are coarse),
+   on generic triangles and on right triangles with leg ratios down to 2^-20.
 """
 import subprocess
 from pathlib import Path
@@ -82,12 +84,43 @@ def search(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("size", [1.0, 4.0])
-def test_margin_bound_holds_on_grazing_search(search, size):
-    r = subprocess.run([str(search), "1500000", str(size), "3"], capture_output=True, text=True, timeout=300)
+def _accepted(out):
+    """(camera rays accepted, shadow rays accepted) of the search's report."""
+    cam = sum(int(line.split("accepted ")[1].split(",")[0]) for line in out.splitlines() if line.startswith("X "))
+    (shadow,) = [int(line.split("accepted ")[1].split(",")[0]) for line in out.splitlines() if line.startswith("shadow:")]
+    return cam, shadow
+
+
+# (trials, size, tilt decades, global scale, translation, shape); shape 0: the Synthetic100k-like sliver, 1: generic
+# triangles with edges of about `size`, 2: right triangles with leg ratios 2^0 .. 2^-20.  "1.0" and "4.0" (the size: the ids they always had) are the search
+# as it always ran (the tool's defaults for the last three arguments).  A scale of 2^-10 is absent on purpose: the
+# reference's |a| < FLT_EPSILON guard then rejects every ray, and a search that accepts nothing tests nothing.
+SEARCHES = {
+    "1.0": (1500000, 1.0, 3, 1.0, 0.0, 0),
+    "4.0": (1500000, 4.0, 3, 1.0, 0.0, 0),
+    "scale_2p20": (300000, 1.0, 3, 2.0 ** 20, 0.0, 0),
+    "scale_2p28_generic": (300000, 1.0, 3, 2.0 ** 28, 0.0, 1),
+    "offset_1e5": (300000, 1.0, 3, 1.0, 1e5, 0),
+    "offset_1e5_size4_generic": (300000, 4.0, 3, 1.0, 1e5, 1),
+    "offset_1e3_generic_tilt5": (300000, 1.0, 5, 1.0, 1e3, 1),
+    "right_triangles": (300000, 1.0, 3, 1.0, 0.0, 2),
+    "right_triangles_size4": (300000, 4.0, 3, 1.0, 0.0, 2),
+}
+
+
+@pytest.mark.parametrize("what", sorted(SEARCHES))
+def test_margin_bound_holds_on_grazing_search(search, what):
+    """No accepted ray's line passes farther from its triangle than rtx_cull.h's margin, |X - P| <= W and
+    |t~ - t*| <= dt hold for every accepted ray, and the configuration accepts rays in both forms."""
+    trials, size, tilt, scale, offset, shape = SEARCHES[what]
+    r = subprocess.run([str(search), str(trials), str(size), str(tilt), repr(scale), repr(offset), str(shape)],
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:]
     out = r.stdout
-    assert "violations 0" in out
-    # the search is meaningful: it finds accepted rays far (> 1e-3) from their triangle
-    far = sum(int(line.split("1e-3: ")[1].split(";")[0]) for line in out.splitlines() if "1e-3: " in line)
-    assert far > 0, out
+    assert out.count("violations 0") == 2 and "VIOLATION" not in out, out[-2000:]
+    cam, shadow = _accepted(out)
+    assert cam > 0 and shadow > 0, out
+    if what in ("1.0", "4.0"):
+        # the search is meaningful: it finds accepted rays far (> 1e-3) from their triangle
+        far = sum(int(line.split("1e-3: ")[1].split(";")[0]) for line in out.splitlines() if "1e-3: " in line)
+        assert far > 0, out

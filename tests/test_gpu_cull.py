@@ -6,33 +6,19 @@ in the plane of a triangle (its margin is then infinite), at a vertex, inside an
 height field, far away, several views per launch with different anchors, and a camera that
 moves between frames of one context (the anchor's records are rebuilt)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import oracle_bind
 from gp1_raytracer_2223_amd import abi
-from gp1_raytracer_2223_amd.renderer import DeviceContext
 from gp1_raytracer_2223_amd.scene import HostScene
+from gpu_support import ctx_env as _ctx_env
 
 pytestmark = pytest.mark.gpu
 
 MESH_SCENES = ["W4_Bunny", "W4_Reference", "W4_Optional", "Synthetic100k", "Bunny8Lights"]
 POW_FREE = {"W4_Bunny", "Synthetic100k", "Bunny8Lights"}
-
-
-def _ctx_env(**env):
-    saved = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return DeviceContext(int(os.environ.get("RTX_TEST_DEVICE", "0")))
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.fixture(scope="module")

@@ -10,6 +10,14 @@
  * a ray direction d inside the plane, tilted out of it by a tiny angle, and an origin o at
  * distance ~10 before P (the camera's distance).  Count float-MT acceptances and report the
  * largest exact distance (double precision) between the accepted ray's line and the triangle.
+ *
+ * usage: mt_graze_search [trials [size [tilt_decades [scale [offset [shape]]]]]]
+ *   scale   multiplies the whole construction (triangle, target offsets, the distances of the origin
+ *           and the light, the origin's offset from the plane); default 1
+ *   offset  is added to every coordinate of the triangle, and so to the rays aimed at it; default 0
+ *   shape   0: the sliver above; 1: a generic triangle, each edge component uniform in +-size;
+ *           2: a right triangle in a random orientation, legs size and size 2^-r, r uniform in [0, 20]
+ * The defaults reproduce the search as it was before these arguments existed, draw for draw.
  */
 #include <float.h>
 #include <math.h>
@@ -149,16 +157,36 @@ int main(int argc, char** argv) {
     const long trials = argc > 1 ? atol(argv[1]) : 2000000;
     const double size = argc > 2 ? atof(argv[2]) : 1.0;   /* triangle scale */
     const double tilt_decades = argc > 3 ? atof(argv[3]) : 3.0;   /* ray tilt out of the plane: 1e-7 .. 1e(-7+this) */
+    const double G = argc > 4 ? atof(argv[4]) : 1.0;              /* global scale */
+    const double off0 = argc > 5 ? atof(argv[5]) : 0.0;           /* translation of every coordinate */
+    const int shape = argc > 6 ? atoi(argv[6]) : 0;
     srand(12345);
     long acc_far[4] = {0, 0, 0, 0}, acc[4] = {0, 0, 0, 0}, viol = 0, lacc = 0, lviol = 0;
     const double Xs[4] = {0.01, 0.1, 0.5, 2.0};
     double worst[4] = {0, 0, 0, 0}, worst_ratio = 0, worst_lratio = 0, worst_dt = 0;
     for (long it = 0; it < trials; ++it) {
         /* sliver: grid triangle with a steep height step */
-        const float x0 = (float)(-3.0 + 6.0 * urand()), z0 = (float)(-1.0 + 4.0 * urand());
-        const v3 v0 = mk(x0, (float)(0.3 + 0.5 * size * urand()), z0);
-        const v3 v1 = mk(x0, (float)(0.3 + 0.5 * size * urand()), z0 + (float)(0.02 * size));
-        const v3 v2 = mk(x0 + (float)(0.024 * size), (float)(0.3 + 0.5 * size * urand()), z0);
+        const float x0 = (float)((-3.0 + 6.0 * urand()) * G + off0), z0 = (float)((-1.0 + 4.0 * urand()) * G + off0);
+        const v3 v0 = mk(x0, (float)((0.3 + 0.5 * size * urand()) * G + off0), z0);
+        v3 v1, v2;
+        if (shape == 0) {
+            v1 = mk(x0, (float)((0.3 + 0.5 * size * urand()) * G + off0), z0 + (float)(0.02 * size * G));
+            v2 = mk(x0 + (float)(0.024 * size * G), (float)((0.3 + 0.5 * size * urand()) * G + off0), z0);
+        } else if (shape == 1) {
+            float e[6];
+            for (int k = 0; k < 6; ++k) e[k] = (float)((2.0 * urand() - 1.0) * size * G);
+            v1 = mk(v0.x + e[0], v0.y + e[1], v0.z + e[2]);
+            v2 = mk(v0.x + e[3], v0.y + e[4], v0.z + e[5]);
+        } else {
+            /* two perpendicular unit vectors, the second leg 2^-r of the first */
+            d3 a = {2.0 * urand() - 1.0, 2.0 * urand() - 1.0, 2.0 * urand() - 1.0}, b = {2.0 * urand() - 1.0, 2.0 * urand() - 1.0, 2.0 * urand() - 1.0};
+            a = dsc(a, 1.0 / (dlen(a) + 1e-300));
+            b = dsub(b, dsc(a, ddot(a, b)));
+            b = dsc(b, 1.0 / (dlen(b) + 1e-300));
+            const double l1 = size * G, l2 = size * G * pow(2.0, -20.0 * urand());
+            v1 = mk(v0.x + (float)(a.x * l1), v0.y + (float)(a.y * l1), v0.z + (float)(a.z * l1));
+            v2 = mk(v0.x + (float)(b.x * l2), v0.y + (float)(b.y * l2), v0.z + (float)(b.z * l2));
+        }
         const d3 A = D(v0), B = D(v1), C = D(v2);
         d3 n = dcross(dsub(B, A), dsub(C, A));
         n = dsc(n, 1.0 / dlen(n));
@@ -168,13 +196,13 @@ int main(int argc, char** argv) {
         const int k = (int)((it >> 1) % 4);
         const double ang = 2 * M_PI * urand();
         const d3 cen = dsc(dadd(dadd(A, B), C), 1.0 / 3.0);
-        const d3 Pt = dadd(cen, dadd(dsc(t1, Xs[k] * cos(ang)), dsc(t2, Xs[k] * sin(ang))));
+        const d3 Pt = dadd(cen, dadd(dsc(t1, Xs[k] * G * cos(ang)), dsc(t2, Xs[k] * G * sin(ang))));
         const double ang2 = 2 * M_PI * urand();
         const double tilt = pow(10.0, -7.0 + tilt_decades * urand()) * (urand() < 0.5 ? -1 : 1);
         d3 dd = dadd(dadd(dsc(t1, cos(ang2)), dsc(t2, sin(ang2))), dsc(n, tilt));
         dd = dsc(dd, 1.0 / dlen(dd));
-        const double off = pow(10.0, -8.0 + 4.0 * urand()) * (urand() < 0.5 ? -1 : 1);
-        const double back = 0.5 + 12.0 * urand();
+        const double off = G * pow(10.0, -8.0 + 4.0 * urand()) * (urand() < 0.5 ? -1 : 1);
+        const double back = G * (0.5 + 12.0 * urand());
         const d3 Od = dadd(dsub(Pt, dsc(dd, back)), dsc(n, off));
         const v3 o = mk((float)Od.x, (float)Od.y, (float)Od.z);
         if (it & 1) {
@@ -216,7 +244,7 @@ int main(int argc, char** argv) {
         } else {
             /* shadow form: a light on the line beyond the target, direction and tmax as
                Renderer.cpp:130-136 computes them */
-            const double beyond = 0.1 + 8.0 * urand();
+            const double beyond = G * (0.1 + 8.0 * urand());
             const d3 Ld = dadd(Pt, dsc(dd, beyond));
             const v3 L = mk((float)Ld.x, (float)Ld.y, (float)Ld.z);
             v3 l = sub(L, o);
