@@ -102,6 +102,23 @@ class Ray(C.Structure):   # rtx_ray (rtx.h): dae::Ray{origin, direction, min, ma
     _fields_ = [("origin", F3), ("direction", F3), ("tmin", C.c_float), ("tmax", C.c_float)]
 
 
+MAX_HEAVY_TILES = 8192   # RTX_MAX_HEAVY_TILES (rtx_diag.h)
+_U32P = C.POINTER(C.c_uint32)
+
+
+class ScheduleCase(C.Structure):   # rtx_schedule_case (rtx_diag.h): host arrays of n words, was_heavy may be NULL
+    _fields_ = [("cost", _U32P), ("was_heavy", _U32P), ("saved", _U32P), ("n", C.c_uint32),
+                ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("parts", C.c_uint32),
+                ("split_slots", C.c_uint32), ("permille", C.c_uint32), ("split_min", C.c_uint32),
+                ("wave_slots", C.c_uint32), ("xcd", C.c_uint32)]
+
+
+class ScheduleResult(C.Structure):   # rtx_schedule_result (rtx_diag.h): host arrays the caller owns
+    _fields_ = [("order", _U32P), ("order_xcd", _U32P), ("cost_after", _U32P), ("saved_after", _U32P),
+                ("heavy_flag", _U32P), ("heavy_list", _U32P), ("heavy_n", C.c_uint32 * 4),
+                ("threshold", C.c_uint64)]
+
+
 XRGB8888 = (16, 8, 0, 0)
 
 
@@ -193,7 +210,7 @@ HIP_SYMBOLS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error",
                "rtx_update_shadows_async", "rtx_refresh_shadows_async", "rtx_time_shadows_update",
                "rtx_relight_resolve_async", "rtx_relight_resolve", "rtx_time_relight_resolve",
                "rtx_edit_lights", "rtx_edit_materials", "rtx_edit_light_values_device",
-               "rtx_edit_material_values_device"]
+               "rtx_edit_material_values_device", "rtx_schedule_heavy", "rtx_schedule_run"]
 
 
 def load_hip() -> C.CDLL:
@@ -285,6 +302,12 @@ def load_hip() -> C.CDLL:
         if hasattr(lib, "rtx_schedule_xcd_order"):   # absent only in older experiment builds (RTX_HIP_LIB)
             lib.rtx_schedule_xcd_order.argtypes = [VP, C.POINTER(C.c_uint32), C.c_uint32]
             lib.rtx_schedule_xcd_order.restype = C.c_int
+        if hasattr(lib, "rtx_schedule_run"):   # absent only in older experiment builds (RTX_HIP_LIB)
+            lib.rtx_schedule_heavy.argtypes = [VP, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+            lib.rtx_schedule_heavy.restype = C.c_int
+            lib.rtx_schedule_run.argtypes = [VP, C.POINTER(ScheduleCase), C.POINTER(ScheduleResult)]
+            lib.rtx_schedule_run.restype = C.c_int
         if hasattr(lib, "rtx_group_create"):   # absent only in older experiment builds
             lib.rtx_gather_async.argtypes = [VP, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
             lib.rtx_gather_async.restype = C.c_int

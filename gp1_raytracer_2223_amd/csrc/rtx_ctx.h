@@ -36,6 +36,31 @@ struct alignas(16) CullBox {
 
 static_assert(kPolicyMaxViews == kMaxViews, "rtx_policy.h's cameras per frame");
 
+namespace rtxh {
+// What the tile schedule's launches (sched_launch, rtx_sched.hip) work on: device buffers for n_tiles tiles
+// (hist: kCostBuckets per chunk of kSchedChunk tiles, csum: one per chunk, heavy_list: kMaxHeavyTiles,
+// heavy_n: 4 words, zero before the first run), and the scalars of one run.
+struct SchedBufs {
+    uint32_t* cost;              // the measured costs; zero afterwards
+    const uint32_t* was_heavy;   // the flags the measured frame was split by, or null: no tile was
+    uint32_t* saved;             // last one-piece cost per tile
+    uint32_t* hist;
+    unsigned long long* csum;
+    unsigned long long* thr;     // the heavy threshold
+    uint32_t* order;
+    uint32_t* order_xcd;         // the XCD re-deal of `order`, or null: none
+    uint32_t* heavy_flag;
+    uint32_t* heavy_list;
+    uint32_t* heavy_n;
+};
+struct SchedParams {
+    uint32_t n_tiles, tiles_x, tiles_y;
+    uint32_t parts;         // motion mode: split tiles are costed by their part waves' sum
+    uint32_t split_slots;   // effective: 0 no tile is heavy, 0xffffffff every tile is
+    uint32_t permille, split_min, wave_slots;
+};
+}  // namespace rtxh
+
 // A device buffer: its pointer and the units (elements, unless grow is told another size) it holds.
 // One constructed with rtx_ctx::bufs is the context's: rtx_destroy frees every one of those.  Explicit
 // lifetime, no destructor: a free needs the context's device current.
@@ -125,6 +150,8 @@ struct rtx_ctx {
     std::string sched_key;
     bool sched_ready = false;
     bool sched_enabled = true;
+    rtxh::SchedParams sched_params{};     // of the last measured frame's update, and the heavy set it
+    int sched_stage = 0;                  // staged (rtx_schedule_heavy)
     uint64_t sched_frame = 0;
     uint64_t scene_gen = 0;
     // split rendering of heavy tiles: double-buffered flag/list sets (HeavySet)
@@ -308,8 +335,10 @@ int cull_views(rtx_ctx* c, const FrameArgs& F);
 inline bool cull_lights_due(const rtx_ctx* c) { return c->cull_boxes_pending || c->cull_lights_dirty != 0; }
 void octant_expand(float4* nodes, uint32_t n2, uint32_t stride, hipStream_t s);
 
-// rtx_sched.hip: queue the next frames' dispatch order and heavy set from measured frame F's tile costs.
+// rtx_sched.hip: queue the next frames' dispatch order and heavy set from measured frame F's tile costs;
+// and the launches themselves, on buffers and scalars of the caller's (HIP's error, nothing of a context).
 int sched_update(rtx_ctx* c, const FrameArgs& F);
+hipError_t sched_launch(hipStream_t s, const SchedBufs& B, const SchedParams& P);
 
 // rtx_frame.hip: the launch record shared by a colour frame and the hit pass; a colour frame's
 // checks, buffers and schedule; the HSTK variant's stacks; the frame's launches (count: 0 a frame,

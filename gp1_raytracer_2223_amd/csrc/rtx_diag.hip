@@ -1,5 +1,6 @@
 // rtx_diag.hip — timing, counting and state read-outs behind the C-ABI (include/rtx.h, rtx_diag.h):
-// rtx_time_*, rtx_count_work*, the *_info getters, the cull dump, the stamp dump and the scene image.
+// rtx_time_*, rtx_count_work*, the *_info getters, the schedule's read-outs and its run on given costs, the
+// cull dump, the stamp dump and the scene image.
 #include <algorithm>
 #include <cstring>
 
@@ -104,6 +105,91 @@ extern "C" int rtx_schedule_xcd_order(rtx_ctx* c, uint32_t* order, uint32_t n) {
     if (const int rc = join_split(c); rc != RTX_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(order, c->d_order_xcd, n * 4, hipMemcpyDeviceToHost));
+    return RTX_OK;
+}
+
+static_assert(RTX_MAX_HEAVY_TILES == kMaxHeavyTiles, "rtx_diag.h's heavy list");
+
+extern "C" int rtx_schedule_heavy(rtx_ctx* c, uint32_t* heavy_flag, uint32_t n, uint32_t* heavy_list,
+                                  uint32_t heavy_n[4], uint64_t* threshold, uint32_t params[4]) {
+    if (!c) return RTX_E_INVALID;
+    if (!c->sched_ready) return fail(c, RTX_E_STATE, "no frame of the current schedule has been measured");
+    if (n > c->sched_cap) return fail(c, RTX_E_INVALID, "n exceeds the schedule size");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = join_split(c); rc != RTX_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int k = c->sched_stage;
+    if (heavy_flag) HIP_TRY(c, hipMemcpy(heavy_flag, c->d_heavy_flag[k], n * 4, hipMemcpyDeviceToHost));
+    if (heavy_list) HIP_TRY(c, hipMemcpy(heavy_list, c->d_heavy_list[k], kMaxHeavyTiles * 4, hipMemcpyDeviceToHost));
+    if (heavy_n) HIP_TRY(c, hipMemcpy(heavy_n, c->d_heavy_n, 16, hipMemcpyDeviceToHost));
+    if (threshold) HIP_TRY(c, hipMemcpy(threshold, c->d_thr, 8, hipMemcpyDeviceToHost));
+    if (params) {
+        const SchedParams& P = c->sched_params;
+        params[0] = P.split_slots; params[1] = P.permille; params[2] = P.split_min; params[3] = P.wave_slots;
+    }
+    return RTX_OK;
+}
+
+namespace {
+// rtx_schedule_run's scratch: one device allocation cut into 256-byte aligned sections, freed on return.
+struct SchedScratch {
+    char* base = nullptr;
+    size_t used = 0;
+    ~SchedScratch() { (void)hipFree(base); }
+    size_t reserve(size_t bytes) {
+        const size_t at = used;
+        used += (bytes + 255) & ~size_t(255);
+        return at;
+    }
+    template <class T>
+    T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+};
+}  // namespace
+
+extern "C" int rtx_schedule_run(rtx_ctx* c, const rtx_schedule_case* in, rtx_schedule_result* out) {
+    if (!c || !in || !out) return RTX_E_INVALID;
+    const uint32_t n = in->n;
+    const uint64_t per_view = static_cast<uint64_t>(in->tiles_x) * in->tiles_y;
+    if (n == 0 || n > (1u << 20)) return fail(c, RTX_E_INVALID, "n must be 1..2^20 tiles");
+    if (!in->cost || !in->saved || !out->order || !out->cost_after || !out->saved_after || !out->heavy_flag ||
+        !out->heavy_list || (in->xcd && !out->order_xcd))
+        return fail(c, RTX_E_INVALID, "a required array is NULL");
+    if (per_view == 0) return fail(c, RTX_E_INVALID, "tiles_x * tiles_y must not be 0");
+    if (in->xcd && n % per_view != 0) return fail(c, RTX_E_INVALID, "n must be whole views for the XCD re-deal");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // as sched_buffers (rtx_frame.hip) and rtx_create size the context's own
+    const size_t nb = static_cast<size_t>(n) * 4, nch = (n + kSchedChunk - 1) / kSchedChunk;
+    SchedScratch S;
+    const size_t o_cost = S.reserve(nb), o_was = S.reserve(nb), o_saved = S.reserve(nb), o_order = S.reserve(nb),
+                 o_xcd = S.reserve(nb), o_flag = S.reserve(nb), o_hist = S.reserve(nch * kCostBuckets * 4),
+                 o_csum = S.reserve(nch * 8), o_thr = S.reserve(8), o_list = S.reserve(kMaxHeavyTiles * 4),
+                 o_hn = S.reserve(16);
+    HIP_TRY(c, hipMalloc(&S.base, S.used));
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(S.at<char>(o_cost), in->cost, nb, hipMemcpyHostToDevice, s));
+    if (in->was_heavy) HIP_TRY(c, hipMemcpyAsync(S.at<char>(o_was), in->was_heavy, nb, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(S.at<char>(o_saved), in->saved, nb, hipMemcpyHostToDevice, s));
+    // (what a run must write reads 0xffffffff where it did not)
+    HIP_TRY(c, hipMemsetAsync(S.at<char>(o_order), 0xff, o_hist - o_order, s));
+    HIP_TRY(c, hipMemsetAsync(S.at<char>(o_thr), 0xff, o_hn - o_thr, s));
+    HIP_TRY(c, hipMemsetAsync(S.at<char>(o_hn), 0, 16, s));
+    const SchedBufs B = {S.at<uint32_t>(o_cost), in->was_heavy ? S.at<uint32_t>(o_was) : nullptr,
+                         S.at<uint32_t>(o_saved), S.at<uint32_t>(o_hist), S.at<unsigned long long>(o_csum),
+                         S.at<unsigned long long>(o_thr), S.at<uint32_t>(o_order),
+                         in->xcd ? S.at<uint32_t>(o_xcd) : nullptr, S.at<uint32_t>(o_flag), S.at<uint32_t>(o_list),
+                         S.at<uint32_t>(o_hn)};
+    const SchedParams P = {n, in->tiles_x, in->tiles_y, in->parts, in->split_slots, in->permille, in->split_min,
+                           in->wave_slots};
+    HIP_TRY(c, sched_launch(s, B, P));
+    HIP_TRY(c, hipMemcpyAsync(out->order, B.order, nb, hipMemcpyDeviceToHost, s));
+    if (in->xcd) HIP_TRY(c, hipMemcpyAsync(out->order_xcd, B.order_xcd, nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out->cost_after, B.cost, nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out->saved_after, B.saved, nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out->heavy_flag, B.heavy_flag, nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out->heavy_list, B.heavy_list, kMaxHeavyTiles * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out->heavy_n, B.heavy_n, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&out->threshold, B.thr, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
     return RTX_OK;
 }
 

@@ -24,7 +24,7 @@ __device__ __forceinline__ uint32_t cost_class(uint32_t cst) {   // heavier -> s
     const uint32_t lg = cst ? 32u - static_cast<uint32_t>(__builtin_clz(cst)) : 0u;   // 0..32
     const uint32_t half = (cst && lg >= 2) ? ((cst >> (lg - 2)) & 1u) : 0u;
     uint32_t k = 2u * lg + half;                                                     // 0..65
-    k = k > 2u * 6u ? k - 2u * 6u : 0u;        // costs below 2^6 (x16 cycles) share a class
+    k = k > 2u * 6u ? k - 2u * 6u : 0u;        // costs below 48 (x16 cycles) share the last class
     return (kCostBuckets - 1) - (k < kCostBuckets ? k : kCostBuckets - 1);
 }
 
@@ -267,6 +267,28 @@ __global__ void __launch_bounds__(kScanThreads) rtx_sched_xcd(const uint32_t* __
 
 namespace rtxh {
 
+// The schedule's launches, the only place that queues them: count, scan, scatter and, with an
+// `order_xcd`, the XCD re-deal, on stream `s`.  Nothing of a context is read: a frame's update
+// (sched_update) and the diagnostics' run on given costs (rtx_schedule_run) both come through here.
+hipError_t sched_launch(hipStream_t s, const SchedBufs& B, const SchedParams& P) {
+    const uint32_t nch = (P.n_tiles + kSchedChunk - 1) / kSchedChunk;
+    hipLaunchKernelGGL(rtx_sched_count, dim3(nch), dim3(kReorderThreads), 0, s, B.cost, P.n_tiles, B.was_heavy,
+                       B.saved, B.hist, B.csum, nch, P.parts, B.heavy_n + 1);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(rtx_sched_scan, dim3(1), dim3(kScanThreads), 0, s, B.hist, nch, B.csum, P.n_tiles,
+                       P.split_slots, P.permille, P.split_min, P.wave_slots, B.thr, B.heavy_n);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(rtx_sched_scatter, dim3(nch), dim3(kReorderThreads), 0, s, B.cost, B.order, P.n_tiles, B.hist,
+                       nch, B.thr, P.split_slots == 0xffffffffu ? 1u : 0u, B.heavy_flag, B.heavy_list, B.heavy_n);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (B.order_xcd) {
+        hipLaunchKernelGGL(rtx_sched_xcd, dim3(1), dim3(kScanThreads), 0, s, B.order, B.order_xcd, P.n_tiles,
+                           P.tiles_x, P.tiles_y);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 int sched_update(rtx_ctx* c, const FrameArgs& F) {
     const uint32_t slots = (c->split_mode == 0 || !c->facts.split_ok) ? 0u
                            : (c->split_mode == 2 ? 0xffffffffu : c->split_slots);
@@ -275,23 +297,12 @@ int sched_update(rtx_ctx* c, const FrameArgs& F) {
     const uint32_t permille = c->concurrent ? std::max<uint32_t>(c->tuner.permille, kThroughputPermille)
                                             : c->tuner.permille;
     c->heavy.permille[stage] = permille;
-    const uint32_t nch = (F.n_tiles + kSchedChunk - 1) / kSchedChunk;
-    hipLaunchKernelGGL(rtx_sched_count, dim3(nch), dim3(kReorderThreads), 0, c->stream, F.cost, F.n_tiles,
-                       F.heavy_flag, c->d_saved_cost, c->d_hist, c->d_csum, nch, F.part_cost, c->d_heavy_n + 1);
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(rtx_sched_scan, dim3(1), dim3(kScanThreads), 0, c->stream, c->d_hist, nch,
-                       c->d_csum,
-                       F.n_tiles, slots, permille, c->split_min, c->split_slots, c->d_thr, c->d_heavy_n);
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(rtx_sched_scatter, dim3(nch), dim3(kReorderThreads), 0, c->stream, F.cost, c->d_order,
-                       F.n_tiles, c->d_hist, nch, c->d_thr, slots == 0xffffffffu ? 1u : 0u,
-                       c->d_heavy_flag[stage], c->d_heavy_list[stage], c->d_heavy_n);
-    HIP_TRY(c, hipGetLastError());
-    if (c->xcd_order) {
-        hipLaunchKernelGGL(rtx_sched_xcd, dim3(1), dim3(kScanThreads), 0, c->stream, c->d_order, c->d_order_xcd,
-                           F.n_tiles, F.tiles_x, F.tiles_y);
-        HIP_TRY(c, hipGetLastError());
-    }
+    c->sched_stage = stage;
+    c->sched_params = {F.n_tiles, F.tiles_x, F.tiles_y, F.part_cost, slots, permille, c->split_min, c->split_slots};
+    const SchedBufs B = {F.cost, F.heavy_flag, c->d_saved_cost, c->d_hist, c->d_csum, c->d_thr, c->d_order,
+                         c->xcd_order ? c->d_order_xcd.get() : nullptr, c->d_heavy_flag[stage], c->d_heavy_list[stage],
+                         c->d_heavy_n};
+    HIP_TRY(c, sched_launch(c->stream, B, c->sched_params));
     HIP_TRY(c, hipMemcpyAsync(c->h_heavy_n, c->d_heavy_n, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_heavy, c->stream));
     c->heavy.pending = true;

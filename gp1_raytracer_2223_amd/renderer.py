@@ -398,6 +398,49 @@ class DeviceContext:
         self._call("rtx_split_info", C.byref(h), C.byref(p))
         return h.value, p.value
 
+    def schedule_state(self, n: int):
+        """(order, cost) of the first n tiles after a measured frame (rtx_schedule_state): the dispatch
+        permutation and the one-piece tile costs it was sorted by."""
+        order, cost, tiles = np.zeros(n, np.uint32), np.zeros(n, np.uint32), C.c_uint32()
+        self._call("rtx_schedule_state", _u32p(order), _u32p(cost), int(n), C.byref(tiles))
+        if tiles.value < n:
+            raise RuntimeError(f"rtx_schedule_state: the schedule holds {tiles.value} tiles, {n} asked for")
+        return order, cost
+
+    def schedule_heavy(self, n: int) -> dict:
+        """What the last measured frame selected (rtx_schedule_heavy): the heavy flags of the first n tiles,
+        the heavy list, the four counter words, the threshold and the scalars the update ran with."""
+        flag, lst = np.zeros(n, np.uint32), np.zeros(abi.MAX_HEAVY_TILES, np.uint32)
+        hn, thr, par = (C.c_uint32 * 4)(), C.c_uint64(), (C.c_uint32 * 4)()
+        self._call("rtx_schedule_heavy", _u32p(flag), int(n), _u32p(lst), hn, C.byref(thr), par)
+        return {"heavy_flag": flag, "heavy_list": lst, "heavy_n": [int(v) for v in hn], "threshold": thr.value,
+                "split_slots": par[0], "permille": par[1], "split_min": par[2], "wave_slots": par[3]}
+
+    def schedule_run(self, cost, saved, was_heavy=None, *, tiles_x: int, tiles_y: int, parts: int = 0,
+                     split_slots: int, permille: int, split_min: int, wave_slots: int, xcd: bool = False) -> dict:
+        """The schedule kernels on given costs (rtx_schedule_run): uint32 arrays of n tiles in, the order, the
+        XCD order when asked for, costs and saved costs afterwards, heavy flags, list, counter words and
+        threshold out.  Nothing of the context's own schedule is touched."""
+        cost, saved = np.ascontiguousarray(cost, np.uint32), np.ascontiguousarray(saved, np.uint32)
+        n = cost.size
+        if was_heavy is not None:
+            was_heavy = np.ascontiguousarray(was_heavy, np.uint32)
+        if saved.size != n or (was_heavy is not None and was_heavy.size != n):
+            raise ValueError("cost, saved and was_heavy must have one word per tile")
+        case = abi.ScheduleCase(_u32p(cost), _u32p(was_heavy) if was_heavy is not None else None, _u32p(saved), n,
+                                int(tiles_x), int(tiles_y), int(parts), int(split_slots), int(permille),
+                                int(split_min), int(wave_slots), int(bool(xcd)))
+        out = {k: np.zeros(n, np.uint32) for k in ("order", "cost_after", "saved_after", "heavy_flag")}
+        out["order_xcd"] = np.zeros(n, np.uint32) if xcd else None
+        out["heavy_list"] = np.zeros(abi.MAX_HEAVY_TILES, np.uint32)
+        res = abi.ScheduleResult(_u32p(out["order"]), _u32p(out["order_xcd"]) if xcd else None,
+                                 _u32p(out["cost_after"]), _u32p(out["saved_after"]), _u32p(out["heavy_flag"]),
+                                 _u32p(out["heavy_list"]))
+        self._call("rtx_schedule_run", C.byref(case), C.byref(res))
+        out["heavy_n"] = [int(v) for v in res.heavy_n]
+        out["threshold"] = int(res.threshold)
+        return out
+
     def split_tune_info(self) -> dict:
         """The split threshold's tuner: factor, last timed main kernel / split chain (ms), state."""
         f, m, ch, d = C.c_float(), C.c_float(), C.c_float(), C.c_uint32()

@@ -148,6 +148,49 @@ int rtx_schedule_state(rtx_ctx* ctx, uint32_t* order, uint32_t* cost, uint32_t n
  * re-dealt by rtx_sched_xcd.  RTX_E_STATE when the context has no XCD order (the knob is off, or no
  * frame of the current schedule has been measured yet). */
 int rtx_schedule_xcd_order(rtx_ctx* ctx, uint32_t* order, uint32_t n);
+/* Diagnostics of the heavy set (tests): what the last measured frame's schedule update selected.  Joins as
+ * rtx_schedule_state does, then copies out the heavy flags of the first n tiles (the set that update
+ * staged, adopted since or not), its heavy list (RTX_MAX_HEAVY_TILES words; the entries past the count
+ * are stale), the four counter words {heavy tiles (not clamped), 0, largest tile cost, cost per wave
+ * slot}, the heavy threshold, and the scalars the update ran with: {effective split slots (0 no tile is
+ * heavy, 0xffffffff every tile is), split permille, least split cost, wave slots}.  Null pointers are
+ * skipped.  RTX_E_STATE when no frame of the current schedule has been measured, RTX_E_INVALID when n
+ * exceeds the schedule size. */
+#define RTX_MAX_HEAVY_TILES 8192
+int rtx_schedule_heavy(rtx_ctx* ctx, uint32_t* heavy_flag, uint32_t n, uint32_t* heavy_list, uint32_t heavy_n[4],
+                       uint64_t* threshold, uint32_t params[4]);
+/* Diagnostics of the schedule kernels (tests): run the launches that a measured frame queues (count,
+ * scan, scatter and, with `xcd`, the XCD re-deal) on costs of the caller's.  All arrays are host memory.
+ * The run uses scratch device buffers of its own on the context's device, initialised like a fresh
+ * launch shape's, queues on the context stream, waits, copies out and frees: no schedule, policy or
+ * heavy-set state of the context is read or written, and its frames are unchanged.
+ * RTX_E_INVALID, before any device work: a NULL case, result or required array (was_heavy may be NULL: no
+ * tile was split; order_xcd only with `xcd`), n == 0 or above 2^20, tiles_x * tiles_y == 0, or with
+ * `xcd` an n that is no multiple of tiles_x * tiles_y. */
+typedef struct rtx_schedule_case {
+    const uint32_t* cost;        /* [n] the measured tile costs */
+    const uint32_t* was_heavy;   /* [n] non-zero: the tile was rendered split; or NULL */
+    const uint32_t* saved;       /* [n] the last one-piece cost per tile */
+    uint32_t n;                  /* tiles */
+    uint32_t tiles_x, tiles_y;   /* tiles per view (the XCD re-deal's blocks) */
+    uint32_t parts;              /* motion mode: split tiles are sorted by cost, not by saved */
+    uint32_t split_slots;        /* effective: 0 no tile is heavy, 0xffffffff every tile is */
+    uint32_t permille;
+    uint32_t split_min;
+    uint32_t wave_slots;
+    uint32_t xcd;                /* non-zero: the XCD re-deal too */
+} rtx_schedule_case;
+typedef struct rtx_schedule_result {
+    uint32_t* order;             /* [n] */
+    uint32_t* order_xcd;         /* [n], with `xcd` */
+    uint32_t* cost_after;        /* [n] */
+    uint32_t* saved_after;       /* [n] */
+    uint32_t* heavy_flag;        /* [n] */
+    uint32_t* heavy_list;        /* [RTX_MAX_HEAVY_TILES]; 0xffffffff past the entries written */
+    uint32_t heavy_n[4];
+    uint64_t threshold;
+} rtx_schedule_result;
+int rtx_schedule_run(rtx_ctx* ctx, const rtx_schedule_case* in, rtx_schedule_result* out);
 
 /* Diagnostics: 128 status words of the last update of registered mesh i (0-3 as above,
  * 4-6 subtrees / task-split ids / nodes split as tasks, 8-27 phase stamps of the device build
